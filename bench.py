@@ -11,16 +11,23 @@ in HBM.
   Every N          the SAME workload: BASELINE config 3 (BigGAN-128, ch 96, bf16 - the north star's target) at its FIXED
                    global batch 256, 256 / N images per rank, "scaling": "strong" - so the driver's N = 1, 2, 4, 8 lines
                    are one series.  (--scaling weak keeps 32 images per rank instead.)
-  N = 1 (default)  additionally carries `fp32_config2` (BASELINE config 2: ch 64, batch 64, fp32 - the reference's
-                   precision - with its own roofline), the --g_regularization none / --da_policy "" companions of
-                   SURVEY.md section 8(d), the 32-image share one of 8 ranks runs, and the CPU baseline.
+  N = 1 (default)  with --full additionally carries `fp32_config2` (BASELINE config 2: ch 64, batch 64, fp32 - the
+                   reference's precision - with its own roofline), the --g_regularization none / --da_policy ""
+                   companions of SURVEY.md section 8(d), the 32-image share one of 8 ranks runs, and the CPU baseline.
   `--gpus N` without torchrun's environment starts the N ranks itself (one process per GPU, RCCL) before any GPU call
   and relays rank 0's line; under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.
 
-Prints ONE JSON line on rank 0 with the throughput, the MFMA roofline of the convolution / attention GEMM launches
-(timed with HIP events on their stream in a second pass over the same steps; algorithmic FLOPs only - the
-regulariser's Gram matrices and dense layers are excluded) and a CPU baseline: the oracle (a torch-CPU restatement,
-"port" - TensorFlow is not available) timed on this host's cores on a bounded sample.
+Prints ONE JSON line on rank 0 with the throughput (`value`) and `ms_per_step`.  A plain run does nothing else: it
+builds the model, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the MFMA
+roofline of the convolution / attention GEMM launches (timed with HIP events on their stream in a second pass over
+the same steps; algorithmic FLOPs only - the regulariser's Gram matrices and dense layers are excluded), the N = 1
+companions above and a CPU baseline: the oracle (a torch-CPU restatement, "port" - TensorFlow is not available) timed
+on this host's cores on a bounded sample.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): its losses and the state it leaves - live
+weights of both networks and the generator's EMA shadows, each a fixed seeded sample when larger than 4 Mi elements -
+as float32 DIR/<name>.npy.  Inputs are seeded and the step's cross-block sums add in a fixed order, so runs with the
+same arguments compute the same step and two builds can be compared array for array.
 """
 import argparse
 import collections
@@ -269,8 +276,51 @@ def roofline_pass(gan, real, nsteps, peak, fpi, B, ms_per_step, workload):
     return out
 
 
-def run_workload(name, B, a, world, rank, note, extra=(), steps=None, warmup=None, roofline=True, graph=False):
-    """Build the model for one workload, time `steps` iterations, optionally the roofline pass.  Returns a dict."""
+DUMP_ELEMS = 1 << 22       # per state array of --dump-outputs: 4 Mi float32 = 16 MiB, three of them stay under 64 MB
+DUMP_SEED = 20240601
+
+
+def sample_flat(tensors, cap=None, seed=DUMP_SEED):
+    """`tensors` flattened and concatenated in the given order, as a float32 numpy array: all of it when it has at most
+    `cap` (default DUMP_ELEMS) elements, else the elements at a fixed seeded set of at most `cap` sorted positions."""
+    import numpy as np
+    import torch
+    cap = cap or DUMP_ELEMS
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    if flat.numel() > cap:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), cap))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy().astype(np.float32, copy=False)
+
+
+def dump_outputs(gan, losses, out_dir, rank=0):
+    """--dump-outputs: what one training step hands back - its losses - and the state it leaves behind - the live weights
+    of both networks (spectral-norm vectors and batch-norm statistics included) and the generator's EMA shadows -
+    as DIR/<name>.npy (float32).  Collective under data parallelism (the sharded EMA is gathered first); rank 0 writes."""
+    import numpy as np
+    gan.sync_sharded_state()
+    if rank != 0:
+        return []
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = collections.OrderedDict()
+    for k, v in sorted(losses.items()):
+        arrays[k] = v.detach().reshape(-1).float().cpu().numpy()
+    state = gan.state_tensors()
+    for net in ("generator", "discriminator"):
+        names = sorted(k for k in gan.store.vars if k.startswith(net + "/"))
+        arrays[net + "_weights"] = sample_flat([state[k] for k in names])
+    ema = sorted(k for k in state if k.endswith("/ExponentialMovingAverage"))
+    if ema:
+        arrays["generator_ema"] = sample_flat([state[k] for k in ema])
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    return list(arrays)
+
+
+def run_workload(name, B, a, world, rank, note, extra=(), steps=None, warmup=None, roofline=True, graph=False,
+                 dump_dir=None):
+    """Build the model for one workload, time `steps` iterations, optionally dump what the last one computed
+    (`dump_dir`), optionally the roofline pass.  Returns a dict."""
     import gc
     import torch
     from biggan_tensorflow_amd import main as M, model, scope as S
@@ -314,6 +364,9 @@ def run_workload(name, B, a, world, rank, note, extra=(), steps=None, warmup=Non
     ms_per_step = dt / steps * 1e3
     value = B * world * steps / dt
     note("%s: timed %d steps: %.1f ms/step, %.1f images/sec" % (name, steps, ms_per_step, value))
+    if dump_dir:                       # before anything else runs a step on this model
+        written = dump_outputs(gan, losses, dump_dir, rank)
+        note("%s: outputs of the last timed step written to %s: %s" % (name, dump_dir, ", ".join(written)))
     fpi, _, _ = step_flops_per_image(img, ch)
     out = {"workload": desc, "img_size": img, "ch": ch, "per_gpu_batch": B, "global_batch": B * world,
            "precision": precision, "dtype": "f32" if precision == "fp32" else "bf16",
@@ -379,10 +432,10 @@ def dry_run(a, rank, world):
         torch.distributed.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", type=str, default="", choices=[""] + sorted(WORKLOADS),
                     help="default: c3 = BASELINE config 3 at its fixed global batch 256 split over the ranks")
@@ -397,13 +450,28 @@ def main():
                     help="BASELINE's configs use hinge; e.g. ra-dragan (the reference's default) adds the gradient penalty")
     ap.add_argument("--precision", type=str, default="", help="override: fp32 | bf16-staged | bf16")
     ap.add_argument("--graph", action="store_true", help="replay the iteration from captured HIP graphs (N=1 only)")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: the roofline pass, the CPU baseline and, for "
+                         "the N = 1 default run, fp32_config2, the two SURVEY 8(d) companions and the 32-image share")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default="",
+                    help="write the losses and (a fixed seeded sample of) the state left by the last timed step as "
+                         "DIR/<name>.npy, float32")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no_roofline", action="store_true", help="--full without the roofline pass")
     ap.add_argument("--no_companions", action="store_true",
-                    help="N = 1 default run: only the headline (skip fp32_config2, the two SURVEY 8(d) companions and the "
-                         "32-image share)")
+                    help="--full N = 1 default run: skip fp32_config2, the two SURVEY 8(d) companions and the 32-image "
+                         "share")
     ap.add_argument("--dry_run", action="store_true", help=argparse.SUPPRESS)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+def main():
+    a = parse_args()
 
     if a.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(a.gpus, sys.argv[1:]))      # (nothing in this process has touched a GPU yet)
@@ -432,10 +500,11 @@ def main():
     if a.graph and world != 1:
         raise SystemExit("--graph is a single-process option (RCCL collectives cannot be captured on this stack: "
                          "tools/rccl_graph_probe.py aborts)")
-    res = run_workload(name, B, a, world, rank, note, roofline=not a.no_roofline, graph=a.graph)
+    res = run_workload(name, B, a, world, rank, note, roofline=a.full and not a.no_roofline, graph=a.graph,
+                       dump_dir=a.dump_outputs)
 
     companions = fp32_c2 = per32 = None
-    if default_run and world == 1 and not a.no_companions and not a.graph:
+    if a.full and default_run and world == 1 and not a.no_companions and not a.graph:
         # the two companions SURVEY 8(d) asks for, one rank's 32-image share of the 8-GPU run, and BASELINE config 2
         # (the reference's precision) with its own roofline
         companions = {}
@@ -454,7 +523,7 @@ def main():
                    "losses": c2["losses"]}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         sb = {64: 32, 128: 8 if ch <= 64 else 4, 256: 2}.get(img, 1)      # ~10-30 s of CPU work on 16 cores
         note("cpu baseline (oracle, batch %d) ..." % sb)
         cpu = cpu_baseline(img, ch, sb, 2 if img <= 128 else 1, note)

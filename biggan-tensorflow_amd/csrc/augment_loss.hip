@@ -33,7 +33,7 @@ __device__ __forceinline__ void da_color_pre(float (&v)[DA_MAXC], int C, float u
 }
 
 // per-sample sum of the brightness/saturation-adjusted image (reduce_mean of rand_contrast, :35)
-__global__ __launch_bounds__(AL_BLOCK) void da_mean_kernel(const float* __restrict__ x, DaArgs a, double* sums) {
+__global__ __launch_bounds__(AL_BLOCK) void da_mean_kernel(const float* __restrict__ x, DaArgs a, double* sums, double* part) {
     __shared__ float sh[4];
     const int n = blockIdx.y;
     const int64_t px = (int64_t)a.S * a.S;
@@ -50,7 +50,23 @@ __global__ __launch_bounds__(AL_BLOCK) void da_mean_kernel(const float* __restri
             if (c < a.C) s += v[c];
     }
     s = block_sum_256(s, sh);
-    if (threadIdx.x == 0) atomicAdd(&sums[n], (double)s);     // fp64: order-independent to ~1e-16
+    if (threadIdx.x == 0) {
+        if (part)
+            part[(int64_t)n * gridDim.x + blockIdx.x] = (double)s;
+        else
+            sums[n] += (double)s;                                  // (the image's only block)
+    }
+}
+
+// sums[n] += the nb per-block sums of image n, added in block order (da_mean_kernel / da_bwd_sum_kernel: the sums do
+// not depend on the order the blocks finish in)
+__global__ __launch_bounds__(AL_BLOCK) void da_sums_finalize_kernel(const double* __restrict__ part, double* sums, int N,
+                                                                      int nb) {
+    const int n = blockIdx.x * AL_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    double acc = 0.0;
+    for (int b = 0; b < nb; ++b) acc += part[(int64_t)n * nb + b];
+    sums[n] += acc;
 }
 
 __device__ __forceinline__ bool da_cut(const DaArgs& a, int n, int i, int j) {
@@ -113,7 +129,7 @@ __device__ __forceinline__ bool da_bwd_src(const DaArgs& a, int n, int p, int q,
     return true;
 }
 
-__global__ __launch_bounds__(AL_BLOCK) void da_bwd_sum_kernel(const float* __restrict__ dy, DaArgs a, double* sums) {
+__global__ __launch_bounds__(AL_BLOCK) void da_bwd_sum_kernel(const float* __restrict__ dy, DaArgs a, double* sums, double* part) {
     __shared__ float sh[4];
     const int n = blockIdx.y;
     const int64_t px = (int64_t)a.S * a.S;
@@ -128,7 +144,12 @@ __global__ __launch_bounds__(AL_BLOCK) void da_bwd_sum_kernel(const float* __res
         }
     }
     s = block_sum_256(s, sh);
-    if (threadIdx.x == 0) atomicAdd(&sums[n], (double)s);
+    if (threadIdx.x == 0) {
+        if (part)
+            part[(int64_t)n * gridDim.x + blockIdx.x] = (double)s;
+        else
+            sums[n] += (double)s;                                  // (the image's only block)
+    }
 }
 
 __global__ __launch_bounds__(AL_BLOCK) void da_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, DaArgs a,
@@ -640,8 +661,12 @@ int bg_diffaugment_fwd(const float* x, float* y, const float* u_b, const float* 
             return BG_ERR_LAUNCH;
         }
         int bx = (int)((px + AL_BLOCK * 8 - 1) / (AL_BLOCK * 8));
-        if (bx < 1) bx = 1;
-        hipLaunchKernelGGL(da_mean_kernel, dim3(bx, N), dim3(AL_BLOCK), 0, s, x, a, mean_ws);
+        double* part = bx > 1 ? reinterpret_cast<double*>(colreduce_workspace(2 * (size_t)N * bx, s)) : nullptr;
+        if (bx > 1 && !part) return BG_ERR_LAUNCH;
+        hipLaunchKernelGGL(da_mean_kernel, dim3(bx, N), dim3(AL_BLOCK), 0, s, x, a, mean_ws, part);
+        if (part)
+            hipLaunchKernelGGL(da_sums_finalize_kernel, dim3((N + AL_BLOCK - 1) / AL_BLOCK), dim3(AL_BLOCK), 0, s, part,
+                               mean_ws, N, bx);
         BG_LAUNCH_CHECK();
     }
     int64_t blocks = ((int64_t)N * px + AL_BLOCK - 1) / AL_BLOCK;
@@ -668,8 +693,12 @@ int bg_diffaugment_bwd(const float* dy, float* dx, const float* u_s, const float
             return BG_ERR_LAUNCH;
         }
         int bx = (int)((px + AL_BLOCK * 8 - 1) / (AL_BLOCK * 8));
-        if (bx < 1) bx = 1;
-        hipLaunchKernelGGL(da_bwd_sum_kernel, dim3(bx, N), dim3(AL_BLOCK), 0, s, dy, a, mean_ws);
+        double* part = bx > 1 ? reinterpret_cast<double*>(colreduce_workspace(2 * (size_t)N * bx, s)) : nullptr;
+        if (bx > 1 && !part) return BG_ERR_LAUNCH;
+        hipLaunchKernelGGL(da_bwd_sum_kernel, dim3(bx, N), dim3(AL_BLOCK), 0, s, dy, a, mean_ws, part);
+        if (part)
+            hipLaunchKernelGGL(da_sums_finalize_kernel, dim3((N + AL_BLOCK - 1) / AL_BLOCK), dim3(AL_BLOCK), 0, s, part,
+                               mean_ws, N, bx);
         BG_LAUNCH_CHECK();
     }
     int64_t blocks = ((int64_t)N * px + AL_BLOCK - 1) / AL_BLOCK;

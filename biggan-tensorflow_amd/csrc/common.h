@@ -10,6 +10,11 @@
 namespace bg {
 
 void set_error(const char* fmt, ...);
+// per-device scratch of per-block partial sums for deterministic reductions (elementwise.hip); nullptr (with the
+// error set) when it cannot be had
+float* colreduce_workspace(size_t n_floats, hipStream_t s);
+// true once after a launcher that cannot return a status skipped its launch for want of that workspace
+bool take_workspace_error();
 
 #define BG_REQUIRE(cond, ...)                         \
     do {                                              \
@@ -27,6 +32,7 @@ void set_error(const char* fmt, ...);
                           hipGetErrorString(e__));                               \
             return BG_ERR_LAUNCH;                                                \
         }                                                                        \
+        if (bg::take_workspace_error()) return BG_ERR_LAUNCH;                    \
     } while (0)
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

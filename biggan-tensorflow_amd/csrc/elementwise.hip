@@ -3,6 +3,7 @@
 // elementwise ops, bias gradient, fused TF-Adam + EMA.  16-byte vector accesses, wave64 shuffle
 // reductions, grid-stride loops capped at 2048 blocks (256 CUs x 8).
 #include <stdlib.h>
+#include <mutex>
 #include "common.h"
 
 namespace bg {
@@ -23,11 +24,14 @@ __device__ __forceinline__ void stg4(float* p, const float4& v) { *reinterpret_c
 // ==========================================================================================
 // column-reduction skeleton: rows x C matrix (optionally segmented by blockIdx.y), each thread owns
 // VEC consecutive columns and a strided subset of the block's rows; NQ quantities are reduced
-// over rows, combined across the block's row-lanes through LDS and added to out[q*qstride + seg*C + c]
-// with one float atomic per column per block.
+// over rows and combined across the block's row-lanes through LDS.  Deterministic: with one block per segment the
+// block adds its sums to out[q*qstride + seg*C + c] itself; with several, every block stores its sums in
+// part[((seg*gridDim.x + block)*NQ + q)*C + c] and colreduce_finalize_kernel adds them up in a fixed order.  (Float
+// atomics here made the sums depend on the order blocks finished in; a gradient that is zero in exact arithmetic -
+// the attention f_conv bias - then changed sign from run to run, and Adam's first step turns a sign into +-lr.)
 // ==========================================================================================
 template <int NQ, int VEC, class Fn, class OutT>
-__global__ __launch_bounds__(EW_BLOCK) void colreduce_kernel(Fn fn, OutT* out, int64_t qstride,
+__global__ __launch_bounds__(EW_BLOCK) void colreduce_kernel(Fn fn, OutT* out, float* part, int64_t qstride,
                                                              int64_t rows_per_seg, int C, int rows_per_block) {
     __shared__ float red[NQ * EW_BLOCK * VEC];   // VEC*NQ floats per thread
     const int CV = C / VEC;                      // vector columns
@@ -79,11 +83,121 @@ __global__ __launch_bounds__(EW_BLOCK) void colreduce_kernel(Fn fn, OutT* out, i
                 for (int j = 0; j < VEC; ++j) {
                     float s = 0.f;
                     for (int l = 0; l < lanes; ++l) s += red[(q * VEC + j) * EW_BLOCK + l * tx + cq];
-                    atomicAdd(&out[q * qstride + (int64_t)seg * C + cv * VEC + j], (OutT)s);
+                    if (part)
+                        part[(((int64_t)seg * gridDim.x + blockIdx.x) * NQ + q) * C + cv * VEC + j] = s;
+                    else       // the only block of its segment: no other thread writes this element
+                        out[q * qstride + (int64_t)seg * C + cv * VEC + j] += (OutT)s;
                 }
         }
         __syncthreads();
     }
+}
+
+// out[q*qstride + seg*C + c] += the nblk partial sums of part (layout above).  A block takes CRF_COLS outputs; group g
+// of its threads adds partials g, g + CRF_GROUPS, ... (independent loads in flight), and the groups' sums are added in
+// group order: a fixed order, whatever the timing.
+#define CRF_COLS 16
+#define CRF_GROUPS (EW_BLOCK / CRF_COLS)
+template <int NQ, class OutT>
+__global__ __launch_bounds__(EW_BLOCK) void colreduce_finalize_kernel(const float* __restrict__ part, OutT* out,
+                                                                      int64_t qstride, int nseg, int C, int nblk) {
+    __shared__ double red[CRF_GROUPS][CRF_COLS];
+    const int cl = threadIdx.x % CRF_COLS, g = threadIdx.x / CRF_COLS;
+    const int64_t total = (int64_t)nseg * NQ * C;
+    const int64_t i = (int64_t)blockIdx.x * CRF_COLS + cl;     // output (seg, q, c), flattened
+    int64_t seg = 0;
+    int q = 0, c = 0;
+    double acc = 0.0;
+    if (i < total) {
+        c = (int)(i % C);
+        q = (int)((i / C) % NQ);
+        seg = i / ((int64_t)NQ * C);
+        const float* p = part + (seg * nblk * NQ + q) * C + c;
+        const int64_t st = (int64_t)NQ * C;
+#pragma unroll 4
+        for (int b = g; b < nblk; b += CRF_GROUPS) acc += (double)p[b * st];
+    }
+    red[g][cl] = acc;
+    __syncthreads();
+    if (g == 0 && i < total) {
+        double sum = 0.0;
+        for (int k = 0; k < CRF_GROUPS; ++k) sum += red[k][cl];
+        out[q * qstride + seg * C + c] += (OutT)sum;
+    }
+}
+
+static inline dim3 crf_grid(int64_t outputs) { return dim3((unsigned)((outputs + CRF_COLS - 1) / CRF_COLS)); }
+
+// Workspace of the per-block partial sums, one per device (at least 4 MB), handed out under a
+// lock.  Every launch that uses it is ordered after the previous one on the calling stream: the host code enqueues on
+// one stream at a time (torch's current stream; the side stream of BigGAN.capture_graphs' warm-up is joined before
+// the capture).  A larger request grows it outside stream capture; the old buffer is freed after a device
+// synchronisation unless a graph captured since its allocation may still hold its address - then it is kept.  A
+// request that needs growth DURING capture, or a failed allocation, is an error (no quiet change of the reduction):
+// the captured step has run eagerly before (capture_graphs does), so its shapes are already covered.
+static thread_local bool g_ws_error = false;
+bool take_workspace_error() {
+    const bool e = g_ws_error;
+    g_ws_error = false;
+    return e;
+}
+
+float* colreduce_workspace(size_t n, hipStream_t s) {
+    static std::mutex mu;
+    static float* ws[64];
+    static size_t cap[64];
+    static bool captured[64];      // ws[dev] was handed to a stream capture
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        set_error("deterministic reduction: no current device");
+        return nullptr;
+    }
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+        set_error("deterministic reduction: cannot query the stream's capture status");
+        return nullptr;
+    }
+    const bool capturing = st != hipStreamCaptureStatusNone;
+    if (n <= cap[dev]) {
+        captured[dev] = captured[dev] || capturing;
+        return ws[dev];
+    }
+    if (capturing) {
+        set_error("deterministic reduction: %zu floats of partial sums needed during stream capture, %zu reserved "
+                  "(run the captured step once eagerly first)", n, cap[dev]);
+        return nullptr;
+    }
+    size_t want = n > 2 * cap[dev] ? n : 2 * cap[dev];
+    if (want < (size_t(1) << 20)) want = size_t(1) << 20;
+    float* p = nullptr;
+    if (hipMalloc(&p, want * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("deterministic reduction: hipMalloc of %zu bytes of partial sums failed", want * sizeof(float));
+        return nullptr;
+    }
+    if (ws[dev] && !captured[dev]) {
+        (void)hipDeviceSynchronize();            // earlier launches may still read or write it
+        (void)hipFree(ws[dev]);
+    }
+    ws[dev] = p;
+    cap[dev] = want;
+    captured[dev] = false;
+    return p;
+}
+
+// Kernels that end with one sum per block and column (dot products, the thin PReLU slope gradient) store it in
+// part[block * C + c] and colreduce_finalize_kernel adds them up in a fixed order, as in launch_colreduce.  *part is
+// nullptr for a single block (it adds to the output itself); false: no workspace, the error is set.
+static bool block_partials(int grid, int C, hipStream_t s, float** part) {
+    *part = grid > 1 ? colreduce_workspace((size_t)grid * C, s) : nullptr;
+    return grid <= 1 || *part;
+}
+
+static void finalize_block_partials(const float* part, float* out, int grid, int C, hipStream_t s) {
+    if (part)
+        hipLaunchKernelGGL((colreduce_finalize_kernel<1, float>), crf_grid(C), dim3(EW_BLOCK), 0, s, part, out,
+                           (int64_t)0, 1, C, grid);
 }
 
 // WIDE: 8 columns per thread when C % 8 == 0 - the 16-byte loads of a bf16 tensor (4 columns would be 8-byte loads and
@@ -91,9 +205,8 @@ __global__ __launch_bounds__(EW_BLOCK) void colreduce_kernel(Fn fn, OutT* out, i
 template <int NQ, bool WIDE = false, class Fn, class OutT>
 static void launch_colreduce(Fn fn, OutT* out, int64_t qstride, int64_t rows_per_seg, int nseg, int C,
                              hipStream_t s) {
-    // Every block ends with one atomic per column on the SAME addresses, and those serialise (~0.1 us per
-    // block, measured: 1024 blocks = 105 us whatever the tensor size).  192 blocks x 4 loads in flight per
-    // thread already cover the HBM bandwidth-delay product (268 MB in 55 us = 4.9 TB/s); 128 for < 100 MB.
+    // 192 blocks x 4 loads in flight per thread already cover the HBM bandwidth-delay product (268 MB in 55 us =
+    // 4.9 TB/s); 128 for < 100 MB.  (Sized when every block ended in same-address atomics, which serialised.)
     static const int env_blocks = getenv("BG_COLRED_BLOCKS") ? atoi(getenv("BG_COLRED_BLOCKS")) : 0;
     const int64_t bytes = rows_per_seg * (int64_t)nseg * C * 4;
     const int target_blocks = env_blocks > 0 ? env_blocks : (bytes > (100ll << 20) ? 192 : 128);
@@ -101,21 +214,37 @@ static void launch_colreduce(Fn fn, OutT* out, int64_t qstride, int64_t rows_per
     int64_t rpb = (rows_per_seg + blocks_per_seg - 1) / blocks_per_seg;
     if (rpb < 32) rpb = 32;
     blocks_per_seg = (rows_per_seg + rpb - 1) / rpb;
-    dim3 grid((unsigned)blocks_per_seg, (unsigned)nseg);
-    if constexpr (WIDE) {
-        // (small tensors: the 4-column form keeps twice the threads busy - measured 31 vs 38 us per launch at 32 images)
-        if (C % 8 == 0 && rows_per_seg * (int64_t)nseg * C >= (int64_t(16) << 20)) {
-            hipLaunchKernelGGL((colreduce_kernel<NQ, 8, Fn, OutT>), grid, dim3(EW_BLOCK), 0, s, fn, out, qstride,
-                               rows_per_seg, C, (int)rpb);
+    float* part = nullptr;
+    if (blocks_per_seg > 1) {
+        part = colreduce_workspace((size_t)blocks_per_seg * nseg * NQ * C, s);
+        if (!part) {                 // (the caller's BG_LAUNCH_CHECK returns the error set above)
+            g_ws_error = true;
             return;
         }
     }
-    if (C % 4 == 0)
-        hipLaunchKernelGGL((colreduce_kernel<NQ, 4, Fn, OutT>), grid, dim3(EW_BLOCK), 0, s, fn, out, qstride, rows_per_seg,
-                           C, (int)rpb);
-    else
-        hipLaunchKernelGGL((colreduce_kernel<NQ, 1, Fn, OutT>), grid, dim3(EW_BLOCK), 0, s, fn, out, qstride, rows_per_seg,
-                           C, (int)rpb);
+    dim3 grid((unsigned)blocks_per_seg, (unsigned)nseg);
+    bool launched = false;
+    if constexpr (WIDE) {
+        // (small tensors: the 4-column form keeps twice the threads busy - measured 31 vs 38 us per launch at 32 images)
+        if (C % 8 == 0 && rows_per_seg * (int64_t)nseg * C >= (int64_t(16) << 20)) {
+            hipLaunchKernelGGL((colreduce_kernel<NQ, 8, Fn, OutT>), grid, dim3(EW_BLOCK), 0, s, fn, out, part, qstride,
+                               rows_per_seg, C, (int)rpb);
+            launched = true;
+        }
+    }
+    if (!launched) {
+        if (C % 4 == 0)
+            hipLaunchKernelGGL((colreduce_kernel<NQ, 4, Fn, OutT>), grid, dim3(EW_BLOCK), 0, s, fn, out, part, qstride,
+                               rows_per_seg, C, (int)rpb);
+        else
+            hipLaunchKernelGGL((colreduce_kernel<NQ, 1, Fn, OutT>), grid, dim3(EW_BLOCK), 0, s, fn, out, part, qstride,
+                               rows_per_seg, C, (int)rpb);
+    }
+    if (part) {
+        const int64_t total = (int64_t)nseg * NQ * C;
+        hipLaunchKernelGGL((colreduce_finalize_kernel<NQ, OutT>), crf_grid(total), dim3(EW_BLOCK), 0, s, part, out,
+                           qstride, nseg, C, (int)blocks_per_seg);
+    }
 }
 
 template <int VEC>
@@ -892,7 +1021,7 @@ __global__ __launch_bounds__(EW_BLOCK) void scale_dev_kernel(const float* __rest
         y[i] = s * x[i];
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void dot_kernel(const float* __restrict__ a, const float* __restrict__ b,
+__global__ __launch_bounds__(EW_BLOCK) void dot_kernel(float* part, const float* __restrict__ a, const float* __restrict__ b,
                                                         float* out, int64_t n) {
     __shared__ float sh[4];
     float s = 0.f;
@@ -904,7 +1033,12 @@ __global__ __launch_bounds__(EW_BLOCK) void dot_kernel(const float* __restrict__
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EW_BLOCK)
         s += a[i] * b[i];
     s = block_sum_256(s, sh);
-    if (threadIdx.x == 0) atomicAdd(out, s);
+    if (threadIdx.x == 0) {
+        if (part)
+            part[blockIdx.x] = s;
+        else
+            *out += s;
+    }
 }
 
 __global__ __launch_bounds__(EW_BLOCK) void tanh_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -1521,7 +1655,7 @@ __global__ __launch_bounds__(EW_BLOCK) void lincomb_t_kernel(const T* __restrict
 }
 
 template <class T>
-__global__ __launch_bounds__(EW_BLOCK) void dot_t_kernel(const T* __restrict__ a, const T* __restrict__ b, float* out,
+__global__ __launch_bounds__(EW_BLOCK) void dot_t_kernel(float* part, const T* __restrict__ a, const T* __restrict__ b, float* out,
                                                           int64_t n4) {
     __shared__ float sh[4];
     float s = 0.f;
@@ -1532,7 +1666,12 @@ __global__ __launch_bounds__(EW_BLOCK) void dot_t_kernel(const T* __restrict__ a
         s += av[0] * bv[0] + av[1] * bv[1] + av[2] * bv[2] + av[3] * bv[3];
     }
     s = block_sum_256(s, sh);
-    if (threadIdx.x == 0) atomicAdd(out, s);
+    if (threadIdx.x == 0) {
+        if (part)
+            part[blockIdx.x] = s;
+        else
+            *out += s;
+    }
 }
 
 // w / sigma for one [taps][R][Cc] weight plus its two bf16 packed copies (BgSnItem::pack_p / pack_t): 64 x 64 tiles
@@ -2264,7 +2403,7 @@ int bg_prelu_fwd(const float* x, const float* alpha, float* y, int64_t rows, int
 
 // d alpha of a PReLU on a tensor with C <= 4 channels (the discriminator's activation of the IMAGE, ops.py:299): the column
 // skeleton would put 3 threads of a row-lane on a row (4-byte loads, 0.6 TB/s); here a thread owns whole pixels, 4 in flight.
-__global__ __launch_bounds__(EW_BLOCK) void prelu_dalpha_thin_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+__global__ __launch_bounds__(EW_BLOCK) void prelu_dalpha_thin_kernel(float* part, const float* __restrict__ x, const float* __restrict__ dy,
                                                                      float* __restrict__ dalpha, int64_t rows, int C) {
     __shared__ float red[4][EW_BLOCK];
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -2302,7 +2441,12 @@ __global__ __launch_bounds__(EW_BLOCK) void prelu_dalpha_thin_kernel(const float
             for (int c = 0; c < 4; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
         __syncthreads();
     }
-    if ((int)threadIdx.x < C) atomicAdd(&dalpha[threadIdx.x], red[threadIdx.x][0]);
+    if ((int)threadIdx.x < C) {
+        if (part)
+            part[blockIdx.x * C + threadIdx.x] = red[threadIdx.x][0];
+        else
+            dalpha[threadIdx.x] += red[threadIdx.x][0];
+    }
 }
 
 int bg_prelu_bwd(const float* x, const float* dy, const float* alpha, float* dx, float* dalpha, int64_t rows, int C,
@@ -2320,8 +2464,12 @@ int bg_prelu_bwd(const float* x, const float* dy, const float* alpha, float* dx,
     }
     if (dalpha) {
         if (C <= 4 && rows >= (int64_t(1) << 16)) {
-            hipLaunchKernelGGL(prelu_dalpha_thin_kernel, dim3(256), dim3(EW_BLOCK), 0, as_stream(stream), x, dy, dalpha, rows,
-                               C);
+            int grid = 256;
+            float* part = nullptr;
+            if (!block_partials(grid, C, as_stream(stream), &part)) return BG_ERR_LAUNCH;
+            hipLaunchKernelGGL(prelu_dalpha_thin_kernel, dim3(grid), dim3(EW_BLOCK), 0, as_stream(stream), part, x, dy,
+                               dalpha, rows, C);
+            finalize_block_partials(part, dalpha, grid, C, as_stream(stream));
             BG_LAUNCH_CHECK();
             return BG_OK;
         }
@@ -2505,7 +2653,10 @@ int bg_dot(const float* a, const float* b, float* out_accum, int64_t n, void* st
     BG_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0, "bg_dot: pointers must be 16-byte aligned");
     int grid = ew_grid(n / 4 + 1);
     if (grid > 512) grid = 512;
-    hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(EW_BLOCK), 0, as_stream(stream), a, b, out_accum, n);
+    float* part = nullptr;
+    if (!block_partials(grid, 1, as_stream(stream), &part)) return BG_ERR_LAUNCH;
+    hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(EW_BLOCK), 0, as_stream(stream), part, a, b, out_accum, n);
+    finalize_block_partials(part, out_accum, grid, 1, as_stream(stream));
     BG_LAUNCH_CHECK();
     return BG_OK;
 }
@@ -2599,7 +2750,10 @@ int bg_spectral_norm_bwd(const float* g_wnorm, const float* w_norm, const float*
     const int64_t n = (int64_t)rows * cols;
     int grid = ew_grid(n / 4 + 1);
     if (grid > 512) grid = 512;
-    hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(EW_BLOCK), 0, s, g_wnorm, w_norm, scr + 3, n);
+    float* part = nullptr;
+    if (!block_partials(grid, 1, s, &part)) return BG_ERR_LAUNCH;
+    hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(EW_BLOCK), 0, s, part, g_wnorm, w_norm, scr + 3, n);
+    finalize_block_partials(part, scr + 3, grid, 1, s);
     BG_LAUNCH_CHECK();
     hipLaunchKernelGGL(sn_bwd_kernel, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, g_wnorm, u_hat, v_hat, sigma, scr + 3, dw,
                        rows, cols);
@@ -2988,8 +3142,11 @@ int bg_dot_t(const void* a, const void* b, int dtype, float* out_accum, int64_t 
     BG_REQUIRE(a && b && out_accum && n > 0 && n % 4 == 0 && BG_DT_OK(dtype), "bg_dot_t: bad argument (n %% 4 == 0)");
     int blocks = ew_grid(n / 4);
     if (blocks > 512) blocks = 512;
-    BG_DISPATCH_T(dtype, hipLaunchKernelGGL((dot_t_kernel<T>), dim3(blocks), dim3(EW_BLOCK), 0, as_stream(stream),
+    float* part = nullptr;
+    if (!block_partials(blocks, 1, as_stream(stream), &part)) return BG_ERR_LAUNCH;
+    BG_DISPATCH_T(dtype, hipLaunchKernelGGL((dot_t_kernel<T>), dim3(blocks), dim3(EW_BLOCK), 0, as_stream(stream), part,
                                             (const T*)a, (const T*)b, out_accum, n / 4));
+    finalize_block_partials(part, out_accum, blocks, 1, as_stream(stream));
     BG_LAUNCH_CHECK();
     return BG_OK;
 }

@@ -1006,3 +1006,85 @@ def test_abi_rejects_bad_arguments_with_error_codes():
     rc = L.bg_conv2d_wgrad(d, hip.f32(xx), hip.f32(xx), hip.f32(dw), hip.f32(small), 16, hip.stream())
     torch.cuda.synchronize()
     assert rc == 0 or b"workspace" in L.bg_last_error()      # falls back to an unsplit launch or refuses; never overruns
+
+
+def test_cross_block_reductions_are_bit_reproducible():
+    """Bias gradient, dot product and the thin PReLU slope gradient sum over many blocks; the blocks' partial sums are
+    added in a fixed order (no atomics), so repeated calls are bit-identical - what makes bench.py --dump-outputs
+    identical from run to run - and they agree with a float64 sum."""
+    L = _hip().lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device="cuda").manual_seed(5)
+    rows, C = 256 * 32 * 32, 96
+    dy = torch.randn(rows, C, device="cuda", generator=g)
+    x = torch.randn(rows, C, device="cuda", generator=g)
+    xt, dyt = x[:, :3].contiguous(), dy[:, :3].contiguous()      # C <= 4: the thin slope-gradient kernel
+    alpha = torch.full((3,), 0.2, device="cuda")
+    dx = torch.empty_like(xt)
+    runs = []
+    for _ in range(3):
+        db = torch.empty(C, device="cuda")
+        dot = torch.zeros(1, device="cuda")
+        da = torch.zeros(3, device="cuda")
+        assert L.bg_bias_grad(dy.data_ptr(), db.data_ptr(), rows, C, s) == 0
+        assert L.bg_dot(x.data_ptr(), dy.data_ptr(), dot.data_ptr(), x.numel(), s) == 0
+        assert L.bg_prelu_bwd(xt.data_ptr(), dyt.data_ptr(), alpha.data_ptr(), dx.data_ptr(), da.data_ptr(), rows, 3, s) == 0
+        torch.cuda.synchronize()
+        runs.append((db.clone(), dot.clone(), da.clone()))
+    for r in runs[1:]:
+        for a, b in zip(runs[0], r):
+            assert torch.equal(a, b)
+    x64, dy64 = x.double().cpu(), dy.double().cpu()
+    assert rel_err(t2n(runs[0][0]), dy64.sum(0).numpy()) < 1e-5
+    assert rel_err(t2n(runs[0][1]), np.array([(x64 * dy64).sum().item()])) < 1e-5
+    xt64, dyt64 = xt.double().cpu(), dyt.double().cpu()
+    assert rel_err(t2n(runs[0][2]), (torch.where(xt64 < 0, xt64 * dyt64, 0.0)).sum(0).numpy()) < 1e-5
+
+
+def test_statistics_bf16_and_augment_reductions_are_bit_reproducible():
+    """The other users of the ordered cross-block sums, called three times each: batch-norm statistics (two
+    quantities, fp64 sums; fp32 and the bf16 8-column form), the batch-norm backward reduction (three quantities, one
+    segment per image: several blocks per segment at batch 2), the bf16 bias gradient and dot product, and
+    DiffAugment's per-image means (forward and backward).  Every call must give the same bits; the statistics and the
+    bf16 sums also agree with a float64 sum."""
+    L = _hip().lib()
+    Fn = _fn()
+    from biggan_tensorflow_amd import DiffAugment as DA
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device="cuda").manual_seed(9)
+    rows, C = 256 * 32 * 32, 96
+    x = torch.randn(rows, C, device="cuda", generator=g)
+    xb = x.bfloat16()
+    N, HW = 2, 64 * 64
+    xs, dys = x[:N * HW].contiguous(), torch.randn(N * HW, C, device="cuda", generator=g)
+    mean, rstd = xs.mean(0), xs.var(0).add(1e-5).rsqrt()
+    gamma, beta, alpha = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda"), torch.full((C,), 0.2, device="cuda")
+    img = torch.rand(8, 128, 128, 3, device="cuda", generator=g) * 2 - 1
+    draws = DA.draw(8, 128, "cuda", torch.Generator(device="cuda").manual_seed(3))
+    runs = []
+    for _ in range(3):
+        st = torch.zeros(2 * C, dtype=torch.float64, device="cuda")
+        stb = torch.zeros(2 * C, dtype=torch.float64, device="cuda")
+        part = torch.empty(3 * N * C, device="cuda")
+        dbb = torch.empty(C, device="cuda")
+        dotb = torch.zeros(1, device="cuda")
+        assert L.bg_bn_stats(x.data_ptr(), st.data_ptr(), rows, C, s) == 0
+        assert L.bg_bn_stats_t(xb.data_ptr(), 1, stb.data_ptr(), rows, C, s) == 0
+        assert L.bg_bn_apply_act_bwd_reduce(xs.data_ptr(), dys.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                            gamma.data_ptr(), beta.data_ptr(), 0, alpha.data_ptr(), part.data_ptr(),
+                                            N, HW, C, s) == 0
+        assert L.bg_bias_grad_t(xb.data_ptr(), 1, dbb.data_ptr(), rows, C, s) == 0
+        assert L.bg_dot_t(xb.data_ptr(), xb.data_ptr(), 1, dotb.data_ptr(), xb.numel(), s) == 0
+        xi = img.clone().requires_grad_(True)
+        y = DA.DiffAugment(xi, policy="color,translation,cutout", draws=draws)
+        y.backward(torch.ones_like(y) + y.detach())
+        torch.cuda.synchronize()
+        runs.append((st.clone(), stb.clone(), part.clone(), dbb.clone(), dotb.clone(), y.detach().clone(), xi.grad.clone()))
+    for r in runs[1:]:
+        for i, (a, b) in enumerate(zip(runs[0], r)):
+            assert torch.equal(a, b), i
+    x64, xb64 = x.double().cpu(), xb.double().cpu()
+    assert rel_err(runs[0][0].cpu().numpy(), torch.cat([x64.sum(0), (x64 * x64).sum(0)]).numpy()) < 1e-6
+    assert rel_err(runs[0][1].cpu().numpy(), torch.cat([xb64.sum(0), (xb64 * xb64).sum(0)]).numpy()) < 1e-6
+    assert rel_err(t2n(runs[0][3]), xb64.sum(0).numpy()) < 1e-5
+    assert rel_err(t2n(runs[0][4]), np.array([(xb64 * xb64).sum().item()])) < 1e-5

@@ -479,6 +479,66 @@ def test_bench_keeps_the_global_batch_fixed_under_strong_scaling():
         bench.resolve_workload("c3", 3)
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_leaves_the_extra_measurements_to_full():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline only; the roofline pass, the CPU baseline
+    and the N = 1 companions are opt-in through --full; --steps is the number of timed steps and must be positive."""
+    bench = _bench_module()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, "")
+    a = bench.parse_args(["--full", "--dump-outputs", "out_dir", "--no_cpu_baseline"])
+    assert a.full and a.dump_outputs == "out_dir" and a.no_cpu_baseline and not a.no_roofline
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_bench_dump_outputs_writes_losses_and_seeded_state_samples(tmp_path, monkeypatch):
+    """--dump-outputs: the losses and the state a step leaves (live weights per network, the generator's EMA shadows;
+    not the Adam slots), float32; a state larger than DUMP_ELEMS becomes the same fixed sample on every run."""
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 64)
+    g = torch.Generator().manual_seed(3)
+    variables = {"generator/b/kernel": torch.randn(10, 10, generator=g), "generator/a/kernel": torch.randn(30, generator=g),
+                 "discriminator/c/kernel": torch.randn(5, 4, generator=g, dtype=torch.float64)}
+
+    class Gan:
+        synced = 0
+        store = type("Store", (), {"vars": variables})()
+
+        def sync_sharded_state(self):
+            Gan.synced += 1
+
+        def state_tensors(self):
+            out = dict(variables)
+            for k in ("generator/a/kernel", "generator/b/kernel"):
+                out[k + "/Adam"] = torch.full_like(variables[k], 7.0)
+                out[k + "/ExponentialMovingAverage"] = variables[k] * 0.5
+            return out
+    losses = {"d_loss": torch.tensor(1.25), "g_loss": torch.tensor(-0.5)}
+    names = bench.dump_outputs(Gan(), losses, str(tmp_path / "x"))
+    bench.dump_outputs(Gan(), losses, str(tmp_path / "y"))
+    assert Gan.synced == 2
+    assert sorted(names) == ["d_loss", "discriminator_weights", "g_loss", "generator_ema", "generator_weights"]
+    assert sorted(os.listdir(tmp_path / "x")) == sorted(n + ".npy" for n in names)
+    arr = {n: np.load(tmp_path / "x" / (n + ".npy")) for n in names}
+    for n in names:
+        assert arr[n].dtype == np.float32
+        np.testing.assert_array_equal(arr[n], np.load(tmp_path / "y" / (n + ".npy")))
+    assert arr["d_loss"].tolist() == [1.25] and arr["g_loss"].tolist() == [-0.5]
+    np.testing.assert_array_equal(arr["discriminator_weights"], variables["discriminator/c/kernel"].float().reshape(-1))
+    full_g = torch.cat([variables["generator/a/kernel"], variables["generator/b/kernel"].reshape(-1)]).numpy()
+    assert 0 < arr["generator_weights"].size <= 64
+    assert np.isin(arr["generator_weights"], full_g).all()
+    np.testing.assert_array_equal(arr["generator_ema"], bench.sample_flat([torch.tensor(full_g * 0.5)]))
+
+
 def test_bench_roofline_groups_by_kernel_symbol_and_counts_algorithmic_flops():
     """roofline_from_rows (bench.py): `dominant` is the kernel SYMBOL with the most time (not the per-shape tag: every
     attention launch shares a tag, every conv shape has its own), `achieved` comes from the step's algorithmic FLOPs

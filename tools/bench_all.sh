@@ -2,7 +2,7 @@
 # all single-GPU bench lines of the round (one JSON line each)
 out=gpurun_out/bench_lines.jsonl
 : > $out
-run() { echo "# python bench.py $*" >> $out; timeout -k 10 400 python bench.py --no_cpu_baseline "$@" 2>/dev/null >> $out; echo "done: $*"; }
+run() { echo "# python bench.py $*" >> $out; timeout -k 10 400 python bench.py --full --no_cpu_baseline "$@" 2>/dev/null >> $out; echo "done: $*"; }
 run
 run --da_policy ""
 run --g_regularization none

@@ -12,10 +12,10 @@ mkdir -p gpurun_out/ev
 E=gpurun_out/ev
 case "$part" in
 lines)
-  echo "== default bench"; timeout -k 10 500 python bench.py > $E/bench_default.json 2> $E/bench_default.err; tail -c 400 $E/bench_default.json
+  echo "== default bench"; timeout -k 10 500 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err; tail -c 400 $E/bench_default.json
   out=$E/bench_lines.jsonl
   : > $out
-  run() { echo "# python bench.py $*" >> $out; timeout -k 10 300 python bench.py --no_cpu_baseline "$@" 2>/dev/null >> $out; echo "done: $*"; }
+  run() { echo "# python bench.py $*" >> $out; timeout -k 10 300 python bench.py --full --no_cpu_baseline "$@" 2>/dev/null >> $out; echo "done: $*"; }
   run --workload c3
   run --workload c3 --batch 256
   run --workload c3 --graph

@@ -12,10 +12,10 @@ mkdir -p gpurun_out/ev3
 E=gpurun_out/ev3
 case "$part" in
 lines)
-  echo "== default bench"; timeout -k 10 500 python bench.py > $E/bench_default.json 2> $E/bench_default.err; tail -c 300 $E/bench_default.json
+  echo "== default bench"; timeout -k 10 500 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err; tail -c 300 $E/bench_default.json
   out=$E/bench_lines.jsonl
   : > $out
-  run() { echo "# python bench.py $*" >> $out; timeout -k 10 300 python bench.py --no_cpu_baseline --no_companions "$@" 2>/dev/null >> $out; echo "done: $*"; }
+  run() { echo "# python bench.py $*" >> $out; timeout -k 10 300 python bench.py --full --no_cpu_baseline --no_companions "$@" 2>/dev/null >> $out; echo "done: $*"; }
   run --batch 32
   run --batch 32 --graph
   run --workload c2
