@@ -97,6 +97,116 @@ __global__ __launch_bounds__(DG_COLS) void dense_group_wgrad_kernel(const DenseG
     if (k0 == 0 && it.db) it.db[c] = it.acc_b ? it.db[c] + sb : sb;
 }
 
+// dx[b, k] (+)= sum_i sum_c dy_i[b, c] w_i[k, c] over items that share their input rows (same K).  blockIdx.x = tile of
+// DD_K values of k, blockIdx.y = strip of DG_ROWS rows; thread (kk, r) owns one output element and walks the items and
+// their columns in a fixed order.  Chunks of DD_C columns of w (padded row: no bank conflicts across kk) and of dy are
+// staged in LDS with coalesced loads.
+constexpr int DD_K = 32, DD_C = 64;
+static_assert(DD_K * DG_ROWS == DG_COLS, "one thread per (k, row) of the tile");
+__global__ __launch_bounds__(DG_COLS) void dense_group_dgrad_kernel(const DenseGroupArgs a, float* dx, int64_t lddx,
+                                                                    int acc) {
+    __shared__ float ws[DD_K][DD_C + 1];
+    __shared__ float gs[DG_ROWS][DD_C];
+    const int k0 = blockIdx.x * DD_K, b0 = blockIdx.y * DG_ROWS;
+    const int kk = threadIdx.x % DD_K, r = threadIdx.x / DD_K;
+    const int K = a.item[0].K;
+    float s = 0.f;
+    for (int i = 0; i < a.n; ++i) {
+        const BgDenseItem it = a.item[i];
+        const int N = it.N;
+        for (int c0 = 0; c0 < N; c0 += DD_C) {
+            __syncthreads();
+            for (int e = threadIdx.x; e < DD_K * DD_C; e += DG_COLS) {
+                const int rr = e / DD_C, cc = e - rr * DD_C;
+                ws[rr][cc] = (k0 + rr < K && c0 + cc < N) ? it.w[(int64_t)(k0 + rr) * N + c0 + cc] : 0.f;
+            }
+            for (int e = threadIdx.x; e < DG_ROWS * DD_C; e += DG_COLS) {
+                const int rr = e / DD_C, cc = e - rr * DD_C;
+                gs[rr][cc] = (b0 + rr < a.B && c0 + cc < N) ? it.y[(int64_t)(b0 + rr) * N + c0 + cc] : 0.f;
+            }
+            __syncthreads();
+#pragma unroll 16
+            for (int cc = 0; cc < DD_C; ++cc) s = fmaf(gs[r][cc], ws[kk][cc], s);
+        }
+    }
+    if (k0 + kk < K && b0 + r < a.B) {
+        float* o = dx + (int64_t)(b0 + r) * lddx + k0 + kk;
+        *o = acc ? *o + s : s;
+    }
+}
+
+// ---- latent fan-out / fan-in ----------------------------------------------------------------------------------------
+// target t, element (b, c) = sum over the segments routed to t that cover column c (in segment order) of
+// src[b, src_col + c - dst_col]; accumulate adds to the old value.  One thread per output element, no atomics.
+struct LatentArgs {
+    BgLatentTarget tgt[BG_LATENT_MAX_TARGETS];
+    BgLatentSeg seg[BG_LATENT_MAX_SEGS];
+    int32_t n_tgt, n_seg, B;
+};
+
+__global__ __launch_bounds__(256) void latent_route_kernel(const LatentArgs a) {
+    const int t = blockIdx.y;
+    const BgLatentTarget tg = a.tgt[t];
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)a.B * tg.width) return;
+    const int b = (int)(e / tg.width), c = (int)(e - (int64_t)b * tg.width);
+    float s = 0.f;
+    for (int i = 0; i < a.n_seg; ++i) {
+        const BgLatentSeg sg = a.seg[i];
+        if (sg.target == t && c >= sg.dst_col && c < sg.dst_col + sg.width)
+            s += sg.src[(int64_t)b * sg.lds + sg.src_col + (c - sg.dst_col)];
+    }
+    float* o = tg.dst + (int64_t)b * tg.ldd + c;
+    *o = tg.accumulate ? *o + s : s;
+}
+
+static int latent_prepare(const void* targets, int n_tgt, const void* segs, int n_seg, int B, LatentArgs& a,
+                          const char* who, bool exact_cover) {
+    BG_REQUIRE(targets && segs && n_tgt >= 1 && n_tgt <= BG_LATENT_MAX_TARGETS && n_seg >= 1 &&
+               n_seg <= BG_LATENT_MAX_SEGS && B >= 1, "%s: 1..%d targets, 1..%d segments and a positive batch", who,
+               BG_LATENT_MAX_TARGETS, BG_LATENT_MAX_SEGS);
+    memset(&a, 0, sizeof(a));
+    const BgLatentTarget* tg = static_cast<const BgLatentTarget*>(targets);
+    const BgLatentSeg* sg = static_cast<const BgLatentSeg*>(segs);
+    for (int t = 0; t < n_tgt; ++t) {
+        BG_REQUIRE(tg[t].dst && tg[t].width >= 1 && tg[t].ldd >= tg[t].width, "%s: target %d: bad operand", who, t);
+        a.tgt[t] = tg[t];
+    }
+    for (int i = 0; i < n_seg; ++i) {
+        const BgLatentSeg& s = sg[i];
+        BG_REQUIRE(s.src && s.target >= 0 && s.target < n_tgt && s.width >= 1 && s.src_col >= 0 && s.dst_col >= 0 &&
+                   s.dst_col + s.width <= tg[s.target].width && s.lds >= s.src_col + s.width,
+                   "%s: segment %d: bad operand", who, i);
+        a.seg[i] = s;
+    }
+    if (exact_cover) {          // fan-out: every output column is written by exactly one segment
+        for (int t = 0; t < n_tgt; ++t) {
+            int64_t cover = 0;
+            for (int i = 0; i < n_seg; ++i)
+                if (sg[i].target == t) cover += sg[i].width;
+            BG_REQUIRE(cover == tg[t].width, "%s: target %d: segments cover %lld of %d columns", who, t,
+                       (long long)cover, tg[t].width);
+            for (int i = 0; i < n_seg; ++i)
+                for (int j = i + 1; j < n_seg; ++j)
+                    BG_REQUIRE(sg[i].target != t || sg[j].target != t || sg[i].dst_col + sg[i].width <= sg[j].dst_col ||
+                               sg[j].dst_col + sg[j].width <= sg[i].dst_col, "%s: segments %d and %d overlap", who, i, j);
+        }
+    }
+    a.n_tgt = n_tgt;
+    a.n_seg = n_seg;
+    a.B = B;
+    return BG_OK;
+}
+
+static int latent_launch(const LatentArgs& a, void* stream) {
+    int wmax = 0;
+    for (int t = 0; t < a.n_tgt; ++t) wmax = a.tgt[t].width > wmax ? a.tgt[t].width : wmax;
+    const int64_t blocks = ((int64_t)a.B * wmax + 255) / 256;
+    hipLaunchKernelGGL(latent_route_kernel, dim3((unsigned)blocks, a.n_tgt), dim3(256), 0, as_stream(stream), a);
+    BG_LAUNCH_CHECK();
+    return BG_OK;
+}
+
 static int dg_prepare(const BgDenseItem* items, int n, int B, DenseGroupArgs& a, int* kmax, const char* who, bool bwd) {
     BG_REQUIRE(items && n >= 1 && n <= BG_DENSE_GROUP_MAX && B >= 1, "%s: 1..%d items and a positive batch", who,
                BG_DENSE_GROUP_MAX);
@@ -146,6 +256,43 @@ int bg_dense_group_wgrad(const BgDenseItem* items, int n_items, int B, void* str
     hipLaunchKernelGGL(dense_group_wgrad_kernel, grid, dim3(DG_COLS), 0, as_stream(stream), a);
     BG_LAUNCH_CHECK();
     return BG_OK;
+}
+
+int bg_dense_group_dgrad(const BgDenseItem* items, int n_items, int B, void* dx, int lddx, int accumulate,
+                         void* stream) {
+    BG_REQUIRE(items && n_items >= 1 && n_items <= BG_DENSE_GROUP_MAX && B >= 1 && dx,
+               "bg_dense_group_dgrad: 1..%d items, a positive batch and an output", BG_DENSE_GROUP_MAX);
+    DenseGroupArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = n_items;
+    a.B = B;
+    const int K = items[0].K;
+    for (int i = 0; i < n_items; ++i) {
+        const BgDenseItem& it = items[i];
+        BG_REQUIRE(it.w && it.y && it.K == K && K >= 1 && it.N >= 1, "bg_dense_group_dgrad: item %d: bad operand "
+                   "(every item needs w, dy in y and the same K)", i);
+        a.item[i] = it;
+    }
+    BG_REQUIRE(lddx >= K, "bg_dense_group_dgrad: lddx %d < K %d", lddx, K);
+    dim3 grid((K + DD_K - 1) / DD_K, (B + DG_ROWS - 1) / DG_ROWS);
+    hipLaunchKernelGGL(dense_group_dgrad_kernel, grid, dim3(DG_COLS), 0, as_stream(stream), a, static_cast<float*>(dx),
+                       (int64_t)lddx, accumulate);
+    BG_LAUNCH_CHECK();
+    return BG_OK;
+}
+
+int bg_latent_fanout(const void* targets, int n_targets, const void* segs, int n_segs, int B, void* stream) {
+    LatentArgs a;
+    int rc = latent_prepare(targets, n_targets, segs, n_segs, B, a, "bg_latent_fanout", true);
+    if (rc) return rc;
+    return latent_launch(a, stream);
+}
+
+int bg_latent_fanin(const void* targets, int n_targets, const void* segs, int n_segs, int B, void* stream) {
+    LatentArgs a;
+    int rc = latent_prepare(targets, n_targets, segs, n_segs, B, a, "bg_latent_fanin", false);
+    if (rc) return rc;
+    return latent_launch(a, stream);
 }
 
 }  // extern "C"

@@ -652,7 +652,9 @@ class DenseFn(Function):
 class GroupedDenseFn(Function):
     """n dense projections y_i = x_i w_i + b_i on the same batch rows in ONE launch each way (csrc/dense_group.hip): the
     beta / gamma projections of the conditional batch norms of a generator block (ops.py:623-624).  Arguments:
-    n, then (x_i, w_i, b_i) flattened; x_i are [B, K_i] row views (column slices allowed) that need no gradient."""
+    n, then (x_i, w_i, b_i) flattened; x_i are [B, K_i] row views (column slices allowed).  An x that needs a gradient
+    must be the SAME tensor in every item (a latent shared by the block's projections): its gradient is then one more
+    launch, dx = sum_i dy_i w_i^T (bg_dense_group_dgrad), returned at the first item's position."""
 
     @staticmethod
     def forward(ctx, n, *args):
@@ -660,11 +662,13 @@ class GroupedDenseFn(Function):
         items = (hip.BgDenseItem * n)()
         ys, keep = [], []
         B = args[0].shape[0]
+        ctx.x_grad = args[0].requires_grad
         for i in range(n):
             x, w, b = args[3 * i], args[3 * i + 1], args[3 * i + 2]
+            assert not ctx.x_grad or x is args[0], "a grouped input that needs a gradient must be shared by every item"
             x, ldx = _row_view(x)
             w = _c(w)
-            assert x.shape[0] == B and w.shape[0] == x.shape[1] and not x.requires_grad
+            assert x.shape[0] == B and w.shape[0] == x.shape[1] and (ctx.x_grad or not x.requires_grad)
             y = torch.empty((B, w.shape[1]), dtype=torch.float32, device=x.device)
             it = items[i]
             it.x, it.ldx, it.w, it.bias, it.y = x.data_ptr(), ldx, f32(w).value, (f32(b).value if b is not None else None), \
@@ -678,8 +682,22 @@ class GroupedDenseFn(Function):
 
     @staticmethod
     def backward(ctx, *dys):
+        dx = None
+        if ctx.x_grad and ctx.needs_input_grad[1]:
+            live = [(dy, ctx.keep[i][2]) for i, dy in enumerate(dys) if dy is not None]
+            x = ctx.keep[0][0]
+            if live:
+                items = (hip.BgDenseItem * len(live))()
+                hold = []
+                for it, (dy, w) in zip(items, live):
+                    dy = _c(dy)
+                    hold.append(dy)
+                    it.w, it.y, it.K, it.N = f32(w).value, dy.data_ptr(), w.shape[0], w.shape[1]
+                dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+                check(lib().bg_dense_group_dgrad(items, len(live), ctx.B, dx.data_ptr(), x.shape[1], 0, stream()))
         if _Mode.inputs_only:
-            return (None,) * (1 + 3 * len(ctx.keep))
+            ctx.keep = None
+            return (None, dx) + (None,) * (3 * len(dys) - 1)
         n = len(ctx.keep)
         items = (hip.BgDenseItem * n)()
         m = 0
@@ -711,7 +729,64 @@ class GroupedDenseFn(Function):
         if m:
             check(lib().bg_dense_group_wgrad(items, m, ctx.B, stream()))
         ctx.keep = None
+        outs[1] = dx
         return tuple(outs)
+
+
+class LatentFanoutFn(Function):
+    """The generator's latent assembly (BigGAN.py:338-424 with --cls_embedding / --shared_z / --g_z_dense_concat): every
+    level's vector, e.g. [z_i | class embedding | shared projection], is a column range of ONE packed [B, sum widths]
+    buffer written by one launch (bg_latent_fanout); the levels are returned as column views of it (no torch.cat).
+    Backward, the gradients of every source are reduced over all the levels that read it in one launch
+    (bg_latent_fanin), in a fixed order.
+
+    Arguments: widths (output widths), segs (tuples (source index, source column, output index, output column, width)
+    that together cover every output column once), then the sources: [B, K_s] fp32 row views."""
+
+    @staticmethod
+    def forward(ctx, widths, segs, *srcs):
+        B = srcs[0].shape[0]
+        views = [_row_view(t) for t in srcs]
+        off = [0]
+        for w in widths:
+            off.append(off[-1] + w)
+        out = torch.empty((B, off[-1]), dtype=torch.float32, device=srcs[0].device)
+        tg = (hip.BgLatentTarget * 1)()
+        tg[0].dst, tg[0].ldd, tg[0].width, tg[0].accumulate = out.data_ptr(), off[-1], off[-1], 0
+        sg = (hip.BgLatentSeg * len(segs))()
+        for d, (si, sc, oi, oc, w) in zip(sg, segs):
+            t, ld = views[si]
+            assert t.shape[0] == B and sc + w <= t.shape[1] and oc + w <= widths[oi]
+            d.src, d.lds, d.src_col, d.dst_col, d.width, d.target = t.data_ptr(), ld, sc, off[oi] + oc, w, 0
+        check(lib().bg_latent_fanout(tg, 1, sg, len(segs), B, stream()))
+        ctx.set_materialize_grads(False)
+        ctx.segs, ctx.B, ctx.shapes = segs, B, [(t.shape[1], t.device) for t in srcs]
+        return tuple(out[:, off[i]:off[i + 1]] for i in range(len(widths)))
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        need = [i for i in range(len(ctx.shapes)) if ctx.needs_input_grad[2 + i]]
+        grads = [None] * len(ctx.shapes)
+        hold = [None if g is None else _row_view(_c(g)) for g in gouts]
+        for c0 in range(0, len(need), hip.LATENT_MAX_TARGETS):
+            chunk = need[c0:c0 + hip.LATENT_MAX_TARGETS]
+            tg = (hip.BgLatentTarget * len(chunk))()
+            for d, si in zip(tg, chunk):
+                K, dev = ctx.shapes[si]
+                grads[si] = torch.empty((ctx.B, K), dtype=torch.float32, device=dev)
+                d.dst, d.ldd, d.width, d.accumulate = grads[si].data_ptr(), K, K, 0
+            segs = [(chunk.index(si), sc, hold[oi], oc, w) for si, sc, oi, oc, w in ctx.segs
+                    if si in chunk and hold[oi] is not None]
+            if not segs:
+                for si in chunk:
+                    grads[si].zero_()
+                continue
+            sg = (hip.BgLatentSeg * len(segs))()
+            for d, (ti, sc, (g, ld), oc, w) in zip(sg, segs):
+                d.src, d.lds, d.src_col, d.dst_col, d.width, d.target = g.data_ptr(), ld, oc, sc, w, ti
+            check(lib().bg_latent_fanin(tg, len(chunk), sg, len(segs), ctx.B, stream()))
+        ctx.segs = None
+        return (None, None) + tuple(grads)
 
 
 class AttentionFn(Function):

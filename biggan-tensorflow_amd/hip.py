@@ -12,7 +12,7 @@ import torch
 
 _LIB = None
 LIB_NAME = "libbiggan_hip.so"
-ABI_VERSION = 3
+ABI_VERSION = 4
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 PAD_REFLECT, PAD_ZERO = 0, 1
@@ -47,6 +47,19 @@ class BgDenseItem(Structure):
 
 
 DENSE_GROUP_MAX = 8
+
+
+class BgLatentTarget(Structure):
+    _fields_ = [("dst", c_void_p), ("ldd", c_int64), ("width", c_int32), ("accumulate", c_int32)]
+
+
+class BgLatentSeg(Structure):
+    _fields_ = [("src", c_void_p), ("lds", c_int64), ("src_col", c_int32), ("dst_col", c_int32), ("width", c_int32),
+                ("target", c_int32)]
+
+
+LATENT_MAX_TARGETS = 8
+LATENT_MAX_SEGS = 48
 
 
 class BgAttn16Desc(Structure):
@@ -87,6 +100,9 @@ SIGNATURES = {
     "bg_rgbconv_wgrad": (c_int, [_CD, _P, _P, _P, _P, c_size_t, _P]),
     "bg_dense_group_fwd": (c_int, [POINTER(BgDenseItem), c_int, c_int, _P]),
     "bg_dense_group_wgrad": (c_int, [POINTER(BgDenseItem), c_int, c_int, _P]),
+    "bg_dense_group_dgrad": (c_int, [POINTER(BgDenseItem), c_int, c_int, _P, c_int, c_int, _P]),
+    "bg_latent_fanout": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
+    "bg_latent_fanin": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
     "bg_gemm_workspace_bytes": (c_size_t, [_GD]),
     "bg_gemm": (c_int, [_GD, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_attention2_supported": (c_int, [c_int, c_int, c_int, c_int]),

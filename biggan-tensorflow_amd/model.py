@@ -26,6 +26,10 @@ from .DiffAugment import DiffAugment, draw as draw_augment
 from .utils import orthogonal_regularizer, orthogonal_regularizer_fc, l2_regularizer, round_up, cls_loss_fn
 
 
+def _meta_2d(B, width):
+    return torch.empty(B, width, device="meta")
+
+
 class GANBase(object):
     """GANBase.py:13-55 (attribute plumbing, bn/conv option dicts, da_policy expansion)."""
 
@@ -62,8 +66,8 @@ class BigGAN(GANBase):
         self.depth = args.img_size.bit_length() - 2                                   # BigGAN.py:19
 
         unsupported = [
-            ("cls_embedding", args.cls_embedding),
-            ("shared_z", args.shared_z > 0), ("g_z_dense_concat", args.g_z_dense_concat),
+            # (the reference accepts it and only re-splits z: no labels, no embedding; rejected as a likely mistake)
+            ("cls_embedding without n_labels", args.cls_embedding and args.n_labels <= 0),
             ("g_mixed_resblocks", args.g_mixed_resblocks),
             ("g_final_layer", args.g_final_layer), ("multi_head", args.multi_head),
             ("z_reconstruct", args.z_reconstruct), ("d_reconstruction", args.d_reconstruction),
@@ -136,6 +140,15 @@ class BigGAN(GANBase):
         self.d_compat_use_sn_in_critic_output = args.d_compat_use_sn_in_critic_output
         self.extension_32 = getattr(args, "extension_32", False)
         self.deep = args.deep                                                          # BigGAN.py:20
+        self.cls_embedding = args.cls_embedding                                        # BigGAN.py:24-28
+        self.cls_embedding_size = args.cls_embedding_size
+        if self.cls_embedding and self.cls_embedding_size == 0:
+            self.cls_embedding_size = self.round_up(math.pow(args.n_labels, 0.88) + 24, 8)
+        self.cls_embedding_concat = args.cls_embedding_concat
+        self.shared_z_dim = args.shared_z
+        self.g_z_dense_concat = args.g_z_dense_concat
+        # (BigGAN.py:278: mixed_conv_z_idx also selects it, but needs --g_final_layer, which stays rejected above)
+        self.new_z_dist = bool(self.cls_embedding or self.shared_z_dim > 0 or self.g_z_dense_concat)
         self.n_labels = args.n_labels                                                  # BigGAN.py:22-23
         self.acgan = self.n_labels > 0
         self.virtual_batches = max(int(args.virtual_batches), 1)
@@ -258,6 +271,11 @@ class BigGAN(GANBase):
             opt["fc_regularizer"] = None
 
         self._sn_prefetch("generator", z)
+        if self.new_z_dist:
+            with S.variable_scope("generator", reuse=reuse):
+                block_info = self.g_block_info()
+                levels = self._latent_levels(z, cls_z, opt, block_info)
+                return self._generator_trunk(levels, opt, block_info, new_z_dist=True)
         with S.variable_scope("generator", reuse=reuse):
             block_info = self.g_block_info()
             split_sizes = self.z_split_sizes()
@@ -279,63 +297,203 @@ class BigGAN(GANBase):
                 next_zi[0] += 1
                 return z_split[zi], split_sizes[zi]
 
-            counts = block_info["counts"]
-            ch_mul = 2 ** (len(counts) - 1)                                            # BigGAN.py:427
-            ch = self.g_channels_for_block(0, len(counts))
+            return self._generator_trunk([next_z_split() for _ in range(len(z_split))], opt, block_info)
 
-            layer_z, z_dim = next_z_split()
-            f_width = self.round_up(z_dim * 1.85, 8)                                   # BigGAN.py:433 (z_dim includes the labels)
-            if not self.args.g_first_level_dense_layer:                                # BigGAN.py:444
-                x = fully_connected(layer_z, units=4 * 4 * ch, scope='dense', opt=opt)
-            elif self.activation_fn is relu:                                           # BigGAN.py:434-438
-                x = fully_connected(layer_z, units=f_width, scope='dense1', opt=opt)
-                x = relu(x)
-                x = fully_connected(x, units=4 * 4 * ch, scope='dense2', opt=opt)
+    def new_z_split_sizes(self, block_info):                                           # BigGAN.py:314-333
+        """z split by weights: [0 (shared slot)] + [first_split_ratio] + [1 per block]; the remainder goes to the first
+        level, the shared slot gets --shared_z.  -> (sizes, shared slot or None, first slot, block slots)."""
+        weights = []
+        shared_idx = None
+        if self.shared_z_dim > 0:
+            shared_idx = len(weights)
+            weights.append(0.0)
+        first_idx = len(weights)
+        weights.append(self.first_split_ratio)
+        block_idx = []
+        for count in block_info["counts"]:
+            for _ in range(count):
+                block_idx.append(len(weights))
+                weights.append(1.0)
+        total = sum(weights)
+        nonshared = self.z_dim - self.shared_z_dim
+        sizes = [int(w / total * nonshared) for w in weights]
+        sizes[first_idx] += nonshared - sum(sizes)
+        if shared_idx is not None:
+            sizes[shared_idx] = self.shared_z_dim
+        return sizes, shared_idx, first_idx, block_idx
+
+    def _latent_levels(self, z, cls_z, opt, block_info):
+        """BigGAN.py:335-424 (new_z_dist): class embedding, shared z and the per-level dense layers.  Every level's vector
+        is kept as a list of column pieces (source, first column, width) of a few source tensors (z, the labels, the
+        embedding, the shared projection, the level's own dense layer) and materialised by ONE fan-out launch per stage
+        (functional.LatentFanoutFn) as column views of one packed buffer; backward reduces each source's gradient over
+        all levels in one launch.  -> [(vector, width)] of the first level, then of every block."""
+        opt["cbn_group_dz"] = True                # (ops._cbn_prefetch: the block projections' latent needs a gradient)
+        meta = z.device.type == "meta"
+        B = z.shape[0]
+        sizes, shared_idx, first_idx, block_idx = self.new_z_split_sizes(block_info)
+        srcs = [z.reshape(B, -1)]
+        pieces, off = [], 0
+        for sz in sizes:
+            pieces.append([(0, off, sz)] if sz > 0 else [])
+            off += sz
+        zvec = list(sizes)
+
+        def add_src(t):
+            srcs.append(t)
+            return len(srcs) - 1
+
+        def materialise(slots):
+            """Per slot: one tensor.  Single-piece slots of an existing source are column views of it (no launch)."""
+            if meta:
+                return [_meta_2d(B, sum(p[2] for p in pieces[i])) for i in slots]
+            if all(len(pieces[i]) == 1 for i in slots):
+                return [srcs[pieces[i][0][0]][:, pieces[i][0][1]:pieces[i][0][1] + pieces[i][0][2]] for i in slots]
+            used = sorted({p[0] for i in slots for p in pieces[i]})
+            segs, widths = [], []
+            for oi, i in enumerate(slots):
+                col = 0
+                for si, sc, w in pieces[i]:
+                    segs.append((used.index(si), sc, oi, col, w))
+                    col += w
+                widths.append(col)
+            return list(Fn.LatentFanoutFn.apply(widths, segs, *[srcs[u] for u in used]))
+
+        cls_pieces = []
+        if self.acgan:                                                                 # BigGAN.py:346-365
+            lab = add_src(_meta_2d(B, self.n_labels) if meta else cls_z.reshape(B, self.n_labels))
+            cls_pieces = [(lab, 0, self.n_labels)]
+            if self.cls_embedding:
+                with S.variable_scope('cls_embed'):
+                    e = fully_connected(srcs[lab], units=self.cls_embedding_size, scope='dense1', opt=opt)
+                    e = add_src(opt["act"](e))
+                emb = [(e, 0, self.cls_embedding_size)]
+                cls_pieces = cls_pieces + emb if self.cls_embedding_concat else emb
+            for i in range(len(pieces)):
+                if self.g_z_dense_concat and i == shared_idx:
+                    continue
+                pieces[i] = pieces[i] + cls_pieces
+                zvec[i] += sum(p[2] for p in cls_pieces)
+
+        if shared_idx is not None:                                                     # BigGAN.py:367-392
+            zd = sizes[shared_idx]
+            with S.variable_scope('shared_z'):
+                if self.g_z_dense_concat:
+                    f_width = self.round_up(zd * 0.5, 8)
+                    f_in = pieces[shared_idx] + cls_pieces
+                else:
+                    f_width = self.round_up(zd * 1.5, 8)
+                    f_in = pieces[shared_idx]
+                pieces.append(f_in)                                                    # (a scratch slot for the input)
+                x_in = materialise([len(pieces) - 1])[0]
+                pieces.pop()
+                d = fully_connected(x_in, units=f_width, scope='dense1', opt=opt)
+                d = add_src(opt["act"](d))
+            if self.g_z_dense_concat:
+                shared_pieces = pieces[shared_idx] + [(d, 0, f_width)]
+                zvec[shared_idx] += f_width
             else:
-                with S.variable_scope('first'):                                        # BigGAN.py:440-443
-                    x = fully_connected(layer_z, units=f_width, scope='dense1', opt=opt)
-                    x = opt["act"](x)
-                    x = fully_connected(x, units=4 * 4 * ch, scope='dense2', opt=opt)
-            x = ops._resident_out(x.reshape(-1, 4, 4, ch))                             # BigGAN.py:446 (bf16 trunk from here)
+                shared_pieces = [(d, 0, f_width)]
+                zvec[shared_idx] = f_width
+            for i in range(len(pieces)):
+                if i != shared_idx:
+                    pieces[i] = pieces[i] + shared_pieces
+                    zvec[i] += zvec[shared_idx]
 
-            b_i = 0
-            for block_count in counts:                                                 # BigGAN.py:449-489
-                x = self._grad_mark(x, 'resblock_up_' + str(ch_mul))
-                scope = 'resblock_up_' + str(ch_mul)
-                for sb_i in range(block_count):
-                    layer_z, z_dim = next_z_split()
-                    if block_count > 1:
-                        scope = scope + '_' + str(sb_i)                                # cumulative (BigGAN.py:455)
-                    if self.args.g_other_level_dense_layer:                            # BigGAN.py:457-462
-                        with S.variable_scope('z' + str(ch_mul)):
-                            zw = self.round_up(z_dim * 1.25, 8)                        # (z_dim includes the labels)
-                            layer_z = fully_connected(layer_z, units=zw, scope='dense1', opt=opt)
-                            layer_z = opt["act"](layer_z)
-                    is_last_block = sb_i == block_count - 1 and b_i == len(counts) - 1
-                    if self.args.g_no_last_resblock and is_last_block:                 # BigGAN.py:468-473
-                        with S.variable_scope(scope):
-                            x = upconv(x, ch, use_bias=False, opt=opt)
-                            x = cond_bn(x, layer_z, opt=opt)
-                            x = opt["act"](x)
-                            x = g_conv(x, ch, use_bias=False, opt=opt)
-                    elif self.deep:                                                    # BigGAN.py:475-477
-                        x = resblock_up_cond_deep(x, layer_z, channels_out=ch, use_bias=True, opt=opt, scope=scope)
-                        x = resblock_up_cond_deep(x, layer_z, channels_out=ch, upscale=False, use_bias=True, opt=opt,
-                                                  scope=scope + "_2")
+        level_idx = [first_idx] + block_idx
+        dense_idx = ([first_idx] if self.args.g_first_level_dense_layer else []) + \
+                    (block_idx if self.args.g_other_level_dense_layer else [])
+        final = dict(zip(level_idx, materialise(level_idx)))
+        if dense_idx:                                                                  # BigGAN.py:394-424
+            concat_slots = []
+            for zi in dense_idx:
+                with S.variable_scope('z' + str(zi)):
+                    factor = 1.5 if zi == first_idx else 1.0
+                    if self.g_z_dense_concat:
+                        factor = (factor - 1.0) * 2.0 + 1.0
+                        f_width = self.round_up((zvec[zi] * 0.33) * factor, 8)
                     else:
-                        x = resblock_up_condition(x, layer_z, channels=ch, use_bias=False, opt=opt, scope=scope)
-                b_i += 1
-                if b_i == block_info["sa_index"]:
-                    x = self_attention_2(x, channels=ch, opt=opt, scope='self_attention')
-                ch = self.g_channels_for_block(b_i, len(counts))
-                ch_mul = ch_mul // 2
+                        f_width = self.round_up((sizes[zi] * 0.75 + zvec[zi] * 0.5) * factor, 8)
+                    layer_z = fully_connected(final[zi], units=f_width, scope='dense1', opt=opt)
+                    layer_z = opt["act"](layer_z)
+                if self.g_z_dense_concat:
+                    pieces[zi] = pieces[zi] + [(add_src(layer_z), 0, f_width)]
+                    zvec[zi] += f_width
+                    concat_slots.append(zi)
+                else:
+                    final[zi] = layer_z
+                    zvec[zi] = f_width
+            if concat_slots:        # one more stage: [level | dense(level)], gathered from the sources again
+                final.update(zip(concat_slots, materialise(concat_slots)))
+        return [(final[i], zvec[i]) for i in level_idx]
 
-            x = self._grad_mark(x, 'tail')
-            x = ops._bn_act(x, None, opt, _out_fp32=os.environ.get("BG_IMAGE_LAYERS", "") == "fp32")   # BigGAN.py:491-492
-            x = conv(x, channels=self.c_dim, kernel=self.g_rgb_mix_kernel, stride=1, pad=1, use_bias=False, opt=opt,
-                     scope='G_logit')                                                  # BigGAN.py:570
-            x = tanh(x)                                                                # BigGAN.py:580
-            return x
+    def _generator_trunk(self, levels, opt, block_info, new_z_dist=False):
+        """BigGAN.py:427-580: the first dense layer, the up blocks and the head.  ``levels``: (vector, width) of the first
+        level, then of every block.  With ``new_z_dist`` the per-level dense layers have run already (_latent_levels)."""
+        levels = iter(levels)
+
+        def next_z_split():
+            return next(levels)
+
+        counts = block_info["counts"]
+        ch_mul = 2 ** (len(counts) - 1)                                            # BigGAN.py:427
+        ch = self.g_channels_for_block(0, len(counts))
+
+        layer_z, z_dim = next_z_split()
+        f_width = self.round_up(z_dim * 1.85, 8)                                   # BigGAN.py:433 (z_dim includes the labels)
+        if new_z_dist:                                                             # BigGAN.py:444
+            x = fully_connected(layer_z, units=4 * 4 * ch, scope='first/dense', opt=opt)
+        elif not self.args.g_first_level_dense_layer:                              # BigGAN.py:444
+            x = fully_connected(layer_z, units=4 * 4 * ch, scope='dense', opt=opt)
+        elif self.activation_fn is relu:                                           # BigGAN.py:434-438
+            x = fully_connected(layer_z, units=f_width, scope='dense1', opt=opt)
+            x = relu(x)
+            x = fully_connected(x, units=4 * 4 * ch, scope='dense2', opt=opt)
+        else:
+            with S.variable_scope('first'):                                        # BigGAN.py:440-443
+                x = fully_connected(layer_z, units=f_width, scope='dense1', opt=opt)
+                x = opt["act"](x)
+                x = fully_connected(x, units=4 * 4 * ch, scope='dense2', opt=opt)
+        x = ops._resident_out(x.reshape(-1, 4, 4, ch))                             # BigGAN.py:446 (bf16 trunk from here)
+
+        b_i = 0
+        for block_count in counts:                                                 # BigGAN.py:449-489
+            x = self._grad_mark(x, 'resblock_up_' + str(ch_mul))
+            scope = 'resblock_up_' + str(ch_mul)
+            for sb_i in range(block_count):
+                layer_z, z_dim = next_z_split()
+                if block_count > 1:
+                    scope = scope + '_' + str(sb_i)                                # cumulative (BigGAN.py:455)
+                if self.args.g_other_level_dense_layer and not new_z_dist:         # BigGAN.py:457-462
+                    with S.variable_scope('z' + str(ch_mul)):
+                        zw = self.round_up(z_dim * 1.25, 8)                        # (z_dim includes the labels)
+                        layer_z = fully_connected(layer_z, units=zw, scope='dense1', opt=opt)
+                        layer_z = opt["act"](layer_z)
+                is_last_block = sb_i == block_count - 1 and b_i == len(counts) - 1
+                if self.args.g_no_last_resblock and is_last_block:                 # BigGAN.py:468-473
+                    with S.variable_scope(scope):
+                        x = upconv(x, ch, use_bias=False, opt=opt)
+                        x = cond_bn(x, layer_z, opt=opt)
+                        x = opt["act"](x)
+                        x = g_conv(x, ch, use_bias=False, opt=opt)
+                elif self.deep:                                                    # BigGAN.py:475-477
+                    x = resblock_up_cond_deep(x, layer_z, channels_out=ch, use_bias=True, opt=opt, scope=scope)
+                    x = resblock_up_cond_deep(x, layer_z, channels_out=ch, upscale=False, use_bias=True, opt=opt,
+                                              scope=scope + "_2")
+                else:
+                    x = resblock_up_condition(x, layer_z, channels=ch, use_bias=False, opt=opt, scope=scope)
+            b_i += 1
+            if b_i == block_info["sa_index"]:
+                x = self_attention_2(x, channels=ch, opt=opt, scope='self_attention')
+            ch = self.g_channels_for_block(b_i, len(counts))
+            ch_mul = ch_mul // 2
+
+        x = self._grad_mark(x, 'tail')
+        x = ops._bn_act(x, None, opt, _out_fp32=os.environ.get("BG_IMAGE_LAYERS", "") == "fp32")   # BigGAN.py:491-492
+        x = conv(x, channels=self.c_dim, kernel=self.g_rgb_mix_kernel, stride=1, pad=1, use_bias=False, opt=opt,
+                 scope='G_logit')                                                  # BigGAN.py:570
+        x = tanh(x)                                                                # BigGAN.py:580
+        return x
 
     ##################################################################################
     # Discriminator  (BigGAN.py:588-715)

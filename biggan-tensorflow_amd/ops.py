@@ -391,8 +391,12 @@ def _cbn_prefetch(z, subscopes, opt):
     each - and, backward, one launch instead of a weight-gradient, a bias-gradient and a split-K reduce each.
     ``subscopes``: scopes of the block, relative to the current one, whose 'batch_norm' the block will open.  The results
     wait in the run's dense cache for the fully_connected calls that would have computed them; anything unusual (first,
-    shape-only pass; non-default batch-norm types; a z that needs a gradient) simply leaves the cache empty."""
-    if z is None or _is_meta(z) or _is_dual(z) or not z.is_cuda or z.requires_grad:
+    shape-only pass; non-default batch-norm types) simply leaves the cache empty.  A z that needs a gradient (the learned
+    latents of --cls_embedding / --shared_z / --g_z_dense_concat, which set opt['cbn_group_dz']) gets its input gradient
+    from one more grouped launch; elsewhere such a z keeps the ungrouped path."""
+    if z is None or _is_meta(z) or _is_dual(z) or not z.is_cuda:
+        return
+    if z.requires_grad and not opt.get("cbn_group_dz"):
         return
     if os.environ.get("BG_GROUP_CBN", "1") == "0":                    # A/B switch
         return

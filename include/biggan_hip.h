@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 3
+#define BG_ABI_VERSION 4
 
 enum { BG_OK = 0, BG_ERR_ARG = 1, BG_ERR_LAUNCH = 2, BG_ERR_UNSUPPORTED = 3 };
 enum { BG_PAD_REFLECT = 0, BG_PAD_ZERO = 1 };
@@ -168,6 +168,35 @@ typedef struct BgDenseItem {
 } BgDenseItem;
 int bg_dense_group_fwd(const BgDenseItem* items_host, int n_items, int B, void* stream);
 int bg_dense_group_wgrad(const BgDenseItem* items_host, int n_items, int B, void* stream);
+/* Input gradient of a group whose items all read the SAME input rows (a latent that needs a gradient):
+ *   dx[b, :K] (+)= sum_i dy_i[b, :] w_i^T      (dy_i in y, w_i [K, N_i]; every item has the same K; dx rows lddx floats
+ *   apart; accumulate selects add vs overwrite).  One thread per element of dx, items and columns in a fixed order. */
+int bg_dense_group_dgrad(const BgDenseItem* items_host, int n_items, int B, void* dx, int lddx, int accumulate,
+                         void* stream);
+
+/* Latent fan-out / fan-in of the generator's shared class embedding and shared z (BigGAN.py:338-424): every level's
+ * vector [z_i | class vector | shared vector] is a column range of one packed buffer, written by ONE launch, and the
+ * gradients of the shared sources are reduced over all levels by ONE launch.  Both calls route column segments:
+ *   target t, element (b, c) (+)= sum over the segments with target == t that cover c, in array order, of
+ *                                 src[b * lds + src_col + c - dst_col]
+ *   fan-out: every column of every target is covered by exactly one segment (checked);
+ *   fan-in : any number of segments per column; a column no segment covers becomes 0 (or keeps its value).
+ * ``targets`` / ``segs`` are HOST arrays of BgLatentTarget / BgLatentSeg (copied into the launch), declared void* so
+ * that the ABI gains no new pointer types.  No atomics: one thread per output element. */
+#define BG_LATENT_MAX_TARGETS 8
+#define BG_LATENT_MAX_SEGS 48
+typedef struct BgLatentTarget {
+    float* dst;
+    int64_t ldd;
+    int32_t width, accumulate;
+} BgLatentTarget;
+typedef struct BgLatentSeg {
+    const float* src;
+    int64_t lds;
+    int32_t src_col, dst_col, width, target;
+} BgLatentSeg;
+int bg_latent_fanout(const void* targets_host, int n_targets, const void* segs_host, int n_segs, int B, void* stream);
+int bg_latent_fanin(const void* targets_host, int n_targets, const void* segs_host, int n_segs, int B, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Fused attention of self_attention_2 (ops.py:481-485): o = softmax(q k^T) v, no 1/sqrt(d) scale.
