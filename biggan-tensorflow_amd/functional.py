@@ -589,6 +589,96 @@ class Deconv2dFn(Function):
         return dx, dw, db, None, None, dacc, None
 
 
+class MixConvFn(Function):
+    """Several stride-1 convolutions of one input, each writing its channel slice of one output (bg_mixconv_*):
+    clown_conv (ops.py:403-436), string kernels (ops.py:52-59), dilation (ops.py:95).  ``spec``: per branch
+    (c_off, cb, k, dil, lo, pad_mode, transposed), see BgMixBranch; ``params``: (w, bias-or-None) per branch, conv kernels
+    [k,k,Cin,cb], transposed-conv kernels [k,k,cb,Cin].  The output has the union of the branches' channels; it is bf16
+    when x is (or bf16-resident mode) and its width is a multiple of 8, fp32 otherwise."""
+
+    @staticmethod
+    def _table(spec, ws, bs=None, dws=None):
+        t = (hip.BgMixBranch * len(spec))()
+        for i, (c_off, cb, k, dil, lo, mode, tr) in enumerate(spec):
+            e = t[i]
+            e.c_off, e.cb, e.k, e.dil, e.lo, e.pad_mode, e.transposed = c_off, cb, k, dil, lo, mode, tr
+            e.w = ws[i].data_ptr()
+            if bs is not None and bs[i] is not None:
+                e.bias = bs[i].data_ptr()
+            if dws is not None and dws[i] is not None:          # (None: no weight gradient for this branch)
+                e.dw, e.acc_w = dws[i][0].data_ptr(), int(dws[i][1])
+        return t
+
+    @staticmethod
+    def _desc(x, Ct, ydt):
+        N, H, W_, Cin = x.shape
+        compute = Precision.compute if x.dtype == torch.float32 and ydt == torch.float32 else hip.COMPUTE_BF16
+        return hip.conv_desc(N, H, W_, Cin, H, W_, Ct, 1, 1, 0, hip.PAD_ZERO, compute, dt(x),
+                             hip.BF16 if ydt == BF16 else hip.F32)
+
+    @staticmethod
+    def forward(ctx, x, spec, *params):
+        import ctypes
+        assert 1 <= len(spec) <= hip.MIX_MAX_BRANCHES and len(params) == 2 * len(spec)
+        ctx.fork = getattr(x, "bg_fork", None)
+        x = _c(x)
+        ws = [_c(w) for w in params[0::2]]
+        bs = [None if b is None else _c(b) for b in params[1::2]]
+        Ct = max(s[0] + s[1] for s in spec)
+        ydt = BF16 if (x.dtype == BF16 or Precision.resident) and Ct % 8 == 0 else torch.float32
+        y = torch.empty(tuple(x.shape[:3]) + (Ct,), dtype=ydt, device=x.device)
+        t = MixConvFn._table(spec, ws, bs)
+        check(lib().bg_mixconv_fwd(MixConvFn._desc(x, Ct, ydt), ctypes.cast(t, ctypes.c_void_p), len(spec), act(x),
+                                   act(y), Ct, stream()))
+        ctx.spec, ctx.x, ctx.ws, ctx.bs, ctx.Ct = spec, x, ws, bs, Ct
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        import ctypes
+        dy = _c(dy)
+        spec, x, ws, bs, Ct = ctx.spec, ctx.x, ctx.ws, ctx.bs, ctx.Ct
+        L = lib()
+        d = MixConvFn._desc(x, Ct, dy.dtype)
+        n = len(spec)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx, add_ = _fork_target(ctx.fork, x)
+            t = MixConvFn._table(spec, ws)
+            check(L.bg_mixconv_dgrad(d, ctypes.cast(t, ctypes.c_void_p), n, act(dy), Ct, act(dx), int(add_), stream()))
+            _fork_done(ctx.fork, dx)
+        grads = [None] * (2 * n)
+        if not _Mode.inputs_only:
+            dws, want = [], False
+            for i, w in enumerate(ws):
+                if not ctx.needs_input_grad[2 + 2 * i]:
+                    dws.append(None)
+                elif is_variable(w):
+                    dws.append(grad_slot(w))
+                    want = True
+                else:
+                    g = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+                    dws.append((g, False))
+                    grads[2 * i] = g
+                    want = True
+            if want:
+                t = MixConvFn._table(spec, ws, None, dws)
+                tp = ctypes.cast(t, ctypes.c_void_p)
+                nb = L.bg_mixconv_wgrad_workspace_bytes(d, tp, n)
+                wsp = workspace(nb, x.device)
+                check(L.bg_mixconv_wgrad(d, tp, n, act(x), act(dy), Ct, f32(wsp), nb, stream()))
+            dbias = []
+            for i, b in enumerate(bs):
+                if b is not None and ctx.needs_input_grad[3 + 2 * i]:
+                    if not dbias:             # bias gradients of every channel of the output, then each branch's slice
+                        dbias.append(torch.empty(Ct, dtype=torch.float32, device=x.device))
+                        _bias_grad(dy.view(-1, Ct), dbias[0])
+                    lo, cb = spec[i][0], spec[i][1]
+                    grads[2 * i + 1] = param_grad(b, True, lambda out, lo=lo, cb=cb: out.copy_(dbias[0][lo:lo + cb]))
+        ctx.x = ctx.ws = ctx.bs = None
+        return (dx, None) + tuple(grads)
+
+
 # ------------------------------------------------------------------------------------------
 # matmul family
 # ------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ import torch
 
 _LIB = None
 LIB_NAME = "libbiggan_hip.so"
-ABI_VERSION = 4
+ABI_VERSION = 5
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 PAD_REFLECT, PAD_ZERO = 0, 1
@@ -62,6 +62,16 @@ LATENT_MAX_TARGETS = 8
 LATENT_MAX_SEGS = 48
 
 
+class BgMixBranch(Structure):
+    """One branch of a multi-branch convolution (bg_mixconv_*); the entry points take a host array of them as void*."""
+    _fields_ = [("c_off", c_int32), ("cb", c_int32), ("k", c_int32), ("dil", c_int32), ("lo", c_int32),
+                ("pad_mode", c_int32), ("transposed", c_int32), ("acc_w", c_int32),
+                ("w", c_void_p), ("bias", c_void_p), ("dw", c_void_p)]
+
+
+MIX_MAX_BRANCHES = 8
+
+
 class BgAttn16Desc(Structure):
     _fields_ = [(n, c_int32) for n in ("B", "N", "Nk", "d", "dv", "reserved")] + \
                [(n, c_int64) for n in ("ldq", "sq", "ldk", "sk", "ldv", "sv", "ldo", "so",
@@ -103,6 +113,10 @@ SIGNATURES = {
     "bg_dense_group_dgrad": (c_int, [POINTER(BgDenseItem), c_int, c_int, _P, c_int, c_int, _P]),
     "bg_latent_fanout": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
     "bg_latent_fanin": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
+    "bg_mixconv_fwd": (c_int, [_CD, _P, c_int, _P, _P, c_int, _P]),
+    "bg_mixconv_dgrad": (c_int, [_CD, _P, c_int, _P, c_int, _P, c_int, _P]),
+    "bg_mixconv_wgrad_workspace_bytes": (c_size_t, [_CD, _P, c_int]),
+    "bg_mixconv_wgrad": (c_int, [_CD, _P, c_int, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_gemm_workspace_bytes": (c_size_t, [_GD]),
     "bg_gemm": (c_int, [_GD, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_attention2_supported": (c_int, [c_int, c_int, c_int, c_int]),

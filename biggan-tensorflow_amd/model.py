@@ -20,7 +20,7 @@ from . import functional as Fn
 from . import scope as S
 from . import hip
 from .ops import (fully_connected, resblock_up_condition, resblock_down, resblock, self_attention_2, conv, bn,
-                  resblock_up_cond_deep, resblock_down_deep, upconv, g_conv, cond_bn,
+                  resblock_up_cond_deep, resblock_down_deep, upconv, g_conv, cond_bn, mixed_resblock,
                   prelu, relu, lrelu, tanh, global_sum_pooling, discriminator_loss, generator_loss)
 from .DiffAugment import DiffAugment, draw as draw_augment
 from .utils import orthogonal_regularizer, orthogonal_regularizer_fc, l2_regularizer, round_up, cls_loss_fn
@@ -68,7 +68,6 @@ class BigGAN(GANBase):
         unsupported = [
             # (the reference accepts it and only re-splits z: no labels, no embedding; rejected as a likely mistake)
             ("cls_embedding without n_labels", args.cls_embedding and args.n_labels <= 0),
-            ("g_mixed_resblocks", args.g_mixed_resblocks),
             ("g_final_layer", args.g_final_layer), ("multi_head", args.multi_head),
             ("z_reconstruct", args.z_reconstruct), ("d_reconstruction", args.d_reconstruction),
             ("d_reconstruction_halfres", args.d_reconstruction_halfres),
@@ -140,6 +139,8 @@ class BigGAN(GANBase):
         self.d_compat_use_sn_in_critic_output = args.d_compat_use_sn_in_critic_output
         self.extension_32 = getattr(args, "extension_32", False)
         self.deep = args.deep                                                          # BigGAN.py:20
+        self.g_mixed_resblocks = args.g_mixed_resblocks                                # BigGAN.py:40-41
+        self.g_mixed_resblock_ch_div = args.g_mixed_resblock_ch_div
         self.cls_embedding = args.cls_embedding                                        # BigGAN.py:24-28
         self.cls_embedding_size = args.cls_embedding_size
         if self.cls_embedding and self.cls_embedding_size == 0:
@@ -485,6 +486,9 @@ class BigGAN(GANBase):
             b_i += 1
             if b_i == block_info["sa_index"]:
                 x = self_attention_2(x, channels=ch, opt=opt, scope='self_attention')
+            if self.g_mixed_resblocks:                                             # BigGAN.py:485-486
+                x = mixed_resblock(x, self.round_up(ch / self.g_mixed_resblock_ch_div, 8), ch, opt=opt,
+                                   scope='res_mixed' + str(ch_mul))
             ch = self.g_channels_for_block(b_i, len(counts))
             ch_mul = ch_mul // 2
 

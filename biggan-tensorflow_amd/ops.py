@@ -134,11 +134,15 @@ def subpixel_conv(x, channels, opt, kernel=3, scale=2, use_bias=True, scope='sub
 
 
 def decode_kernel_sizes(str):
-    raise NotImplementedError("mixed-kernel convolutions (ops.py:29) are outside the default hot path")
+    """ops.py:29-42: "32x3,32x5" -> {"slices": [{"size": 32, "kernel": 3}, ...], "total_channels": 64}."""
+    entries = [tuple(int(v) for v in item.split('x')) for item in str.split(',')]
+    slices = [{"size": width, "kernel": k} for width, k in entries]
+    return {"slices": slices, "total_channels": sum(width for width, _ in entries)}
 
 
 def encode_kernel_sizes(slices, ch_mul=1.0):
-    raise NotImplementedError("mixed-kernel convolutions (ops.py:44) are outside the default hot path")
+    """ops.py:44-45: the inverse, each width scaled by ch_mul and truncated (with a 1e-8 nudge against 2.9999...)."""
+    return ",".join("%dx%d" % (int(float(sl["size"]) * ch_mul + 1e-8), sl["kernel"]) for sl in slices)
 
 
 def _to(x, dtype):
@@ -163,10 +167,15 @@ def conv(x, channels, opt, kernel=4, stride=2, pad=0, dilation=1, use_bias=True,
     """ops.py:49-113.  ``_out_dtype`` (extension, bf16-resident mode): element type of the result.
     ``_accumulate_into`` (extension): add the result into an existing tensor in the kernel epilogue (fused residual sum)."""
     with variable_scope(scope) as full_scope:
-        if isinstance(kernel, str):
-            raise NotImplementedError("mixed-kernel convolutions (ops.py:52-59) are outside the default hot path")
+        if isinstance(kernel, str):                   # ops.py:52-59: one slice per entry, concatenated (one launch)
+            slices = decode_kernel_sizes(kernel)["slices"]
+            branches = [_MixBranch('conv' + str(sl["kernel"]) + "_slice", False, sl["size"], sl["kernel"],
+                                   (sl["kernel"] - 1) // 2, dilation) for sl in slices]
+            y = _mixconv(x, branches, opt, stride, use_bias)
+            return _mix_epilogue(y, _out_dtype, _accumulate_into)
         if dilation != 1:
-            raise NotImplementedError("dilation != 1")
+            y = _mixconv(x, [_MixBranch(None, False, channels, kernel, pad, dilation)], opt, stride, use_bias)
+            return _mix_epilogue(y, _out_dtype, _accumulate_into)
         N, H, W, Cin = x.shape
         pad_mode = hip.PAD_REFLECT
         pad_lo = pad_hi = 0
@@ -595,12 +604,124 @@ def resblock_down_deep(x_init, channels_out, opt, downscale=True, use_bias=True,
     return _add(x, x_skip)
 
 
+class _MixBranch:
+    """One convolution of a multi-branch launch: variables under ``scope`` (None: the current one), created as conv /
+    deconv would create them."""
+
+    def __init__(self, scope, transposed, channels, kernel, pad=0, dilation=1):
+        self.scope, self.transposed, self.channels, self.kernel = scope, transposed, channels, kernel
+        self.pad, self.dilation = pad, dilation
+
+
+def _mix_geometry(br, H, W, stride, opt):
+    """(lo, pad_mode) of a branch in the BgMixBranch convention; every branch must keep the H x W grid."""
+    k, d = br.kernel, br.dilation
+    if d != 1 and stride != 1:
+        raise ValueError("conv: dilation %d with stride %d (TF rejects dilation together with stride > 1)" % (d, stride))
+    if stride != 1:
+        raise NotImplementedError("mixed-kernel convolutions with stride %d" % stride)
+    if br.transposed:                                     # TF 'SAME' stride-1 conv2d_transpose: low crop (k-1)//2
+        return k - 1 - (k - 1) // 2, hip.PAD_ZERO
+    keff = (k - 1) * d + 1
+    if br.pad <= 0:
+        if keff != 1:
+            raise NotImplementedError("mixed-kernel / dilated conv without padding shrinks the map")
+        return 0, hip.PAD_REFLECT
+    pad_type = opt.get("conv", {}).get("padding_type", 'reflect')
+    if pad_type == 'zero':                                # TF 'SAME' with the effective kernel (k-1)*d+1
+        return (keff - 1) // 2, hip.PAD_ZERO
+    if pad_type != 'reflect':
+        raise ValueError("Unsupported padding type: " + str(pad_type))
+    lo, hi = br.pad, br.pad                               # ops.py:68-76: pad doubled and split floor / ceil
+    if lo + hi - keff + 1 != 0:
+        raise NotImplementedError("mixed-kernel / dilated conv whose reflect padding changes the map size")
+    if max(lo, hi) > min(H, W) - 1:
+        raise ValueError("tf.pad REFLECT: padding %d does not fit a %dx%d map" % (max(lo, hi), H, W))
+    return lo, hip.PAD_REFLECT
+
+
+def _mixconv(x, branches, opt, stride=1, use_bias=True):
+    """The branches' convolutions of x as ONE multi-branch launch (functional.MixConvFn), their outputs concatenated
+    along the channels in branch order.  Variables: per branch in order, what conv / deconv creates (kernel, its
+    regulariser, the spectral-norm ``u``, bias)."""
+    N, H, W, Cin = x.shape
+    if _is_dual(x):
+        raise NotImplementedError("mixed-kernel convolutions have no tangent pass (the generator only)")
+    store_scope = S.default_store().scope_name
+    spec, params, c_off = [], [], 0
+    for br in branches:
+        lo, mode = _mix_geometry(br, H, W, stride, opt)
+        with variable_scope(br.scope) if br.scope is not None else _null_scope():
+            full_scope = S.default_store().scope_name
+            if br.transposed:
+                reg = opt.get("conv", {}).get("regularizer", None)          # attached regardless of scope (ops.py:127)
+                shape = [br.kernel, br.kernel, br.channels, Cin]
+            else:
+                reg = opt.get("conv", {}).get("regularizer", None) if 'generator' in full_scope else None
+                shape = [br.kernel, br.kernel, Cin, br.channels]
+            w = get_variable("kernel", shape=shape, initializer=weight_init, regularizer=reg)
+            _regularize(w, reg)
+            wk = spectral_norm(w, _shape_only=_is_meta(x)) if opt.get("conv", {}).get("sn", True) else w
+            bias = get_variable("bias", [br.channels], initializer=S.constant_initializer(0.0)) if use_bias else None
+        if br.channels > 0:
+            spec.append((c_off, br.channels, br.kernel, br.dilation, lo, mode, int(br.transposed)))
+            params += [wk, bias]
+        c_off += br.channels
+    assert S.default_store().scope_name == store_scope
+    if _is_meta(x):
+        return _meta((N, H, W, c_off))
+    return Fn.MixConvFn.apply(x, tuple(spec), *params)
+
+
+class _null_scope:
+    def __enter__(self):
+        return None
+
+    def __exit__(self, *exc):
+        return False
+
+
+def _mix_epilogue(y, out_dtype, acc):
+    if out_dtype is not None:
+        y = _to(y, out_dtype)
+    return y if acc is None else _add(y, acc)
+
+
 def clown_conv(x, channels, opt, use_bias=True, scope='clown', z=None):
-    raise NotImplementedError("clown_conv (ops.py:403, --g_mixed_resblocks) is outside the default hot path")
+    """ops.py:403-436: transposed 4x4 / 3x3 / 2x2 and conv 3x3 / 5x5 / dilated 5x5 on x, concatenated (one
+    multi-branch launch), then bn (cond_bn when z is given) and PReLU - PReLU whatever opt['act'] is (ops.py:434)."""
+    split_ch = channels // 8
+    half_split_ch = split_ch // 2
+    other_half_split_ch = split_ch - half_split_ch
+    rest_split = channels - split_ch * 7
+    deconv4_ch = split_ch + rest_split
+    conv5_ch = split_ch
+    no_deconv2 = opt.get("mixed_conv_no_deconv2", False)
+    if no_deconv2:
+        deconv4_ch += half_split_ch
+        conv5_ch += other_half_split_ch
+    with variable_scope(scope):
+        branches = [_MixBranch("deconv4", True, deconv4_ch, 4), _MixBranch("deconv3", True, split_ch * 2, 3)]
+        if not no_deconv2:
+            branches.append(_MixBranch("deconv2", True, split_ch, 2))
+        branches += [_MixBranch("conv3", False, split_ch, 3, pad=1), _MixBranch("conv5", False, conv5_ch, 5, pad=2),
+                     _MixBranch("dilconv5", False, split_ch, 5, pad=4, dilation=2)]
+        concat = _mixconv(x, branches, opt, 1, use_bias)
+        return _bn_act(concat, z, dict(opt, act=prelu))
 
 
 def mixed_resblock(x, inner_channels, out_channels, opt, use_bias=False, z=None, scope='res_mixed'):
-    raise NotImplementedError("mixed_resblock (ops.py:433, --g_mixed_resblocks) is outside the default hot path")
+    """ops.py:438-442: x + proj(clown(x)), proj a 1x1 conv without bias (``use_bias`` is unused, as in the reference).
+    Without autograd (sampling) the residual is summed in proj's epilogue straight into x; with it, x is still read by
+    the clown's backward, so the sum is a separate add."""
+    with variable_scope(scope):
+        x_main, x_skip = _fork(x)
+        res = clown_conv(x_main, inner_channels, scope="clown", opt=opt, z=z)
+        if _is_meta(x) or torch.is_grad_enabled():
+            res = conv(res, channels=out_channels, kernel=1, stride=1, pad=0, use_bias=False, opt=opt, scope='proj')
+            return _add(res, x_skip)
+        return conv(res, channels=out_channels, kernel=1, stride=1, pad=0, use_bias=False, opt=opt, scope='proj',
+                    _accumulate_into=x_skip)
 
 
 def self_attention(x, channels, opt, scope='self_attention'):

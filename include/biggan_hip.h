@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 4
+#define BG_ABI_VERSION 5
 
 enum { BG_OK = 0, BG_ERR_ARG = 1, BG_ERR_LAUNCH = 2, BG_ERR_UNSUPPORTED = 3 };
 enum { BG_PAD_REFLECT = 0, BG_PAD_ZERO = 1 };
@@ -197,6 +197,51 @@ typedef struct BgLatentSeg {
 } BgLatentSeg;
 int bg_latent_fanout(const void* targets_host, int n_targets, const void* segs_host, int n_segs, int B, void* stream);
 int bg_latent_fanin(const void* targets_host, int n_targets, const void* segs_host, int n_segs, int B, void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Multi-branch stride-1 convolution (ops.py:403-436 clown_conv, ops.py:52-59 string kernels, ops.py:95 dilation):
+ * several convolutions of ONE input x[N,H,W,Cin], each writing its own channel slice of one output row.
+ * ``table`` is a HOST array of n BgMixBranch (copied into the launch by value, so it may die after the call and a
+ * captured graph keeps it), declared void* so that the ABI gains no new pointer types.  Per branch:
+ *   y[n,p,q,c_off+c] = bias[c] + sum_{i,j<k} sum_ci x[n, P(p - lo + i*dil), P(q - lo + j*dil), ci] * W(i,j,ci,c)
+ * with P the padding (BG_PAD_REFLECT: tf.pad REFLECT, the index mirrored at the border without repeating it;
+ * BG_PAD_ZERO: taps outside the image read 0) and W the branch kernel:
+ *   transposed = 0: w [k,k,Cin,cb] (conv, ops.py:88),              W(i,j,ci,c) = w[i][j][ci][c]
+ *   transposed = 1: w [k,k,cb,Cin] (stride-1 conv2d_transpose SAME, ops.py:127), stored as a correlation with the
+ *                   flipped kernel: W(i,j,ci,c) = w[k-1-i][k-1-j][c][ci], lo = k - 1 - TF's low crop.
+ * Geometry from the descriptor: N, H, W, Cin, Ho = H, Wo = W, stride 1; x_dtype names x / dx, y_dtype y / dy
+ * (BG_F32 or BG_BF16); with fp32 x and y, compute = BG_COMPUTE_BF16 rounds x and w to bf16 as they are read,
+ * BG_COMPUTE_F32 is an exact fp32 FMA chain.  bf16 tensors are multiplied as bf16 x bf16 (w rounded to bf16) with
+ * fp32 accumulation; with bf16 x and y / dy and Cin % 32 == 0 the three passes are implicit GEMMs on
+ * v_mfma_f32_16x16x32_bf16.  y / dy rows are ldy elements apart (the branches' slices may sit inside a wider tensor whose
+ * other channels are left untouched); x / dx rows are Cin apart.  Any branch width; at most BG_MIX_MAX_BRANCHES.
+ * Reflect padding needs lo <= H-1, W-1 and the high overhang (k-1)*dil - lo <= H-1, W-1 (TF's rule).
+ * Deterministic: no atomics; the weight gradient's split-K slabs (ws) are reduced in a fixed order.
+ * ------------------------------------------------------------------------------------------ */
+#define BG_MIX_MAX_BRANCHES 8
+typedef struct BgMixBranch {
+    int32_t c_off;         /* first channel of the branch in a row of y / dy                              */
+    int32_t cb;            /* branch width (output channels)                                             */
+    int32_t k, dil, lo;    /* taps per axis, dilation, low tap offset                                    */
+    int32_t pad_mode;      /* BG_PAD_REFLECT / BG_PAD_ZERO                                               */
+    int32_t transposed;    /* 0: conv kernel [k,k,Cin,cb]; 1: transposed-conv kernel [k,k,cb,Cin]         */
+    int32_t acc_w;         /* weight gradient: 1 adds into dw, 0 overwrites                               */
+    const float* w;        /* fp32 kernel in the variable's layout                                       */
+    const float* bias;     /* forward, nullable: [cb]                                                    */
+    float* dw;             /* weight gradient (same layout as w), NULL: none for this branch; bias gradients
+                              come from bg_bias_grad_t */
+} BgMixBranch;
+/* forward: y[..., c_off : c_off + cb] = branch(x) for every branch */
+int bg_mixconv_fwd(const BgConvDesc* d, const void* table_host, int n_branches, const void* x, void* y, int ldy,
+                   void* stream);
+/* input gradient: dx (+)= sum over branches of the adjoint of the branch (reflect padding folded back at the border),
+ * summed in registers; one thread per element of dx */
+int bg_mixconv_dgrad(const BgConvDesc* d, const void* table_host, int n_branches, const void* dy, int ldy, void* dx,
+                     int accumulate, void* stream);
+/* weight gradients of every branch (dw of each table entry, fp32, (+)= per acc_w) */
+size_t bg_mixconv_wgrad_workspace_bytes(const BgConvDesc* d, const void* table_host, int n_branches);
+int bg_mixconv_wgrad(const BgConvDesc* d, const void* table_host, int n_branches, const void* x, const void* dy,
+                     int ldy, void* ws, size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Fused attention of self_attention_2 (ops.py:481-485): o = softmax(q k^T) v, no 1/sqrt(d) scale.
