@@ -7,6 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import launch_replay as R
+from tests.test_gpu_launch_replay import replay_and_check
+
 pytestmark = pytest.mark.gpu
 
 
@@ -23,6 +26,13 @@ def _dot(a, b):
 def _rnd(shape, seed, scale=1.0):
     g = torch.Generator(device="cuda").manual_seed(seed)
     return torch.randn(shape, device="cuda", generator=g) * scale
+
+
+def _cotangent(y, seed):
+    """g = y + r with r random at y's scale: <y, g> ~ |y|^2 is far above the identities' tolerance, so a dgrad or wgrad
+    that returns zeros fails them (an independent g has <y, g> ~ |y||g| / sqrt(numel), below the tolerance)."""
+    y = y.detach().float()
+    return y + _rnd(tuple(y.shape), seed, float(y.double().pow(2).mean().sqrt()))
 
 
 # (kind, N, H, Cin, Cout, k, s): the layer shapes of G-128 / D-128 at ch = 64, batch 64 (D sees 2B = 128)
@@ -54,11 +64,12 @@ def test_adjoint_identities_full_size(kind, N, H, Cin, Cout, k, s, mode):
         else:
             w = _rnd((k, k, Cout, Cin), 2, 0.05).requires_grad_(True)
             y = Fn.Deconv2dFn.apply(x, w, None, s, 1, None)
-        g = _rnd(tuple(y.shape), 3)
+        g = _cotangent(y, 3)
         y.backward(g)
         lhs = _dot(y.detach(), g)
         scale = float(y.detach().double().norm() * g.double().norm())
         tol = (2e-2 if mode == "bf16" else 2e-4) * scale
+        assert abs(lhs) >= 10 * tol, (lhs, tol)            # a zero gradient cannot pass
         assert abs(lhs - _dot(x.detach(), x.grad)) <= tol, (lhs, _dot(x.detach(), x.grad), scale)
         assert abs(lhs - _dot(w.detach(), w.grad)) <= tol, (lhs, _dot(w.detach(), w.grad), scale)
         assert torch.isfinite(y).all()
@@ -162,11 +173,12 @@ def test_adjoint_identities_config3_bf16_resident(kind, N, H, Cin, Cout, k, s):
             w = _rnd((k, k, Cout, Cin), 2, 0.05).requires_grad_(True)
             y = Fn.Deconv2dFn.apply(x, w, None, s, 1, None)
         assert y.dtype == torch.bfloat16
-        g = _rnd(tuple(y.shape), 3).bfloat16()
+        g = _cotangent(y, 3).bfloat16()
         y.backward(g)
         lhs = _dot(y.detach().float(), g.float())
         scale = float(y.detach().double().norm() * g.double().norm())
         tol = 2e-2 * scale
+        assert abs(lhs) >= 10 * tol, (lhs, tol)            # a zero gradient cannot pass
         wb = w.detach().bfloat16().float()          # the kernels see the packed bf16 copy of w
         assert abs(lhs - _dot(x.detach().float(), x.grad.float())) <= tol
         assert abs(lhs - _dot(wb, w.grad)) <= tol
@@ -180,7 +192,8 @@ def test_full_size_bf16_iteration_configs_3_4_5(img, ch, B):
     """One D + G iteration of BASELINE configs 3, 4 and 5 at the per-GPU batch BASELINE.json states (32 / 32 / 64),
     --precision bf16: finite losses in the range of a random-init hinge GAN, the D op's forward bit-reproducible from
     identical state and inputs, gradients reproducible (no atomics in any GEMM), every gradient and parameter finite,
-    u / Adam / EMA state advancing.  (Config 5 needs ~150 GB of HBM for its activations at batch 64.)"""
+    u / Adam / EMA state advancing.  (Config 5 needs ~150 GB of HBM for its activations at batch 64.)  Every GEMM-family
+    launch of the iteration is then replayed against float64 (tests/launch_replay.py), with the model freed."""
     from tests.common import make_args
     import biggan_tensorflow_amd  # noqa: F401
     from biggan_tensorflow_amd import model, scope as S, functional as Fn
@@ -208,12 +221,17 @@ def test_full_size_bf16_iteration_configs_3_4_5(img, ch, B):
         gan.store.load_arrays(state, reset_ema=False)
         u0 = gan.store.vars["generator/first/dense2/u"].clone()
         w0 = gan.g_arena.params[:4096].clone()
-        losses = gan.train_step(real)
+        with R.Recorder() as rec:                    # every GEMM-family launch of the iteration's D and G ops
+            losses = gan.train_step(real)
         assert all(np.isfinite(v.item()) for v in losses.values())
         assert not torch.equal(gan.store.vars["generator/first/dense2/u"], u0)
         assert not torch.equal(gan.g_arena.params[:4096], w0)
         assert torch.isfinite(gan.g_arena.grads).all() and torch.isfinite(gan.g_arena.params).all()
         assert torch.isfinite(gan.d_arena.grads).all() and torch.isfinite(gan.d_arena.params).all()
+        del losses, real, z, dr, df, state, u0, w0
+        gan = None                                   # (config 5's activations alone take ~150 GB)
+        torch.cuda.empty_cache()
+        replay_and_check(rec, "c%d@%d" % ({128: 3, 256: 4, 512: 5}[img], B))
     finally:
         Fn.set_precision("fp32")
         gan = None
