@@ -1614,6 +1614,98 @@ class TanhFn(Function):
         return dx
 
 
+# ------------------------------------------------------------------------------------------
+# RGBA images (--c_dim 4): the generator's alpha helper and the discriminator's alpha mask (alpha.hip).  The image is
+# an fp32 [..., 4] tensor in every precision.
+# ------------------------------------------------------------------------------------------
+def _rgba_rows(x):
+    if x.dtype != torch.float32 or x.shape[-1] != 4:
+        raise ValueError("alpha ops take an fp32 [..., 4] image, got %s %s" % (x.dtype, tuple(x.shape)))
+    return x.numel() // 4
+
+
+class AlphaHeadFn(Function):
+    """tanh(r, g, b, a + w (r + g + b + a)) with the learned scalar w = generator/alphahelper_w (BigGAN.py:572-580).
+    Saves x only: the backward recomputes tanh in its single pass and delivers dL/dw into w's gradient slot."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        x = _c(x)
+        rows = _rgba_rows(x)
+        y = torch.empty_like(x)
+        check(lib().bg_alpha_head_fwd(f32(x), f32(w), f32(y), rows, stream()))
+        ctx.x, ctx.w = x, w
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _c(dy)
+        x, w = ctx.x, ctx.w
+        rows = x.numel() // 4
+        L = lib()
+        dx = torch.empty_like(x)
+        done = []
+
+        def prod(out):                  # dx and dw in one launch; the kernel adds dw into `out`
+            out.zero_()
+            check(L.bg_alpha_head_bwd(f32(x), f32(w), f32(dy), f32(dx), f32(out), rows, stream()))
+            done.append(True)
+        dw = param_grad(w, ctx.needs_input_grad[1], prod)
+        if not done:
+            check(L.bg_alpha_head_bwd(f32(x), f32(w), f32(dy), f32(dx), None, rows, stream()))
+        ctx.x = ctx.w = None
+        return dx, dw
+
+
+class AlphaMaskFn(Function):
+    """rgb' = (rgb + 1)(a + 1)/2 - 1, alpha unchanged (BigGAN.py:616-619), the first op of the discriminator."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x)
+        rows = _rgba_rows(x)
+        y = torch.empty_like(x)
+        check(lib().bg_alpha_mask_fwd(f32(x), f32(y), rows, stream()))
+        ctx.x = x
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _c(dy)
+        x = ctx.x
+        dx = torch.empty_like(x)
+        check(lib().bg_alpha_mask_bwd(f32(x), f32(dy), f32(dx), x.numel() // 4, stream()))
+        ctx.x = None
+        return dx
+
+
+class AlphaMaskTangentFn(Function):
+    """Forward-mode tangent of the alpha mask at x: ydot_rgb = (xdot_rgb (a + 1) + (rgb + 1) xdot_a)/2, ydot_a = xdot_a.
+    The gradient penalty's forward-mode pass starts at the constant x^ (model.BigGAN.gradient_penalty), so only xdot's
+    gradient exists: the map is linear in xdot with the mask's own backward as its adjoint."""
+
+    @staticmethod
+    def forward(ctx, xdot, x):
+        if x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("alpha mask tangent: no gradient through the primal (it is a constant of the "
+                                      "gradient penalty's forward-mode pass)")
+        xdot, x = _c(xdot), _c(x)
+        rows = _rgba_rows(x)
+        y = torch.empty_like(x)
+        check(lib().bg_alpha_mask_tangent(f32(x), f32(xdot), f32(y), rows, stream()))
+        ctx.x = x
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _c(dy)
+        x = ctx.x
+        dxdot = torch.empty_like(x)
+        check(lib().bg_alpha_mask_bwd(f32(x), f32(dy), f32(dxdot), x.numel() // 4, stream()))
+        ctx.x = None
+        return dxdot, None
+
+
 class ScaleFn(Function):
     """a * x with a host scalar a (fp32 tensors)."""
 

@@ -12,7 +12,7 @@ import torch
 
 _LIB = None
 LIB_NAME = "libbiggan_hip.so"
-ABI_VERSION = 5
+ABI_VERSION = 6
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 PAD_REFLECT, PAD_ZERO = 0, 1
@@ -166,6 +166,11 @@ SIGNATURES = {
     "bg_tanh_fwd": (c_int, [_P, _P, c_int64, _P]),
     "bg_tanh_bwd": (c_int, [_P, _P, _P, c_int64, _P]),
     "bg_bias_grad": (c_int, [_P, _P, c_int64, c_int, _P]),
+    "bg_alpha_head_fwd": (c_int, [_P, _P, _P, c_int64, _P]),
+    "bg_alpha_head_bwd": (c_int, [_P, _P, _P, _P, _P, c_int64, _P]),
+    "bg_alpha_mask_fwd": (c_int, [_P, _P, c_int64, _P]),
+    "bg_alpha_mask_bwd": (c_int, [_P, _P, _P, c_int64, _P]),
+    "bg_alpha_mask_tangent": (c_int, [_P, _P, _P, c_int64, _P]),
     "bg_diffaugment_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "bg_diffaugment_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "bg_hinge_d_sums": (c_int, [_P, _P, _P, c_int, _P]),

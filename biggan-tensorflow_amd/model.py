@@ -21,7 +21,8 @@ from . import scope as S
 from . import hip
 from .ops import (fully_connected, resblock_up_condition, resblock_down, resblock, self_attention_2, conv, bn,
                   resblock_up_cond_deep, resblock_down_deep, upconv, g_conv, cond_bn, mixed_resblock,
-                  prelu, relu, lrelu, tanh, global_sum_pooling, discriminator_loss, generator_loss)
+                  prelu, relu, lrelu, tanh, alpha_helper_tanh, alpha_mask, global_sum_pooling, discriminator_loss,
+                  generator_loss)
 from .DiffAugment import DiffAugment, draw as draw_augment
 from .utils import orthogonal_regularizer, orthogonal_regularizer_fc, l2_regularizer, round_up, cls_loss_fn
 
@@ -72,11 +73,12 @@ class BigGAN(GANBase):
             ("z_reconstruct", args.z_reconstruct), ("d_reconstruction", args.d_reconstruction),
             ("d_reconstruction_halfres", args.d_reconstruction_halfres),
             ("d_reconstruction_texture", args.d_reconstruction_texture), ("d_final_conv", args.d_final_conv),
-            ("c_dim!=3", args.c_dim != 3),
         ]
         bad = [n for n, v in unsupported if v]
         if bad:
             raise NotImplementedError("flags outside the MI355X hot path (SURVEY.md section 8): " + ", ".join(bad))
+        if args.c_dim not in (1, 3, 4):                                                # TF decode_png: 1, 3 or 4 channels
+            raise ValueError("--c_dim %d: images have 1 (grayscale), 3 (RGB) or 4 (RGBA) channels" % args.c_dim)
         self.gan_type = args.gan_type
         self.d_loss_func = args.d_loss_func if args.d_loss_func else self.gan_type     # BigGAN.py:127-128
         if self.gan_type not in Fn.GAN_LOSS_KINDS or self.d_loss_func not in Fn.GAN_LOSS_KINDS:
@@ -131,6 +133,8 @@ class BigGAN(GANBase):
         self.bias_in_sa = args.bias_in_sa
         self.bn_in_d = args.bn_in_d
         self.c_dim = args.c_dim
+        self.alpha_mask = self.c_dim == 4 and args.alpha_mask                          # BigGAN.py:616
+        self.g_alpha_helper = self.c_dim == 4 and args.g_alpha_helper                  # BigGAN.py:572
         self.g_rgb_mix_kernel = args.g_rgb_mix_kernel
         self.z_trunc_train = args.z_trunc_train
         self.g_learning_rate, self.d_learning_rate = args.g_lr, args.d_lr
@@ -496,6 +500,8 @@ class BigGAN(GANBase):
         x = ops._bn_act(x, None, opt, _out_fp32=os.environ.get("BG_IMAGE_LAYERS", "") == "fp32")   # BigGAN.py:491-492
         x = conv(x, channels=self.c_dim, kernel=self.g_rgb_mix_kernel, stride=1, pad=1, use_bias=False, opt=opt,
                  scope='G_logit')                                                  # BigGAN.py:570
+        if self.g_alpha_helper:                                                    # BigGAN.py:572-580
+            return alpha_helper_tanh(x)
         x = tanh(x)                                                                # BigGAN.py:580
         return x
 
@@ -520,6 +526,8 @@ class BigGAN(GANBase):
         outputs = {}
         self._sn_prefetch("discriminator", x)
         with S.variable_scope("discriminator", reuse=reuse):
+            if self.alpha_mask:                                                        # BigGAN.py:616-619
+                x = alpha_mask(x)
             ch = self.d_channels_for_block(0)
             block_info = self.d_block_info()
             b_i = 0

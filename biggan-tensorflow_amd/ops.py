@@ -905,6 +905,26 @@ def tanh(x):
     return Fn.TanhFn.apply(x)
 
 
+def alpha_helper_tanh(x):
+    """BigGAN.py:572-580 (--c_dim 4 --g_alpha_helper): a' = a + w (r + g + b + a) with the learned scalar
+    ``alphahelper_w`` (initial value 5, no regulariser, no spectral norm) created in the current scope, then tanh over
+    all four channels - one launch.  (The reference's rgb_w, BigGAN.py:574, is never used and is not built.)"""
+    w = get_variable("alphahelper_w", shape=[], initializer=S.constant_initializer(5.0))
+    if _is_meta(x):
+        return _meta(x.shape)
+    return Fn.AlphaHeadFn.apply(x, w)
+
+
+def alpha_mask(x):
+    """BigGAN.py:616-619 (--c_dim 4 --alpha_mask): rgb' = (rgb + 1)(a + 1)/2 - 1, alpha unchanged.  On a ``Dual`` the
+    primal takes the mask and the tangent its forward-mode map at the primal."""
+    if _is_meta(x):
+        return _meta(x.shape)
+    if _is_dual(x):
+        return Dual(Fn.AlphaMaskFn.apply(x.p), Fn.AlphaMaskTangentFn.apply(x.t, x.p))
+    return Fn.AlphaMaskFn.apply(x)
+
+
 ##################################################################################
 # Normalization function
 ##################################################################################

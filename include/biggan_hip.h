@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 5
+#define BG_ABI_VERSION 6
 
 enum { BG_OK = 0, BG_ERR_ARG = 1, BG_ERR_LAUNCH = 2, BG_ERR_UNSUPPORTED = 3 };
 enum { BG_PAD_REFLECT = 0, BG_PAD_ZERO = 1 };
@@ -454,6 +454,25 @@ int bg_scale_dev(const float* x, const float* s_dev, float* y, int64_t n, void* 
 int bg_tanh_fwd(const float* x, float* y, int64_t n, void* stream);
 int bg_tanh_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream);
 int bg_bias_grad(const float* dy, float* db, int64_t rows, int C, void* stream);         /* db[c] = sum_rows dy */
+
+/* --------------------------------------------------------------------------------------------
+ * RGBA images (--c_dim 4; alpha.hip).  fp32 NHWC tensors of `rows` pixels x 4 channels (r, g, b, a), 16-byte aligned.
+ *   alpha helper (BigGAN.py:572-580), between G_logit and tanh, with w = generator/alphahelper_w ([] in device memory):
+ *     y = tanh(r, g, b, a + w (r + g + b + a))   (the sum includes the alpha logit itself)
+ *   bwd, one pass with g = dy (1 - y^2) (y recomputed from x): dx_c = g_c + w g_a (colour), dx_a = g_a (1 + w);
+ *     dw_accum[0] += sum over pixels of g_a (r + g + b + a): per-block fp64 partials added in a fixed order, no
+ *     atomics (dw_accum NULL: no weight gradient).
+ *   alpha mask (BigGAN.py:616-619), D's input: rgb' = (rgb + 1)(a + 1)/2 - 1, alpha unchanged;
+ *     bwd: dx_rgb = dy_rgb (a + 1)/2, dx_a = dy_a + sum_c dy_c (rgb_c + 1)/2;
+ *     tangent (forward mode, the gradient penalty's pass): ydot_rgb = (xdot_rgb (a + 1) + (rgb + 1) xdot_a)/2,
+ *     ydot_a = xdot_a.
+ * ------------------------------------------------------------------------------------------ */
+int bg_alpha_head_fwd(const float* x, const float* w, float* y, int64_t rows, void* stream);
+int bg_alpha_head_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw_accum, int64_t rows,
+                      void* stream);
+int bg_alpha_mask_fwd(const float* x, float* y, int64_t rows, void* stream);
+int bg_alpha_mask_bwd(const float* x, const float* dy, float* dx, int64_t rows, void* stream);
+int bg_alpha_mask_tangent(const float* x, const float* xdot, float* ydot, int64_t rows, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * bf16-resident data path (BASELINE configs 3-5): "_t" forms of the bandwidth-bound kernels above.  Activation
