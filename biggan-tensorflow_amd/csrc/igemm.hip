@@ -1040,6 +1040,24 @@ static void conv16_dgrad_params(const BgConvDesc* d, bool padded, NN16Params& p)
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// Reflect padding on the HIGH side only: the k = 2 convolution of subpixel_conv (ops.py:23-27: pad 0.5 -> 0 low, 1 high).
+// The mirrored-source forms of the input gradient (the fp32 MIRROR kernels, the ring launches) assume low = high, so this
+// geometry takes the gradient on the padded grid and folds it back (launch_reflect_fold), in both precisions.
+static int conv_pad_hi(const BgConvDesc* d) { return (d->Ho - 1) * d->stride + d->k - 1 - d->pad_lo - (d->H - 1); }
+static bool reflect_hi_only(const BgConvDesc* d) {
+    return d->pad_mode == BG_PAD_REFLECT && d->pad_lo == 0 && conv_pad_hi(d) > 0;
+}
+
+// fp32-tensor launch of the input gradient on the padded grid of a reflect_hi_only geometry (stride 1)
+static void conv_dgrad_padded_params(const BgConvDesc* d, NNParams& p) {
+    conv_dgrad_params(d, p);
+    Gather& g = p.g;
+    g.Ho = padded_extent(d->Ho, d->k, d->stride);
+    g.Wo = padded_extent(d->Wo, d->k, d->stride);
+    g.Hq = g.Ho; g.Wq = g.Wo; g.pad = 0; g.reflect = 0;
+    p.M = d->N * g.Hq * g.Wq;
+}
+
 // Input gradient of a reflect-padded 3 x 3 convolution WITHOUT the padded grid (ops.py:81-82, 94 under autodiff): the
 // plain transposed gather on the H x W map (zero-padding semantics: halo-tile kernel on 16 / 32 / 64 maps, position-major
 // tap kernel on 4 x 4 / 8 x 8) plus two thin launches that add the taps of the mirrored padded rows / columns into
@@ -1104,11 +1122,45 @@ int bg_conv2d_fwd(const BgConvDesc* d, const void* x, const void* w, const float
                      (int64_t)p.M * d->Cout, true, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
 }
 
+// the forward launch of d with the depth-to-space store (NN16Params::d2s_c), or false when d / block do not describe one
+static bool conv16_d2s_params(const BgConvDesc* d, int block, NN16Params& r) {
+    if (!d || block != 2 || !resident_fwd(d) || !d->w_packed || d->stride != 1 || d->Ho != d->H || d->Wo != d->W ||
+        d->Cout % 32 || d->Cin % 8)
+        return false;
+    NNParams p;
+    conv_fwd_params(d, p);
+    nn16_from(p, r);
+    r.d2s_c = d->Cout / 4;
+    return true;
+}
+
+int bg_conv2d_fwd_d2s_supported(const BgConvDesc* d, int block) {
+    NN16Params r;
+    if (!conv16_d2s_params(d, block, r) || check_conv(d) != BG_OK) return 0;
+    return nn16_d2s_ok(r, GATHER_CONV, 1) ? 1 : 0;
+}
+
+int bg_conv2d_fwd_d2s(const BgConvDesc* d, const void* x, const void* w, const float* bias, const float* alpha_dev,
+                      void* y, int block, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_conv(d);
+    if (rc) return rc;
+    BG_REQUIRE(x && w && y, "bg_conv2d_fwd_d2s: null tensor pointer");
+    NN16Params r;
+    BG_REQUIRE(conv16_d2s_params(d, block, r) && nn16_d2s_ok(r, GATHER_CONV, 1),
+               "bg_conv2d_fwd_d2s: this launch has no fused depth-to-space store (query bg_conv2d_fwd_d2s_supported)");
+    (void)ws; (void)ws_bytes;                  // supported launches never split K
+    Tag tag("conv2d_fwd_d2s", d);
+    r.A = x; r.B = w; r.bias = bias; r.alpha = alpha_dev; r.out = y; r.accumulate = 0;
+    r.out_f32 = d->y_dtype == BG_F32;
+    ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
+    return launch_nn16(r, GATHER_CONV, 1, (int64_t)r.M * d->Cout, nullptr, 0, as_stream(stream));
+}
+
 size_t bg_conv2d_dgrad_workspace_bytes(const BgConvDesc* d) {
     if (!d) return 0;
     const int z = d->stride * d->stride;
     if (resident_dgrad(d)) {
-        const bool padded = d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && !dgrad_ring_ok(d);
+        const bool padded = (d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && !dgrad_ring_ok(d)) || reflect_hi_only(d);
         NN16Params p;
         conv16_dgrad_params(d, padded, p);
         p.g.reflect = 0;
@@ -1116,6 +1168,13 @@ size_t bg_conv2d_dgrad_workspace_bytes(const BgConvDesc* d) {
         size_t b = nn16_workspace_bytes(p, GATHER_TCONV, z, out_elems);
         if (padded) b = align256(b) + align256((size_t)out_elems * (d->x_dtype == BG_F32 ? 4 : 2));
         return b;
+    }
+    if (reflect_hi_only(d) && d->stride == 1) {
+        NNParams p;
+        conv_dgrad_padded_params(d, p);
+        const int64_t out_elems = (int64_t)p.M * d->Cin;
+        return align256(nn_workspace_bytes(p.M, d->Cin, 1, tconv_min_iters(d, d->Cout), out_elems)) +
+               align256((size_t)out_elems * sizeof(float));
     }
     UnevenPhases uneven(d);
     return nn_workspace_bytes((int64_t)d->N * (d->H / d->stride) * (d->W / d->stride), d->Cin, z,
@@ -1131,7 +1190,7 @@ int bg_conv2d_dgrad(const BgConvDesc* d, const void* dy, const void* w, const fl
     Tag tag("conv2d_dgrad", d);
     if (resident_dgrad(d)) {
         const bool ring = d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && dgrad_ring_ok(d);
-        const bool padded = d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && !ring;
+        const bool padded = (d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && !ring) || reflect_hi_only(d);
         NN16Params r;
         conv16_dgrad_params(d, padded, r);
         r.g.reflect = 0;                        // (the mirrored taps are the ring launches' / the fold's business)
@@ -1165,6 +1224,24 @@ int bg_conv2d_dgrad(const BgConvDesc* d, const void* dy, const void* w, const fl
                                    as_stream(stream));
     }
     BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32 && !d->w_packed, "bg_conv2d_dgrad: unsupported dtype mix");
+    if (reflect_hi_only(d)) {
+        BG_REQUIRE(d->stride == 1 && d->Cin % 8 == 0,
+                   "bg_conv2d_dgrad: reflect padding on the high side only needs stride 1 and Cin %% 8 == 0 (Cin=%d)", d->Cin);
+        NNParams p;
+        conv_dgrad_padded_params(d, p);
+        const int64_t out_elems = (int64_t)p.M * d->Cin;
+        const size_t pbytes = align256((size_t)out_elems * sizeof(float));
+        BG_REQUIRE(ws && ws_bytes >= pbytes, "bg_conv2d_dgrad: workspace too small for the padded gradient");
+        p.A = (const float*)dy; p.B = (const float*)w; p.alpha = alpha_dev; p.out = (float*)ws; p.accumulate = 0;
+        const bool vec = (d->Cout % 4 == 0) && aligned16(dy) && aligned16(w);
+        char* slabs = reinterpret_cast<char*>(ws) + pbytes;
+        ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
+        rc = launch_nn(p, GATHER_TCONV, true, false, vec, 1, tconv_min_iters(d, d->Cout), out_elems, true,
+                       ws_bytes > pbytes ? slabs : nullptr, ws_bytes - pbytes, as_stream(stream),
+                       d->compute == BG_COMPUTE_BF16);
+        if (rc) return rc;
+        return launch_reflect_fold(ws, dx, 1, d->N, d->H, d->W, d->Cin, p.g.Ho, p.g.Wo, 0, accumulate, as_stream(stream));
+    }
     UnevenPhases uneven(d);
     NNParams p;
     conv_dgrad_params(d, p);

@@ -42,6 +42,9 @@ struct NN16Params {
                             // tap) pair except (real, real) is walked.  Together with the plain zero-padding launch
                             // (real, real) that is every padded position folded onto the pixel it mirrors (ops.py:82)
     int32_t ring_lines;     // 2: both borders mirror (stride 1); 1: only the low border does (stride 2, even maps)
+    int32_t d2s_c;          // > 0 (stride-1 forward gathers, N = 4 d2s_c, d2s_c % 8 == 0): the epilogue stores depth-to-space -
+                            // out is [Nb, 2 Ho, 2 Wo, d2s_c] and column (2 i + j) d2s_c + c of pixel (ho, wo) goes to channel c
+                            // of pixel (2 ho + i, 2 wo + j) (ops.py:23-27 subpixel_conv); launches that pass nn16_d2s_ok only
 };
 
 struct TN16Params {
@@ -69,6 +72,9 @@ int64_t nn16_stats_rows(const NN16Params& p, int mode, int zdim);
 // the mirrored-tap launch of a reflect-padded convolution's input gradient (p.ring = 1, p.ring_lines, p.g of the plain
 // launch, accumulate = 1): see NN16Params::ring
 int launch_nn16_ring(NN16Params& p, hipStream_t s);
+// whether a forward gather with p.d2s_c set takes a kernel form whose epilogue has the depth-to-space store: the halo-tile
+// form, or the tap kernel with image-major rows and no split-K
+bool nn16_d2s_ok(const NN16Params& p, int mode, int zdim);
 bool nn16h_d2s_ok(const NN16Params& p);                    // 8-channel stride-2 input gradients: depth-to-space halo form
 int launch_nn16h_d2s(const NN16Params& plain, hipStream_t s);
 size_t tn16_workspace_bytes(const TN16Params& p);

@@ -49,7 +49,9 @@ typedef __attribute__((address_space(1))) const void gbl_void_t;
 typedef __attribute__((address_space(3))) s16x4v lds_s16x4v;
 
 // the source of every out-of-range 16-byte chunk (zero-initialised device memory of the code object)
-__device__ uint4 g_zero_page[512];       // 8 KB: a gather row without a source reads zeros at any channel offset (C <= 4096)
+// 16 KB: a gather row without a source reads zeros at any channel offset (C <= 8192: the input gradient of the first
+// level's sub-pixel convolution at config 3 reduces over 4 x 1536 channels per tap)
+__device__ uint4 g_zero_page[1024];
 
 __device__ __forceinline__ void glds16(const void* src, unsigned char* lds_wave_base) {
     // LDS destination = wave-uniform base + lane * 16 ; the global source address is per lane
@@ -462,6 +464,22 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
             const unsigned op = tabo[row];
             if (op == 0xffffffffu) continue;
             ooff = (int64_t)op * p.out_ld + col;
+        } else if (p.d2s_c) {
+            // depth-to-space store (image-major forward gathers only): this 16-byte segment lies inside one sub-pixel
+            int b, ho, wo;
+            if (p.pow2) {
+                wo = m & (g.Wo - 1);
+                const int t2 = m >> p.wq_shift;
+                ho = t2 & (g.Ho - 1);
+                b = t2 >> p.hq_shift;
+            } else {
+                const int t2 = m / g.Wo;
+                wo = m - t2 * g.Wo;
+                b = t2 / g.Ho;
+                ho = t2 - b * g.Ho;
+            }
+            const int sub = col / p.d2s_c, c = col - sub * p.d2s_c;
+            ooff = (((int64_t)b * (2 * g.Ho) + 2 * ho + (sub >> 1)) * (2 * g.Wo) + 2 * wo + (sub & 1)) * p.d2s_c + c;
         } else {
             ooff = (int64_t)m * p.out_ld + col;
         }
@@ -628,7 +646,11 @@ __device__ __forceinline__ void nn16h_epilogue(const NN16Params& p, const NHTile
             f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(est + row * ELD + cc * 8 + 4);
             const bool live = gy < g.Hq && gx < g.Wq && col < p.N && oy < g.Ho && ox < g.Wo;
             if (live) {
-                const int64_t ooff = ((int64_t)(b * g.Ho + oy) * g.Wo + ox) * p.out_ld + col;
+                int64_t ooff = ((int64_t)(b * g.Ho + oy) * g.Wo + ox) * p.out_ld + col;
+                if (THIN == 0 && p.d2s_c) {             // depth-to-space store: the segment lies inside one sub-pixel
+                    const int sub = col / p.d2s_c, c = col - sub * p.d2s_c;
+                    ooff = (((int64_t)b * (2 * g.Ho) + 2 * oy + (sub >> 1)) * (2 * g.Wo) + 2 * ox + (sub & 1)) * p.d2s_c + c;
+                }
                 if (p.bias) {
                     v0 += *reinterpret_cast<const f32x4_t*>(p.bias + col);
                     v1 += *reinterpret_cast<const f32x4_t*>(p.bias + col + 4);
@@ -1641,6 +1663,17 @@ static int launch_nn16h(NN16Params& p, int mode, int ntaps, hipStream_t s) {
     return BG_OK;
 }
 
+bool nn16_d2s_ok(const NN16Params& p, int mode, int zdim) {
+    const Gather& g = p.g;
+    if (p.d2s_c <= 0 || p.d2s_c % 8 || p.N != 4 * p.d2s_c || p.C % 8 || mode != GATHER_CONV || zdim != 1 || g.stride != 1 ||
+        g.pstep != 1 || g.Hq != g.Ho || g.Wq != g.Wo || p.stats_part || p.ring)
+        return false;
+    if ((int64_t)g.Nb * g.Ho * g.Wo * 4 >= (int64_t(1) << 31)) return false;
+    if (nn16h_taps(p, mode, zdim)) return true;
+    if (nn16_posmajor_fraction(p, mode) < 1.0) return false;
+    return plan_nn16(p, mode, zdim, true).splitk == 1;     // (the plan the unfused launch of the same shape would take)
+}
+
 int64_t nn16_stats_rows(const NN16Params& p, int mode, int zdim) {
     if (p.C % 8 || p.N % 8 || !nn16h_taps(p, mode, zdim)) return 0;
     return 2 * (int64_t)p.g.Nb * (p.g.Hq / NH_T) * (p.g.Wq / NH_T) * (p.g.pstep * p.g.pstep);     // one per half patch
@@ -1652,10 +1685,12 @@ int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, 
     BG_REQUIRE((reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.B) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(p.out) & 15) == 0,
                "bf16-resident conv: tensors must be 16-byte aligned");
-    BG_REQUIRE(p.g.k >= 1 && p.g.k <= NN16_TAPS && p.C <= 4096 && p.g.stride >= 1 && p.g.stride <= 2,
+    BG_REQUIRE(p.g.k >= 1 && p.g.k <= NN16_TAPS && p.C <= 8192 && p.g.stride >= 1 && p.g.stride <= 2,
                "bf16-resident conv: kernel size %d / stride %d / %d channels not supported", p.g.k, p.g.stride, p.C);
     BG_REQUIRE((int64_t)p.g.Nb * p.g.Hs * p.g.Ws < (int64_t(1) << 30) && (int64_t)p.g.Nb * p.g.Ho * p.g.Wo < (int64_t(1) << 31),
                "bf16-resident conv: more than 2^30 source / 2^31 output pixels");
+    BG_REQUIRE(p.d2s_c == 0 || (nn16_d2s_ok(p, mode, zdim) && ws == nullptr),
+               "bf16-resident conv: this launch has no depth-to-space store (bg_conv2d_fwd_d2s_supported)");
     if (const int ntaps = nn16h_taps(p, mode, zdim)) return launch_nn16h(p, mode, ntaps, s);
     BG_REQUIRE(p.stats_part == nullptr, "bf16-resident conv: fused statistics need the halo-tile form (nn16_stats_rows)");
     NN16Plan pl = plan_nn16(p, mode, zdim, ws != nullptr);

@@ -509,6 +509,81 @@ class Conv2dFn(Function):
         return dx, dw, db, None, None, None, None, None, None, (dy if ctx.acc else None)
 
 
+def _shuffle_ok(t, C):
+    """bg_depth_to_space / bg_space_to_depth move 16-byte pieces: C % 8 == 0 for bf16, C % 4 == 0 for fp32."""
+    return C % (8 if t.dtype == BF16 else 4) == 0
+
+
+def depth_to_space(x, r=2):
+    """tf.nn.depth_to_space (ops.py:27), NHWC: [N,H,W,r*r*C] -> [N,r*H,r*W,C] (bg_depth_to_space; a pure permutation)."""
+    x = _c(x)
+    N, H, W_, C4 = x.shape
+    C = C4 // (r * r)
+    assert C * r * r == C4, (x.shape, r)
+    if not _shuffle_ok(x, C):
+        raise NotImplementedError("depth_to_space: %d channels of %s are not a multiple of 16 bytes" % (C, x.dtype))
+    y = torch.empty((N, H * r, W_ * r, C), dtype=x.dtype, device=x.device)
+    check(lib().bg_depth_to_space(act(x), act(y), dt(x), N, H, W_, C, r, stream()))
+    return y
+
+
+def space_to_depth(y, r=2):
+    """The inverse (and adjoint) of depth_to_space: [N,r*H,r*W,C] -> [N,H,W,r*r*C] (bg_space_to_depth)."""
+    y = _c(y)
+    N, Hr, Wr, C = y.shape
+    assert Hr % r == 0 and Wr % r == 0, (y.shape, r)
+    if not _shuffle_ok(y, C):
+        raise NotImplementedError("space_to_depth: %d channels of %s are not a multiple of 16 bytes" % (C, y.dtype))
+    x = torch.empty((N, Hr // r, Wr // r, r * r * C), dtype=y.dtype, device=y.device)
+    check(lib().bg_space_to_depth(act(y), act(x), dt(y), N, Hr // r, Wr // r, C, r, stream()))
+    return x
+
+
+def _fuse_d2s():
+    return os.environ.get("BG_FUSE_D2S", "1") != "0"           # A/B switch: =0 forces conv + bg_depth_to_space
+
+
+class SubpixelConvFn(Function):
+    """subpixel_conv (ops.py:23-27): a stride-1 convolution to r*r*C channels followed by tf.nn.depth_to_space(r); w is
+    [k,k,Cin,r*r*C], the result [N,r*H,r*W,C].
+
+    Forward: where the bf16-resident launch has the fused store (bg_conv2d_fwd_d2s_supported) the convolution writes the
+    shuffled tensor itself and [N,H,W,r*r*C] is never materialised; everywhere else (fp32 tensors, bf16-staged, split-K
+    launches of the small maps, BG_FUSE_D2S=0) it is Conv2dFn's launch followed by bg_depth_to_space.  Both give the same
+    bits.  Backward: dy goes through bg_space_to_depth into [N,H,W,r*r*C] and from there through Conv2dFn's input,
+    weight and bias gradients."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, pad_lo, pad_mode, r=2, out_dtype=None):
+        N, H, W_, Cin = x.shape
+        k, _, cin2, C4 = w.shape
+        assert cin2 == Cin and C4 % (r * r) == 0, (x.shape, w.shape, r)
+        C = C4 // (r * r)
+        ctx.r = r
+        L = lib()
+        if _fuse_d2s() and r == 2 and out_dtype is None and _resident_ok(x, Cin, C4) and C % 8 == 0:
+            d = hip.conv_desc(N, H, W_, Cin, H, W_, C4, k, 1, pad_lo, pad_mode, hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
+            if L.bg_conv2d_fwd_d2s_supported(d, r):
+                ctx.fork = getattr(x, "bg_fork", None)
+                x = _c(x)
+                ctx.resident, ctx.in_dtype, ctx.pad8, ctx.acc, ctx.rgb = True, x.dtype, None, False, False
+                y = torch.empty((N, H * r, W_ * r, C), dtype=BF16, device=x.device)
+                check(L.bg_conv2d_fwd_d2s(d, act(x), act(weight_packs(w)[1]), f32(bias), None, act(y), r, None, 0,
+                                          stream()))
+                ctx.desc = d
+                ctx.x, ctx.w, ctx.bias = x, w, bias
+                return y
+        if out_dtype is None and x.dtype == BF16 and _resident_ok(x, Cin, C4) and C % 8:
+            out_dtype = torch.float32          # (a bf16 run of C channels off the 16-byte grid: shuffled as fp32)
+        y4 = Conv2dFn.forward(ctx, x, w, bias, 1, pad_lo, H, W_, pad_mode, out_dtype, None)
+        return depth_to_space(y4, r)
+
+    @staticmethod
+    def backward(ctx, dy):
+        g = Conv2dFn.backward(ctx, space_to_depth(dy, ctx.r))
+        return g[0], g[1], g[2], None, None, None, None
+
+
 class Deconv2dFn(Function):
     """tf.nn.conv2d_transpose(SAME)+bias_add (ops.py:127-132); w is [k,k,Cout,Cin]."""
 

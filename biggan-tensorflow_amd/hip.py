@@ -12,7 +12,7 @@ import torch
 
 _LIB = None
 LIB_NAME = "libbiggan_hip.so"
-ABI_VERSION = 6
+ABI_VERSION = 7
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 PAD_REFLECT, PAD_ZERO = 0, 1
@@ -91,6 +91,8 @@ SIGNATURES = {
     "bg_png_unfilter": (c_int, [c_char_p, c_int, c_int, c_int, _P]),
     "bg_conv2d_fwd_workspace_bytes": (c_size_t, [_CD]),
     "bg_conv2d_fwd": (c_int, [_CD, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "bg_conv2d_fwd_d2s_supported": (c_int, [_CD, c_int]),
+    "bg_conv2d_fwd_d2s": (c_int, [_CD, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_conv2d_dgrad_workspace_bytes": (c_size_t, [_CD]),
     "bg_conv2d_dgrad": (c_int, [_CD, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_conv2d_wgrad_workspace_bytes": (c_size_t, [_CD]),
@@ -198,6 +200,8 @@ SIGNATURES = {
     "bg_gram16_workspace_bytes": (c_size_t, [c_int, c_int]),
     "bg_gram16": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "bg_cast": (c_int, [_P, c_int, _P, c_int, c_int64, _P]),
+    "bg_depth_to_space": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "bg_space_to_depth": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "bg_pad_channels": (c_int, [_P, c_int, _P, c_int, c_int64, c_int, c_int, c_int64, c_int, _P]),
     "bg_weight_pack": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "bg_bn_stats_t": (c_int, [_P, c_int, _P, c_int64, c_int, _P]),

@@ -130,7 +130,43 @@ def _regularize(w, regularizer):
 # Layer
 ##################################################################################
 def subpixel_conv(x, channels, opt, kernel=3, scale=2, use_bias=True, scope='subpixel_conv_0'):
-    raise NotImplementedError("subpixel_conv (ops.py:23) is outside the default hot path")
+    """ops.py:23-27: conv(x, channels * scale**2, kernel, stride=1, pad=(kernel-1)/2.0, scope=scope), then
+    tf.nn.depth_to_space(scale): out[n, h*r+i, w*r+j, c] = conv[n, h, w, (i*r+j)*channels + c].  The float pad goes
+    through conv's split (ops.py:68-76: pad*2, int(pad//2) low, the rest high): kernel 3 pads 1 / 1, kernel 2 pads 0 low and
+    1 high - under 'reflect' and under 'zero' (TF 'SAME') alike - so the map size is kept.  Variables as conv creates them
+    under ``scope``: kernel [k,k,Cin,channels*scale**2] (one spectral norm over the whole matrix, the generator's conv
+    regulariser), u, bias when ``use_bias``.  One functional.SubpixelConvFn: where the bf16-resident convolution can store
+    depth-to-space itself the wide tensor is never written."""
+    if _is_dual(x):
+        raise NotImplementedError("subpixel_conv has no tangent pass (the generator only)")
+    r = int(scale)
+    c4 = channels * r * r
+    with variable_scope(scope) as full_scope:
+        N, H, W, Cin = x.shape
+        pad = (kernel - 1) / 2.0
+        pad_mode, pad_lo, pad_hi = hip.PAD_REFLECT, 0, 0
+        if pad > 0:
+            pad_type = opt.get("conv", {}).get("padding_type", 'reflect')
+            tot = pad * 2                                # ops.py:68-71 (stride 1: H % stride == 0)
+            pad_lo = int(tot // 2)
+            pad_hi = int(tot - pad_lo)
+            if pad_type == 'zero':                       # TF 'SAME': total k - 1, floor low / ceil high - the same split
+                pad_mode = hip.PAD_ZERO
+            elif pad_type != 'reflect':
+                raise ValueError("Unsupported padding type: " + str(pad_type))
+        if pad_lo + pad_hi != kernel - 1:
+            raise NotImplementedError("subpixel_conv: kernel %d does not keep the map size" % kernel)
+        sn = opt.get("conv", {}).get("sn", True)
+        reg = opt.get("conv", {}).get("regularizer", None) if 'generator' in full_scope else None
+        w = get_variable("kernel", shape=[kernel, kernel, Cin, c4], initializer=weight_init, regularizer=reg)
+        _regularize(w, reg)
+        wk = spectral_norm(w, _shape_only=_is_meta(x)) if sn else w
+        bias = get_variable("bias", [c4], initializer=S.constant_initializer(0.0)) if use_bias else None
+        if _is_meta(x):
+            return _meta((N, H * r, W * r, channels))
+        if pad_mode == hip.PAD_REFLECT and max(pad_lo, pad_hi) > min(H, W) - 1:
+            raise ValueError("tf.pad REFLECT: padding %d does not fit a %dx%d map" % (max(pad_lo, pad_hi), H, W))
+        return _resident_out(Fn.SubpixelConvFn.apply(x, wk, bias, pad_lo, pad_mode, r))
 
 
 def decode_kernel_sizes(str):
@@ -369,8 +405,12 @@ def upconv(x, channels, opt, use_bias=True, _accumulate_into=None, _stats=False)
     elif m == 'nn':
         y = up_sample(x, 2)
         return y if _accumulate_into is None else _add(y, _accumulate_into)
-    elif m in ('subpixel2', 'subpixel3'):
-        raise NotImplementedError("upsampling_method %s is outside the default hot path" % m)
+    elif m == 'subpixel2':
+        y = subpixel_conv(x, channels, kernel=2, scale=2, use_bias=use_bias, opt=opt)
+        return y if _accumulate_into is None else _add(y, _accumulate_into)
+    elif m == 'subpixel3':
+        y = subpixel_conv(x, channels, kernel=3, scale=2, use_bias=use_bias, opt=opt)
+        return y if _accumulate_into is None else _add(y, _accumulate_into)
     else:
         raise ValueError("Invalid upsampling method specified: " + str(m))
 
@@ -492,9 +532,30 @@ def downconv(x, channels, opt, use_bias=True, method=None):
     elif method == 'max_pool_only':
         return max_pooling(x)
     elif method == 'resize_conv35':
-        raise NotImplementedError("downsampling_method %s (mixed kernels) is outside the default hot path" % method)
+        channels5 = int(channels * 0.333333333334)       # ops.py:281-285
+        channels3 = channels - channels5
+        x = _conv35(x, channels3, channels5, use_bias, opt)
+        return avg_pooling(x)
     else:
         raise ValueError("Invalid downsampling method specified: " + str(method))
+
+
+def _conv35(x, channels3, channels5, use_bias, opt):
+    """conv(x, kernel="<c3>x3,<c5>x5", stride=1, pad=1) of resize_conv35: per ops.py:52-59 each slice is its own conv with
+    its own pad (k-1)//2 and its own kernel / u / bias under conv_0/conv<k>_slice, concatenated along the channels.  One
+    multi-branch launch (_mixconv) where it takes the layer; where it cannot - an input whose channels are off the 8-grid
+    in bf16-resident mode (D's first block, Cin = c_dim: the image) - one conv per slice and the concat: the same
+    variables and the same values.  Those two run as 'bf16-staged' (fp32 tensors, bf16 MFMA operands, like the gradient
+    penalty of a bf16-resident model): the bf16-resident kernels stop at 4 taps per axis.  Under the gradient-penalty
+    gan_types (a Dual input) _mixconv raises: there is no tangent pass."""
+    kernel = "%dx3,%dx5" % (channels3, channels5)
+    if _is_meta(x) or _is_dual(x) or not (Fn.Precision.resident and x.shape[-1] % 8):
+        return conv(x, channels3 + channels5, kernel=kernel, stride=1, pad=1, use_bias=use_bias, opt=opt)
+    x3, x5 = _fork(_to(x, torch.float32))
+    with variable_scope('conv_0'), Fn.precision_scope("bf16-staged"):
+        y3 = conv(x3, channels3, kernel=3, stride=1, pad=1, use_bias=use_bias, opt=opt, scope='conv3_slice')
+        y5 = conv(x5, channels5, kernel=5, stride=1, pad=2, use_bias=use_bias, opt=opt, scope='conv5_slice')
+    return _channel_concat(y3, y5)
 
 
 def resblock_down(x_init, channels, opt, use_bias=True, scope='resblock_down'):

@@ -13,7 +13,10 @@
  *   - tensors are NHWC fp32, conv kernels HWIO [k,k,Cin,Cout], transposed-conv kernels
  *     [k,k,Cout,Cin] (the reference's variable layouts, ops.py:88,127);
  *   - return value 0 = success; non-zero = error, message in bg_last_error() (thread-local);
- *   - scratch memory is passed in by the caller, sized by the matching *_workspace_bytes().
+ *   - scratch memory is passed in by the caller, sized by the matching *_workspace_bytes();
+ *   - sub-pixel up-sampling (ops.py:23-27 subpixel_conv = conv to r*r*C channels + tf.nn.depth_to_space) is
+ *     bg_depth_to_space / bg_space_to_depth, and bg_conv2d_fwd_d2s where the bf16-resident convolution can store
+ *     its output at the shuffled address itself.
  */
 #ifndef BIGGAN_HIP_H
 #define BIGGAN_HIP_H
@@ -25,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 6
+#define BG_ABI_VERSION 7
 
 enum { BG_OK = 0, BG_ERR_ARG = 1, BG_ERR_LAUNCH = 2, BG_ERR_UNSUPPORTED = 3 };
 enum { BG_PAD_REFLECT = 0, BG_PAD_ZERO = 1 };
@@ -85,6 +88,18 @@ size_t bg_conv2d_fwd_workspace_bytes(const BgConvDesc*);
 int bg_conv2d_fwd  (const BgConvDesc*, const void* x, const void* w, const float* bias,
                     const float* alpha_dev, void* y, int accumulate,
                     void* ws, size_t ws_bytes, void* stream);
+/* The same convolution with tf.nn.depth_to_space(block) of its output fused into the store (ops.py:23-27
+ * subpixel_conv): d describes the convolution (Cout = block * block * C, stride 1, Ho x Wo = H x W) and y is the shuffled
+ * tensor [N, block * Ho, block * Wo, C]: y[n, h * block + i, w * block + j, c] = conv[n, h, w, (i * block + j) * C + c].
+ * The epilogue writes each 16-byte row segment (8 channels, C % 8 == 0: a segment never straddles a sub-pixel) at its
+ * shuffled address, so [N, Ho, Wo, Cout] is never materialised; the accumulators are those of bg_conv2d_fwd, so the
+ * result is bit-identical to bg_conv2d_fwd + bg_depth_to_space.  bg_conv2d_fwd_d2s_supported returns 1 for the launches
+ * whose kernel form has the fused store (bf16-resident, block = 2: the halo-tile form, and the tap kernel without
+ * split-K and without position-major rows); elsewhere callers run the pair.  No workspace: supported launches never
+ * split K. */
+int bg_conv2d_fwd_d2s_supported(const BgConvDesc*, int block);
+int bg_conv2d_fwd_d2s(const BgConvDesc*, const void* x, const void* w, const float* bias, const float* alpha_dev,
+                      void* y, int block, void* ws, size_t ws_bytes, void* stream);
 /* gradient of the above w.r.t. x (reflect padding folded back)      autodiff of ops.py:82,94
  *   dy has d->y_dtype, dx has d->x_dtype */
 size_t bg_conv2d_dgrad_workspace_bytes(const BgConvDesc*);
@@ -482,6 +497,13 @@ int bg_alpha_mask_tangent(const float* x, const float* xdot, float* ydot, int64_
  * fp32 entry points of the same name.
  * ------------------------------------------------------------------------------------------ */
 int bg_cast(const void* x, int x_dtype, void* y, int y_dtype, int64_t n, void* stream);
+/* tf.nn.depth_to_space (ops.py:27) and its inverse / adjoint, NHWC, block size r (csrc/subpixel.hip):
+ *   bg_depth_to_space: x[N,H,W,r*r*C] -> y[N,r*H,r*W,C],  y[n, h*r+i, w*r+j, c] = x[n, h, w, (i*r+j)*C + c]
+ *   bg_space_to_depth: x[N,r*H,r*W,C] -> y[N,H,W,r*r*C]   (H, W: the LOW-resolution map in both calls)
+ * Pure permutations of BG_F32 or BG_BF16 tensors (bit-exact); C * element size must be a multiple of 16 bytes
+ * (C % 8 == 0 for bf16, C % 4 == 0 for fp32): a run of C channels stays contiguous and moves in 16-byte pieces. */
+int bg_depth_to_space(const void* x, void* y, int dtype, int N, int H, int W, int C, int r, void* stream);
+int bg_space_to_depth(const void* x, void* y, int dtype, int N, int H, int W, int C, int r, void* stream);
 /* Widen or narrow the middle dimension of an [outer][C][inner] view from Cs to Cd entries, converting between fp32 and
  * bf16: the 3-channel image layers (ops.py:49 with Cin = 3, BigGAN.py:570 with Cout = 3) run on the bf16-resident GEMMs
  * with the thin side widened to 8 channels.  mode BG_PAD_ZERO_FILL (0): dst[c] = c < Cs ? src[c] : 0;
