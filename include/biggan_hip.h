@@ -493,8 +493,13 @@ int bg_alpha_mask_tangent(const float* x, const float* xdot, float* ydot, int64_
  * bf16-resident data path (BASELINE configs 3-5): "_t" forms of the bandwidth-bound kernels above.  Activation
  * tensors are fp32 or bf16 in HBM (dtype arguments: BG_F32 / BG_BF16), arithmetic is fp32 in registers, parameters,
  * statistics and reductions stay fp32 / fp64.  x_dtype names the op's INPUT-side tensors (x, dx), y_dtype its
- * OUTPUT-side tensors (y, dy).  C % 4 == 0 (8-byte bf16 accesses).  Same formulas and reference call sites as the
- * fp32 entry points of the same name.
+ * OUTPUT-side tensors (y, dy).  Any C > 0: with C % 8 == 0 and every activation pointer on a 16-byte boundary the
+ * all-bf16 calls move 16 bytes per access; with C % 4 == 0 a bf16 tensor needs 8-byte alignment only (8-byte
+ * accesses) - except column reductions (statistics, backward reduce, dalpha, bias gradient) over 16 Mi elements or
+ * more, which read 16 bytes at C % 8 == 0 and need 16-byte alignment; any other C (the image layers' 3 and 6) goes one
+ * element per thread.  fp32 tensors: 16-byte aligned when C % 4 == 0.  bg_lincomb_t / bg_dot_t: n % 4 == 0, bf16
+ * tensors 8-byte aligned.  Same formulas and reference call sites as the fp32 entry points of the same name;
+ * tests/test_gpu_elementwise16.py holds every one of these forms to a float64 reference.
  * ------------------------------------------------------------------------------------------ */
 int bg_cast(const void* x, int x_dtype, void* y, int y_dtype, int64_t n, void* stream);
 /* tf.nn.depth_to_space (ops.py:27) and its inverse / adjoint, NHWC, block size r (csrc/subpixel.hip):
