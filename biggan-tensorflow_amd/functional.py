@@ -1625,24 +1625,202 @@ class AvgPool2Fn(Function):
 
 
 class UpSample2Fn(Function):
-    """tf.image.resize_nearest_neighbor to twice the size (ops.py:516-519)."""
+    """tf.image.resize_nearest_neighbor to twice the size (ops.py:516-519).  fp32 tensors take the box kernels; a bf16
+    tensor stays bf16 (recon.hip): the copy is exact and the backward's 2x2 sum is rounded once."""
 
     @staticmethod
     def forward(ctx, x):
         x = _c(x)
         N, H, W_, C = x.shape
-        y = torch.empty((N, 2 * H, 2 * W_, C), dtype=torch.float32, device=x.device)
-        check(lib().bg_box2_up(f32(x), f32(y), N, H, W_, C, 1.0, stream()))
+        y = torch.empty((N, 2 * H, 2 * W_, C), dtype=x.dtype, device=x.device)
+        if x.dtype == torch.float32:
+            check(lib().bg_box2_up(f32(x), f32(y), N, H, W_, C, 1.0, stream()))
+        else:
+            check(lib().bg_upsample2_fwd_t(act(x), act(y), dt(x), N, H, W_, C, stream()))
         ctx.shape = (N, H, W_, C)
+        ctx.xdt = x.dtype
         return y
 
     @staticmethod
     def backward(ctx, dy):
         dy = _c(dy)
         N, H, W_, C = ctx.shape
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
-        check(lib().bg_box2_down(f32(dy), f32(dx), N, 2 * H, 2 * W_, C, 1.0, stream()))
+        dx = torch.empty(ctx.shape, dtype=ctx.xdt, device=dy.device)
+        if ctx.xdt == torch.float32:
+            check(lib().bg_box2_down(f32(cast(dy, torch.float32)), f32(dx), N, 2 * H, 2 * W_, C, 1.0, stream()))
+        else:
+            dy = cast(dy, ctx.xdt)
+            check(lib().bg_upsample2_bwd_t(act(dy), act(dx), dt(dx), N, H, W_, C, stream()))
         return dx
+
+
+# ------------------------------------------------------------------------------------------
+# discriminator reconstruction heads (recon.hip): gated linear unit, crop at a device-resident offset, L2-norm loss
+# ------------------------------------------------------------------------------------------
+class GluFn(Function):
+    """ops.py:842-845 on [..., 2C]: x[..., :C] * sigmoid(x[..., C:]), fp32 or bf16."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x)
+        if x.shape[-1] % 2:
+            raise ValueError("glu: the channel count %d is odd" % x.shape[-1])
+        C = x.shape[-1] // 2
+        y = torch.empty(tuple(x.shape[:-1]) + (C,), dtype=x.dtype, device=x.device)
+        check(lib().bg_glu_fwd(act(x), act(y), dt(x), x.numel() // (2 * C), C, stream()))
+        ctx.x = x
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x = ctx.x
+        dy = cast(_c(dy), x.dtype)
+        C = x.shape[-1] // 2
+        dx = torch.empty_like(x)
+        check(lib().bg_glu_bwd(act(x), act(dy), act(dx), dt(x), x.numel() // (2 * C), C, stream()))
+        ctx.x = None
+        return dx
+
+
+class BnGluFn(Function):
+    """Training-mode batch norm (ops.py:580-585) on [N,H,W,2C] fused with the GLU that follows (ops.py:842-845): the
+    statistics as in BnActFn (fp64 sums, cross-replica through ``reduce_fn``, moving statistics updated), then ONE pass
+    that reads x once and writes y [N,H,W,C].  Backward in BnActFn's reduce / finalize / dx split, the GLU's backward
+    recomputed inside the two passes (bg_bn_glu_*)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, moving_mean, moving_var, momentum, eps, unbiased_mv, reduce_fn, world):
+        x = _c(x)
+        N, H, W_, C2 = x.shape
+        C = C2 // 2
+        rows = N * H * W_
+        L = lib()
+        dev = x.device
+        mean = torch.empty(C2, dtype=torch.float32, device=dev)
+        rstd = torch.empty(C2, dtype=torch.float32, device=dev)
+        count = float(rows * world)
+        sums = zeros(2 * C2, torch.float64, dev)
+        if x.dtype == torch.float32:
+            check(L.bg_bn_stats(f32(x), hip.ptr(sums), rows, C2, stream()))
+        else:
+            check(L.bg_bn_stats_t(act(x), dt(x), hip.ptr(sums), rows, C2, stream()))
+        if reduce_fn is not None:
+            reduce_fn(sums)
+        check(L.bg_bn_finalize(hip.ptr(sums), count, eps, momentum, int(unbiased_mv), f32(mean), f32(rstd),
+                               f32(moving_mean), f32(moving_var), C2, stream()))
+        y = torch.empty((N, H, W_, C), dtype=x.dtype, device=dev)
+        gamma_c, beta_c = _c(gamma), _c(beta)
+        check(L.bg_bn_glu_fwd(act(x), f32(mean), f32(rstd), f32(gamma_c), f32(beta_c), act(y), dt(x), rows, C, stream()))
+        ctx.x, ctx.mean, ctx.rstd = x, mean, rstd
+        ctx.gamma, ctx.beta, ctx.gamma_c, ctx.beta_c = gamma, beta, gamma_c, beta_c
+        ctx.count, ctx.reduce_fn = count, reduce_fn
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd = ctx.x, ctx.mean, ctx.rstd
+        dy = cast(_c(dy), x.dtype)
+        N, H, W_, C2 = x.shape
+        C = C2 // 2
+        rows = N * H * W_
+        L = lib()
+        dev = x.device
+        tiles = (C + 255) // 256
+        nseg = max(1, min((rows + 63) // 64, (1024 + tiles - 1) // tiles))       # ~4 blocks per CU, >= 64 rows each
+        part = torch.empty((3, nseg, C2), dtype=torch.float32, device=dev)
+        part[2].zero_()                 # (the dalpha plane bg_bn_bwd_finalize sums: there is no activation slope here)
+        check(L.bg_bn_glu_bwd_reduce(act(x), act(dy), f32(mean), f32(rstd), f32(ctx.gamma_c), f32(ctx.beta_c), f32(part),
+                                     dt(x), rows, C, nseg, stream()))
+        dgamma = torch.empty(C2, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(C2, dtype=torch.float32, device=dev)
+        cm = torch.empty(2 * C2, dtype=torch.float32, device=dev)
+        check(L.bg_bn_bwd_finalize(f32(part), f32(ctx.gamma_c), 0, ctx.count, f32(dgamma), f32(dbeta), None, f32(cm), nseg,
+                                   C2, stream()))
+        if ctx.reduce_fn is not None:
+            ctx.reduce_fn(cm)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            check(L.bg_bn_glu_bwd_dx(act(x), act(dy), f32(mean), f32(rstd), f32(ctx.gamma_c), f32(ctx.beta_c), f32(cm),
+                                     act(dx), dt(x), rows, C, stream()))
+
+        def deliver(t, needed, g):
+            if not needed:
+                return None
+            if is_variable(t):
+                emit_grad(t, lambda out: out.copy_(g))
+                return None
+            return g
+        dg = deliver(ctx.gamma, ctx.needs_input_grad[1], dgamma)
+        db = deliver(ctx.beta, ctx.needs_input_grad[2], dbeta)
+        ctx.x = None
+        return dx, dg, db, None, None, None, None, None, None, None
+
+
+class CropAtFn(Function):
+    """x[N, oy:oy+p, ox:ox+p, C] with (oy, ox) = (off_y[0], off_x[0]) read on the device (BigGAN.py:657; one offset for
+    the whole batch): nothing of the draw reaches the host, so a captured graph replays with fresh draws."""
+
+    @staticmethod
+    def forward(ctx, x, off_y, off_x, p):
+        x = _c(x)
+        N, H, W_, C = x.shape
+        y = torch.empty((N, p, p, C), dtype=x.dtype, device=x.device)
+        check(lib().bg_crop_at_fwd(act(x), act(y), dt(x), i32(off_y), i32(off_x), N, H, W_, p, C, stream()))
+        ctx.shape, ctx.xdt, ctx.off, ctx.p = (N, H, W_, C), x.dtype, (off_y, off_x), p
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = cast(_c(dy), ctx.xdt)
+        N, H, W_, C = ctx.shape
+        dx = torch.empty(ctx.shape, dtype=ctx.xdt, device=dy.device)
+        check(lib().bg_crop_at_bwd(act(dy), act(dx), dt(dx), i32(ctx.off[0]), i32(ctx.off[1]), N, H, W_, ctx.p, C,
+                                   stream()))
+        return dx, None, None, None
+
+
+RECON_IDENTITY, RECON_HALFRES, RECON_CROP = 0, 1, 2
+
+
+class ReconLossFn(Function):
+    """BigGAN.py:815-817 / 830-833: ||tanh(y) - target||_2 / numel * 1000 * ld over the whole batch tensor, from the
+    pre-tanh head output y [N,h,w,C] (fp32) and the fp32 image batch [N,S,S,C]; ``mode`` picks the target (the image, its
+    2x2 average, its crop at offset * f).  -> (loss [1], tanh(y)); the image is not differentiable (sample grids).
+    Under data parallelism the sum of squares is all-reduced before the square root and numel is the global count, so
+    a run at world size N is the arithmetic of one GPU at the global batch."""
+
+    @staticmethod
+    def forward(ctx, y, target, off_y, off_x, mode, f, ld, reduce_fn, world):
+        y, target = _c(y), _c(target)
+        N, h, w, C = y.shape
+        S = target.shape[1]
+        if target.shape[0] != N or target.shape[2] != S or target.shape[3] != C:
+            raise ValueError("recon loss: head output %s against images %s" % (tuple(y.shape), tuple(target.shape)))
+        L = lib()
+        ssq = zeros(1, torch.float64, y.device)
+        img = torch.empty_like(y)
+        check(L.bg_recon_loss_sums(f32(y), f32(target), f32(img), i32(off_y), i32(off_x), mode, f, hip.ptr(ssq), N, h, w,
+                                   S, C, stream()))
+        if reduce_fn is not None:
+            reduce_fn(ssq)
+        scale = 1000.0 * float(ld) / float(y.numel() * world)
+        loss = torch.empty(1, dtype=torch.float32, device=y.device)
+        check(L.bg_recon_loss_finalize(hip.ptr(ssq), scale, f32(loss), stream()))
+        ctx.saved = (y, target, off_y, off_x, ssq)
+        ctx.geom = (mode, f, scale, N, h, w, S, C)
+        ctx.mark_non_differentiable(img)
+        return loss, img
+
+    @staticmethod
+    def backward(ctx, g, _gimg):
+        y, target, off_y, off_x, ssq = ctx.saved
+        mode, f, scale, N, h, w, S, C = ctx.geom
+        dy = torch.empty_like(y)
+        check(lib().bg_recon_loss_bwd(f32(y), f32(target), i32(off_y), i32(off_x), mode, f, hip.ptr(ssq), scale,
+                                      f32(_c(g).reshape(-1)[:1]), f32(dy), N, h, w, S, C, stream()))
+        ctx.saved = None
+        return dy, None, None, None, None, None, None, None, None
 
 
 class SumPoolFn(Function):

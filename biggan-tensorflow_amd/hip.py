@@ -12,7 +12,7 @@ import torch
 
 _LIB = None
 LIB_NAME = "libbiggan_hip.so"
-ABI_VERSION = 7
+ABI_VERSION = 8
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 PAD_REFLECT, PAD_ZERO = 0, 1
@@ -219,6 +219,19 @@ SIGNATURES = {
     "bg_sum_pool_bwd_t": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "bg_lincomb_t": (c_int, [_P, _P, c_float, _P, c_float, _P, c_int, c_int64, _P]),
     "bg_dot_t": (c_int, [_P, _P, c_int, _P, c_int64, _P]),
+    "bg_bn_glu_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, _P]),
+    "bg_bn_glu_bwd_reduce": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, _P]),
+    "bg_bn_glu_bwd_dx": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, _P]),
+    "bg_glu_fwd": (c_int, [_P, _P, c_int, c_int64, c_int, _P]),
+    "bg_glu_bwd": (c_int, [_P, _P, _P, c_int, c_int64, c_int, _P]),
+    "bg_upsample2_fwd_t": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "bg_upsample2_bwd_t": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "bg_crop_at_fwd": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "bg_crop_at_bwd": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "bg_recon_loss_sums": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "bg_recon_loss_finalize": (c_int, [_P, c_double, _P, _P]),
+    "bg_recon_loss_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_double, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                  _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

@@ -4,9 +4,8 @@ eagerly on one MI355X per process.  One training iteration = D step then G step
 (BigGAN.py:1061-1084); each step is one "run" with its own z, DiffAugment draws and one spectral-norm
 power iteration per weight.
 
-Out-of-scope reference features (alternative heads, reconstruction heads, label
-embeddings, mixed-kernel blocks) are accepted as flags and rejected here with
-NotImplementedError.
+Out-of-scope reference features (alternative heads, the z-reconstruction head, d_final_conv)
+are accepted as flags and rejected here with NotImplementedError.
 """
 import copy
 import os
@@ -22,7 +21,7 @@ from . import hip
 from .ops import (fully_connected, resblock_up_condition, resblock_down, resblock, self_attention_2, conv, bn,
                   resblock_up_cond_deep, resblock_down_deep, upconv, g_conv, cond_bn, mixed_resblock,
                   prelu, relu, lrelu, tanh, alpha_helper_tanh, alpha_mask, global_sum_pooling, discriminator_loss,
-                  generator_loss)
+                  generator_loss, glu, up_sample)
 from .DiffAugment import DiffAugment, draw as draw_augment
 from .utils import orthogonal_regularizer, orthogonal_regularizer_fc, l2_regularizer, round_up, cls_loss_fn
 
@@ -70,9 +69,7 @@ class BigGAN(GANBase):
             # (the reference accepts it and only re-splits z: no labels, no embedding; rejected as a likely mistake)
             ("cls_embedding without n_labels", args.cls_embedding and args.n_labels <= 0),
             ("g_final_layer", args.g_final_layer), ("multi_head", args.multi_head),
-            ("z_reconstruct", args.z_reconstruct), ("d_reconstruction", args.d_reconstruction),
-            ("d_reconstruction_halfres", args.d_reconstruction_halfres),
-            ("d_reconstruction_texture", args.d_reconstruction_texture), ("d_final_conv", args.d_final_conv),
+            ("z_reconstruct", args.z_reconstruct), ("d_final_conv", args.d_final_conv),
         ]
         bad = [n for n, v in unsupported if v]
         if bad:
@@ -142,6 +139,17 @@ class BigGAN(GANBase):
         self.moving_decay = args.moving_decay
         self.d_compat_use_sn_in_critic_output = args.d_compat_use_sn_in_critic_output
         self.extension_32 = getattr(args, "extension_32", False)
+        # the discriminator's reconstruction heads (BigGAN.py:42-53); halfres implies the coarse head
+        self.d_reconstruction_halfres = bool(args.d_reconstruction_halfres)
+        self.d_reconstruction = bool(args.d_reconstruction or args.d_reconstruction_halfres)
+        self.d_reconstruction_texture = bool(args.d_reconstruction_texture)
+        self.d_recon_ch, self.d_recon_ld = args.d_recon_ch, args.d_recon_ld
+        self.d_tex_recon_ch, self.d_tex_recon_ld = args.d_tex_recon_ch, args.d_tex_recon_ld
+        self.d_tex_recon_feat_size = args.d_tex_recon_feat_size
+        self.d_tex_recon_patch_div = args.d_tex_recon_patch_div
+        self.d_recon_bn_after_act = bool(args.d_recon_bn_after_act)
+        self.d_save_recon_samples = bool(args.d_save_recon_samples)
+        self.recon_plan = self._recon_plan()
         self.deep = args.deep                                                          # BigGAN.py:20
         self.g_mixed_resblocks = args.g_mixed_resblocks                                # BigGAN.py:40-41
         self.g_mixed_resblock_ch_div = args.g_mixed_resblock_ch_div
@@ -519,12 +527,110 @@ class BigGAN(GANBase):
         sn_opt["conv"]["sn"] = sn
         return sn_opt
 
-    def discriminator(self, x, is_training=True, reuse=False):
+    def d_group_sizes(self):
+        """Side of the feature map after each block group of the discriminator (where a reconstruction head may sit)."""
+        sizes, s = [], self.img_size
+        for count in self.d_block_info()["counts"]:
+            s //= 2 ** count
+            sizes.append(s)
+        return sizes
+
+    def _recon_plan(self):
+        """Where the reconstruction heads attach and how deep they are (BigGAN.py:639-661), checked at construction.
+        The layer count is log2(target / attach size): the reference's ``depth - 3`` reaches the target only after
+        --g_final_layer has bumped ``depth`` (reconstruction heads, deviation 1)."""
+        plan = {}
+        if not (self.d_reconstruction or self.d_reconstruction_texture):
+            return plan
+        sizes = self.d_group_sizes()
+        if self.d_reconstruction:
+            if 8 not in sizes:
+                raise ValueError("--d_reconstruction attaches to the 8x8 feature map, but at --img_size %d the block groups "
+                                 "of the discriminator end at %s" % (self.img_size, ", ".join(map(str, sizes))))
+            target = self.img_size // 2 if self.d_reconstruction_halfres else self.img_size
+            plan["coarse"] = {"size": 8, "target": target, "layers": int(math.log2(target // 8))}
+        if self.d_reconstruction_texture:
+            fs, div = self.d_tex_recon_feat_size, self.d_tex_recon_patch_div
+            if fs not in sizes:
+                raise ValueError("--d_tex_recon_feat_size %d: at --img_size %d the block groups of the discriminator end "
+                                 "at %s" % (fs, self.img_size, ", ".join(map(str, sizes))))
+            if div < 1 or fs % div or self.img_size % div:
+                raise ValueError("--d_tex_recon_patch_div %d must divide the feature size %d and the image size %d"
+                                 % (div, fs, self.img_size))
+            patch, feat_patch = self.img_size // div, fs // div
+            plan["texture"] = {"size": fs, "patch": patch, "feat_patch": feat_patch, "f": self.img_size // fs,
+                               "layers": int(math.log2(patch // feat_patch))}
+        return plan
+
+    def random_crop_offsets(self, img_shape, crop_size):
+        """BigGAN.py:1489-1493: int32 offsets, uniform in [0, size - crop_size], one per sample (only element [0] is
+        used, for the whole batch: BigGAN.py:656-657).  They stay on the device.  Under data parallelism rank 0's draw
+        is used by every rank, so that the ranks crop one window as one GPU at the global batch would."""
+        n = int(img_shape[0])
+        out = []
+        for side in (img_shape[1], img_shape[2]):
+            out.append(torch.randint(0, int(side) - crop_size + 1, (n,), dtype=torch.int32, device=self.device,
+                                     generator=self.gen))
+        if self.world > 1:
+            src = torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0
+            for t in out:
+                torch.distributed.broadcast(t, src=src, group=self.pg)
+        return out[0], out[1]
+
+    def simple_upscale(self, x, ch, scope, opt):
+        """BigGAN.py:744-753: nearest 2x, conv to 2 ch, bn, glu (glu then bn with --d_recon_bn_after_act)."""
+        with S.variable_scope(scope):
+            x = up_sample(x)
+            x = conv(x, channels=ch * 2, kernel=3, pad=1, stride=1, opt=opt)
+            if not self.d_recon_bn_after_act:
+                return ops.bn_glu(x, opt=opt)                      # bn, then glu: one apply kernel
+            return bn(glu(x), opt=opt)
+
+    def simple_upscaler(self, x, layers=3, scope="upscaler", base_width=64, opt={}, _pre_tanh=False):
+        """BigGAN.py:755-762.  ``_pre_tanh`` (extension): return the image conv's output; the loss kernel applies the
+        tanh itself (functional.ReconLossFn)."""
+        with S.variable_scope(scope):
+            for li in range(layers):
+                x = self.simple_upscale(x, base_width * 2 ** (layers - li - 1), "upscale" + str(li), opt=opt)
+            x = conv(x, channels=self.c_dim, kernel=3, pad=1, stride=1, opt=opt)
+            return x if _pre_tanh else tanh(x)
+
+    def _recon_heads(self, x, outputs, opt, recon):
+        """The heads that attach to a feature map of x's size (BigGAN.py:639-661) -> x for the next block.  The map then
+        has more than one consumer: it is forked, so that the branch gradients meet in one buffer."""
+        size = x.shape[1]
+        heads = [k for k in ("coarse", "texture") if k in self.recon_plan and self.recon_plan[k]["size"] == size]
+        if not heads:
+            return x
+        branches = ops._fork(x, 1 + len(heads))
+        for k, xb in zip(heads, branches[1:]):
+            plan = self.recon_plan[k]
+            if k == "coarse":
+                outputs["coarse_logits"] = self.simple_upscaler(xb, base_width=self.d_recon_ch, layers=plan["layers"],
+                                                                opt=opt, _pre_tanh=True)
+            else:
+                ro_x, ro_y = recon["offsets"]
+                outputs["rnd_offset_x"], outputs["rnd_offset_y"] = ro_x, ro_y
+                fp = plan["feat_patch"]
+                if ops._is_meta(xb):
+                    crop = torch.empty(xb.shape[0], fp, fp, xb.shape[3], device="meta")
+                else:                           # (crop_to_bounding_box: the first offset is the height offset)
+                    crop = Fn.CropAtFn.apply(xb, ro_x, ro_y, fp)
+                outputs["texture_logits"] = self.simple_upscaler(crop, base_width=self.d_tex_recon_ch,
+                                                                 layers=plan["layers"], opt=opt, scope="tex_upscaler",
+                                                                 _pre_tanh=True)
+        return branches[0]
+
+    def discriminator(self, x, is_training=True, reuse=False, _recon=None):
+        """``_recon`` (extension): set by the real call of the D step only - {"offsets": (ro_x, ro_y) or None}; the
+        reconstruction heads run in that call and leave their pre-tanh images in the outputs."""
         opt = {"sn": self.sn, "is_training": is_training, "bn_in_d": self.bn_in_d, "act": self.activation_fn,
                "downsampling_method": self.downsampling_method, "self_attention_bias": self.bias_in_sa,
                "bn": copy.deepcopy(self.bn_options), "conv": copy.deepcopy(self.conv_options)}
         outputs = {}
         self._sn_prefetch("discriminator", x)
+        if _recon is not None:
+            self._sn_prefetch("d_recon", x)
         with S.variable_scope("discriminator", reuse=reuse):
             if self.alpha_mask:                                                        # BigGAN.py:616-619
                 x = alpha_mask(x)
@@ -546,6 +652,8 @@ class BigGAN(GANBase):
                 b_i += 1
                 if b_i == block_info["sa_index"]:
                     x = self_attention_2(x, channels=ch, opt=opt, scope='self_attention')
+                if _recon is not None:                                                 # BigGAN.py:639-661
+                    x = self._recon_heads(x, outputs, opt, _recon)
                 ch = self.d_channels_for_block(b_i)
                 ch_mul = ch_mul * 2
             ch = self.d_channels_for_block(b_i - 1)                                    # BigGAN.py:666
@@ -581,8 +689,12 @@ class BigGAN(GANBase):
         z = torch.empty(B, 1, 1, self.z_dim, device="meta")
         img = self.generator(z, None, is_training=True)
         assert tuple(img.shape) == (B, self.img_size, self.img_size, self.c_dim), img.shape
-        out = self.discriminator(img)
+        out = self.discriminator(img, _recon={"offsets": (None, None)} if self.recon_plan else None)
         assert tuple(out["real"].shape) == (B, 1)
+        for key, head in (("coarse_logits", "coarse"), ("texture_logits", "texture")):
+            if head in self.recon_plan:
+                side = self.recon_plan[head].get("target") or self.recon_plan[head]["patch"]
+                assert tuple(out[key].shape) == (B, side, side, self.c_dim), (key, out[key].shape)
         self.store.pack()
         self.g_arena = self.store.arenas["generator"]
         self.d_arena = self.store.arenas["discriminator"]
@@ -590,11 +702,16 @@ class BigGAN(GANBase):
         self.g_vars = self.store.trainable_variables('generator')
         self.sn_batches = {}
         if self.store.device.type == "cuda":
-            for group in ("generator", "discriminator"):
-                pairs = [(self.store.vars[w], self.store.vars[u]) for w, u in self.store.sn_pairs.items()
-                         if w.startswith(group + "/") and w in self.store.arenas[group].offsets]
-                names = [w for w, u in self.store.sn_pairs.items()
-                         if w.startswith(group + "/") and w in self.store.arenas[group].offsets]
+            # (the reconstruction heads run in one call of the D step only: their power iteration is a batch of its own,
+            #  so that their ``u`` advances exactly when they run)
+            def sn_group(name):
+                if name.startswith("discriminator/upscaler/") or name.startswith("discriminator/tex_upscaler/"):
+                    return "d_recon"
+                return name.split("/", 1)[0]
+            for group in ("generator", "discriminator", "d_recon"):
+                arena = self.store.arenas["discriminator" if group == "d_recon" else group]
+                names = [w for w, u in self.store.sn_pairs.items() if sn_group(w) == group and w in arena.offsets]
+                pairs = [(self.store.vars[w], self.store.vars[self.store.sn_pairs[w]]) for w in names]
                 for i in range(0, len(pairs), 256):
                     chunk = names[i:i + 256]
                     # f | g | h projections of every self-attention block share one packed GEMM operand
@@ -921,10 +1038,13 @@ class BigGAN(GANBase):
         fdot = self.discriminator(dual, reuse=True)["real"].t
         return Fn.GpSurrogateFn.apply(fdot, value)
 
-    def d_forward(self, real, z=None, draws_real=None, draws_fake=None, labels=None, cls_z=None, gp_draws=None):
+    def d_forward(self, real, z=None, draws_real=None, draws_fake=None, labels=None, cls_z=None, gp_draws=None,
+                  recon_offsets=None):
         """BigGAN.py:806-808, 856-883: D(aug(real)), D(aug(G(z))), hinge + flood (+ the label loss on the
         real half when n_labels > 0, BigGAN.py:853).  G runs without a backward graph (d_loss is minimised
-        over d_vars only); real and fake go through D as one batch."""
+        over d_vars only); real and fake go through D as one batch.  With a reconstruction head (BigGAN.py:810-836,
+        885-889) the real batch takes a call of its own, the only one the heads run in; ``recon_offsets``: explicit
+        (ro_x, ro_y) int32 device tensors of the texture crop (drawn when None)."""
         B = real.shape[0]
         self._begin_run()
         if z is None:
@@ -935,10 +1055,18 @@ class BigGAN(GANBase):
             fake = self.generator(z, cls_z, is_training=True)
         real_aug = DiffAugment(real, policy=self.da_policy, draws=draws_real, generator=self.gen)
         fake_aug = DiffAugment(fake, policy=self.da_policy, draws=draws_fake, generator=self.gen)
-        if self.bn_in_d:
+        recon = None
+        if self.recon_plan:
+            recon = {"offsets": (None, None)}
+            if "texture" in self.recon_plan:
+                tp = self.recon_plan["texture"]
+                recon["offsets"] = recon_offsets if recon_offsets is not None else \
+                    self.random_crop_offsets((B, tp["size"], tp["size"]), tp["feat_patch"])
+        if self.bn_in_d or recon is not None:
             # batch norm couples the samples of a call: keep the reference's two instantiations
             # (BigGAN.py:807,857), each with its own batch statistics; moving statistics compound
-            d_real, d_fake = self.discriminator(real_aug), self.discriminator(fake_aug, reuse=True)
+            d_real = self.discriminator(real_aug, _recon=recon)
+            d_fake = self.discriminator(fake_aug, reuse=True)
             real_logits, fake_logits = d_real["real"], d_fake["real"]
             d_out = d_real
         else:
@@ -957,6 +1085,20 @@ class BigGAN(GANBase):
             d_cls = self._cls_loss()(labels, real_cls, self.d_cls_loss_weight, self._reduce_fn(), self.world)
             out["d_cls_loss"] = d_cls
             d_loss = Fn.AddFn.apply(d_loss, d_cls)
+        if recon is not None:                                                          # BigGAN.py:810-836, 885-889
+            red, ro_x, ro_y = self._reduce_fn(), recon["offsets"][0], recon["offsets"][1]
+            if "coarse" in self.recon_plan:
+                mode = Fn.RECON_HALFRES if self.d_reconstruction_halfres else Fn.RECON_IDENTITY
+                out["d_recon"], out["coarse_upscaled"] = Fn.ReconLossFn.apply(
+                    d_real["coarse_logits"], real_aug, None, None, mode, 1, self.d_recon_ld, red, self.world)
+                d_loss = Fn.AddFn.apply(d_loss, out["d_recon"])
+            if "texture" in self.recon_plan:
+                out["d_tex_recon"], out["texture_upscaled"] = Fn.ReconLossFn.apply(
+                    d_real["texture_logits"], real_aug, ro_x, ro_y, Fn.RECON_CROP, self.recon_plan["texture"]["f"],
+                    self.d_tex_recon_ld, red, self.world)
+                d_loss = Fn.AddFn.apply(d_loss, out["d_tex_recon"])
+                out["rnd_offset_x"], out["rnd_offset_y"] = ro_x, ro_y
+            out["real_aug"] = real_aug
         out["d_loss"] = d_loss
         return out
 
@@ -967,8 +1109,14 @@ class BigGAN(GANBase):
             return v[k]
         return v
 
+    def _recon_offsets_for(self, k, v):
+        """One (ro_x, ro_y) pair for every virtual batch, or a list of --virtual_batches pairs."""
+        if v is not None and isinstance(v[0], (list, tuple)):
+            return self._per_virtual_batch(k, list(v))
+        return v
+
     def d_step(self, real, z=None, draws_real=None, draws_fake=None, apply=True, labels=None, cls_z=None,
-               defer=False, gp_draws=None):
+               defer=False, gp_draws=None, recon_offsets=None):
         """One run of d_ops (utils.py:252-320): with --virtual_batches k, gradients of k forward/backward
         passes (each on its own real batch / z / draws; lists of k are accepted) are accumulated and
         applied once, scaled 1/k; reported losses are means over the k passes."""
@@ -978,9 +1126,11 @@ class BigGAN(GANBase):
         for k in range(vb):
             out = self.d_forward(*[self._per_virtual_batch(k, a) for a in (real, z, draws_real, draws_fake, labels)],
                                  cls_z=cls_z,                                        # one feed_dict for all k
-                                 gp_draws=self._per_virtual_batch(k, gp_draws))
+                                 gp_draws=self._per_virtual_batch(k, gp_draws),
+                                 recon_offsets=self._recon_offsets_for(k, recon_offsets))
             out["d_loss"].backward()
             self._sn_backward("discriminator")
+            self._sn_backward("d_recon")
             outs.append(out)
         self.store.zero_untouched("discriminator")
         if self.shards:
@@ -994,7 +1144,7 @@ class BigGAN(GANBase):
                 self._finish_d()
         elif apply:
             self._adam(self.d_arena, self.d_learning_rate, with_ema=False, grad_scale=1.0 / vb)
-        return self._mean_losses(outs, ("d_loss", "d_cls_loss", "gp"))
+        return self._mean_losses(outs, ("d_loss", "d_cls_loss", "gp", "d_recon", "d_tex_recon"))
 
     def _finish_d(self):
         pending = getattr(self, "_pending_d", None)
@@ -1132,6 +1282,10 @@ class BigGAN(GANBase):
         losses["d_loss"] = d["d_loss"]
         if d.get("gp") is not None:
             losses["gp"] = d["gp"]
+        for key in ("d_recon", "d_tex_recon"):
+            if key in d:
+                losses[key] = d[key]
+        self._last_d_out = d if self.d_save_recon_samples else None
         if run_g:
             g = self.g_step(first.shape[0], after_generator=self._finish_d,
                             real=(real_g if real_g is not None else real) if self.relativistic else None)
@@ -1204,6 +1358,10 @@ class BigGAN(GANBase):
         self._adam_prepare(self.d_arena, self.d_learning_rate)
         self._graph_d.replay()
         losses["d_loss"] = self._g_out_d["d_loss"]
+        for key in ("d_recon", "d_tex_recon"):
+            if key in self._g_out_d:
+                losses[key] = self._g_out_d[key]
+        self._last_d_out = self._g_out_d if self.d_save_recon_samples else None
         if (self.counter - 1) % self.n_critic == 0:
             self._adam_prepare(self.g_arena, self.g_learning_rate)
             self._graph_g.replay()
@@ -1300,10 +1458,39 @@ class BigGAN(GANBase):
                     print_str += ", " + name + ": %.4f" % val
                 if self.rank == 0:
                     print(print_str, flush=True)
+                if self.d_save_recon_samples and self.counter % self.print_freq == 0 and self.rank == 0:
+                    self.save_recon_samples(epoch, idx + 1)                            # BigGAN.py:1050-1074
                 if (idx + 1) % self.save_freq == 0:                                   # BigGAN.py:1121-1122
                     self.save(self.checkpoint_dir, self.counter)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
+
+    def save_recon_samples(self, epoch, idx):
+        """--d_save_recon_samples (BigGAN.py:1050-1074): the targets and the reconstructions of the last D step as image
+        grids ``<sample_dir>/BigGAN_{recon,txrecon}_{real,fake}_<epoch>_<idx>.png``."""
+        from .utils import save_images, check_folder
+        d = getattr(self, "_last_d_out", None)
+        if not d:
+            return []
+        check_folder(self.sample_dir)
+        grids = {}
+        real = d["real_aug"].detach()
+        if "coarse_upscaled" in d:
+            grids["recon_fake"] = d["coarse_upscaled"]
+            grids["recon_real"] = ops.avg_pooling(real) if self.d_reconstruction_halfres else real
+        if "texture_upscaled" in d:
+            tp = self.recon_plan["texture"]
+            oy = min(max(int(d["rnd_offset_x"][0].item()), 0), tp["size"] - tp["feat_patch"]) * tp["f"]
+            ox = min(max(int(d["rnd_offset_y"][0].item()), 0), tp["size"] - tp["feat_patch"]) * tp["f"]
+            grids["txrecon_fake"] = d["texture_upscaled"]
+            grids["txrecon_real"] = real[:, oy:oy + tp["patch"], ox:ox + tp["patch"], :]
+        paths = []
+        for name, img in grids.items():
+            a = img.detach().float().cpu().numpy()
+            dim = int(math.floor(math.sqrt(a.shape[0])))
+            paths.append(save_images(a[:dim * dim], [dim, dim], os.path.join(
+                self.sample_dir, "%s_%s_%02d_%05d.png" % (self.model_name, name, epoch, idx))))
+        return paths
 
     # ---- sampling with the EMA weights (BigGAN.py:963-971) ------------------------------------
     def sample(self, z=None, cls_z=None, B=None, use_ema=True):

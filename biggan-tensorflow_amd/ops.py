@@ -913,7 +913,9 @@ def up_sample(x, scale_factor=2):
         raise NotImplementedError("up_sample scale_factor != 2")
     if _is_meta(x):
         return _meta((x.shape[0], x.shape[1] * 2, x.shape[2] * 2, x.shape[3]))
-    return _resident_out(Fn.UpSample2Fn.apply(_to(x, torch.float32)))
+    if x.dtype == torch.bfloat16:          # a bf16-resident map stays bf16: the copy is exact, the backward rounds once
+        return Fn.UpSample2Fn.apply(x)
+    return _resident_out(Fn.UpSample2Fn.apply(x))
 
 
 ##################################################################################
@@ -1073,8 +1075,19 @@ def _bn_act(x, z, opt, _out_fp32=False):
     return opt["act"](x)
 
 
-def batch_norm(x, opt={}, scope='batch_norm', _act=None, _out_fp32=False):
-    """ops.py:580-585: tf.layers.batch_normalization(momentum, epsilon=1e-5, training)."""
+def bn_glu(x, opt={}, scope='batch_norm'):
+    """bn followed by glu (BigGAN.py:749-750), fused into one apply kernel the way _bn_act fuses PReLU: plain batch norm in
+    training mode.  Batch-renorm types and inference take bn, then glu.  (BG_FUSE_BNGLU=0: A/B switch, never fused.)"""
+    type, bn_scope = _bn_type(opt, scope)
+    if type in ('bn', 'batch_norm') and opt.get("is_training", True) and not _is_dual(x) \
+            and os.environ.get("BG_FUSE_BNGLU", "1") != "0":
+        return batch_norm(x, opt=opt, scope=bn_scope, _glu=True)
+    return glu(bn(x, opt=opt, scope=scope))
+
+
+def batch_norm(x, opt={}, scope='batch_norm', _act=None, _out_fp32=False, _glu=False):
+    """ops.py:580-585: tf.layers.batch_normalization(momentum, epsilon=1e-5, training).  ``_glu`` (extension): the GLU
+    that follows is applied by the same kernel."""
     C = x.shape[-1]
     with variable_scope(scope):
         gamma = get_variable("gamma", [C], initializer=S.constant_initializer(1.0))
@@ -1084,9 +1097,13 @@ def batch_norm(x, opt={}, scope='batch_norm', _act=None, _out_fp32=False):
     alpha = None
     if _act is not None:
         _, alpha = _act_alpha(_act, x)
+    if _glu and C % 2:
+        raise ValueError("glu: the channel count %d is odd" % C)
     if _is_meta(x):
-        return _meta(x.shape)
+        return _meta(tuple(x.shape[:-1]) + (C // 2,)) if _glu else _meta(x.shape)
     momentum = opt.get("bn", {}).get("momentum", 0.98)
+    if _glu:
+        return _resident_out(Fn.BnGluFn.apply(x, gamma, beta, mm, mv, momentum, 1e-05, True, _run.reduce_fn, _run.world))
     return Fn.BnActFn.apply(x, gamma, beta, alpha, mm, mv, momentum, 1e-05, True, bool(opt["is_training"]),
                             _run.reduce_fn, _run.world, None, _bn_out_dtype(x, _out_fp32))
 
@@ -1231,7 +1248,12 @@ def generator_loss(loss_func, fake, real, flood_level=0):
 
 
 def glu(x, opt=None):
-    raise NotImplementedError("glu (ops.py:842) is outside the default hot path")
+    """ops.py:842-845: main * sigmoid(gate), the two halves of the channels."""
+    if x.shape[-1] % 2:
+        raise ValueError("glu: the channel count %d is odd" % x.shape[-1])
+    if _is_meta(x):
+        return _meta(tuple(x.shape[:-1]) + (x.shape[-1] // 2,))
+    return Fn.GluFn.apply(x)
 
 
 def flood_loss(loss, flood_level):

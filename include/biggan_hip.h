@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 7
+#define BG_ABI_VERSION 8
 
 enum { BG_OK = 0, BG_ERR_ARG = 1, BG_ERR_LAUNCH = 2, BG_ERR_UNSUPPORTED = 3 };
 enum { BG_PAD_REFLECT = 0, BG_PAD_ZERO = 1 };
@@ -661,6 +661,46 @@ int bg_adam_tf_ema_step(float* p, const float* g, float* m, float* v, float* ema
 int bg_adam_tf_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, const float* lr_t_dev,
                             float b1, float b2, float eps, float ema_decay, float grad_scale, int64_t n,
                             void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Discriminator reconstruction heads (BigGAN.py:639-661, 744-762, 810-836; csrc/recon.hip).  dtype = BG_F32 / BG_BF16;
+ * 16-byte accesses when C is a multiple of 4 (fp32) / 8 (bf16) and the tensors are 16-byte aligned, scalar otherwise.
+ * bg_glu_*: ops.py:842-845, x[rows, 2C] -> y[rows, C] = x[:, :C] * sigmoid(x[:, C:]); bwd writes dx for both halves.
+ * bg_upsample2_*_t: nearest-neighbour 2x (ops.py:516-519), x[N,H,W,C] -> y[N,2H,2W,C]; bwd = 2x2 box sum (fp32 sum,
+ *   one rounding).
+ * bg_crop_at_*: y[N,p,p,C] = x[N, oy:oy+p, ox:ox+p, C] with oy = off_y[0], ox = off_x[0] read on the DEVICE (clamped to
+ *   [0, H-p] / [0, W-p]); bwd writes all of dx (zero outside the window).
+ * bg_recon_loss_*: y[N,h,w,C] pre-tanh, target[N,S,S,C] fp32; mode 0: target itself (S == h), 1: its 2x2 average
+ *   (S == 2h), 2: its crop at (off_y[0]*f, off_x[0]*f).  sums: sum[0] += sum (tanh(y) - t)^2 (fp64, caller zeroes;
+ *   all-reduced under data parallelism), tanh_out (nullable) receives tanh(y).  finalize: loss = sqrt(sum) * scale.
+ *   bwd: dy = dloss[0] * scale * (tanh(y) - t) / sqrt(sum) * (1 - tanh(y)^2)  (dloss NULL: 1; sum == 0: dy = 0).
+ * ------------------------------------------------------------------------------------------ */
+/* bg_bn_glu_*: batch-norm apply on x[rows, 2C] (mean, rstd, gamma, beta: float[2C], the affine of bg_bn_apply_act_*)
+ *   fused with the GLU that follows: y[rows, C].  Backward in the reduce / finalize / dx split of batch norm:
+ *   bwd_reduce writes part = float[3][nseg][2C] (plane 0: sum g, plane 1: sum g xh over the rows of a segment, g = the
+ *   gradient at the batch-norm output; plane 2 unused), which bg_bn_bwd_finalize(part, gamma, 0, count, dgamma, dbeta,
+ *   NULL, cm, nseg, 2C) turns into dgamma, dbeta and cm = {m1, m2}; after the caller's all-reduce of cm,
+ *   bwd_dx writes dx[rows, 2C].  nseg: any split of the rows, 1 <= nseg <= min(rows, 65535). */
+int bg_bn_glu_fwd(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y,
+                  int dtype, int64_t rows, int C, void* stream);
+int bg_bn_glu_bwd_reduce(const void* x, const void* dy, const float* mean, const float* rstd, const float* gamma,
+                         const float* beta, float* part, int dtype, int64_t rows, int C, int nseg, void* stream);
+int bg_bn_glu_bwd_dx(const void* x, const void* dy, const float* mean, const float* rstd, const float* gamma,
+                     const float* beta, const float* cm, void* dx, int dtype, int64_t rows, int C, void* stream);
+int bg_glu_fwd(const void* x, void* y, int dtype, int64_t rows, int C, void* stream);
+int bg_glu_bwd(const void* x, const void* dy, void* dx, int dtype, int64_t rows, int C, void* stream);
+int bg_upsample2_fwd_t(const void* x, void* y, int dtype, int N, int H, int W, int C, void* stream);
+int bg_upsample2_bwd_t(const void* dy, void* dx, int dtype, int N, int H, int W, int C, void* stream);
+int bg_crop_at_fwd(const void* x, void* y, int dtype, const int32_t* off_y, const int32_t* off_x, int N, int H, int W,
+                   int p, int C, void* stream);
+int bg_crop_at_bwd(const void* dy, void* dx, int dtype, const int32_t* off_y, const int32_t* off_x, int N, int H, int W,
+                   int p, int C, void* stream);
+int bg_recon_loss_sums(const float* y, const float* target, float* tanh_out, const int32_t* off_y, const int32_t* off_x,
+                       int mode, int f, double* sum, int N, int h, int w, int S, int C, void* stream);
+int bg_recon_loss_finalize(const double* sum, double scale, float* loss, void* stream);
+int bg_recon_loss_bwd(const float* y, const float* target, const int32_t* off_y, const int32_t* off_x, int mode, int f,
+                      const double* sum, double scale, const float* dloss, float* dy, int N, int h, int w, int S, int C,
+                      void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
