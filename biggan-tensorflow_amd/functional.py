@@ -70,6 +70,22 @@ def cast(x, dtype):
     return y
 
 
+def image_tiles_u8(x, grid, gh, gw, tile0=0):
+    """Images x [n,H,W,C] (fp32 or bf16, nominally in [-1,1], C in 1/3/4) -> tiles tile0 .. tile0+n-1 of the uint8 image
+    grid [gh*H, gw*W, C], in place and bit-identical to utils.inverse_transform + utils.grid_u8 (csrc/sample.hip).  Images
+    past the last tile are skipped, other tiles are left as they are: zero-fill the grid once, then fill it one generator
+    batch at a time.  No autograd."""
+    if x.dim() != 4:
+        raise RuntimeError("image_tiles_u8: x must be [n,H,W,C], got %s" % (tuple(x.shape),))
+    n, H, W, C = x.shape
+    if grid.dtype != torch.uint8 or tuple(grid.shape) != (gh * H, gw * W, C):
+        raise RuntimeError("image_tiles_u8: grid must be uint8 [%d,%d,%d], got %s %s"
+                           % (gh * H, gw * W, C, grid.dtype, tuple(grid.shape)))
+    x = _c(x.detach())
+    check(lib().bg_image_tiles_u8(act(x), dt(x), n, H, W, C, hip.ptr(grid), gh, gw, int(tile0), stream()))
+    return grid
+
+
 def weight_packs(w):
     """(pack_p, pack_t): the bf16 K-contiguous copies of a conv / transposed-conv kernel [k,k,A,B]: pack_p keeps the
     variable's order [k*k][A][B], pack_t is [k*k][B][A].  Spectrally normalised kernels get them from the
@@ -1334,7 +1350,8 @@ class SnBatch:
         """``run_stamp``: identity of the run (ops.begin_run) in which the packed copies / sigma are written; consumers
         that read them outside the conv path (the regulariser's Gram from the packed weights) check it, so that packs of an
         earlier run - older weights, older sigma - are never used silently."""
-        if self.shard is None:
+        if self.shard is None or getattr(self, "local_only", False):
+            # (local_only: sampling on one rank - every weight is iterated here, from the gathered u of the last step)
             check(lib().bg_spectral_norm_batch_fwd(hip.ptr(self.table), self.n, hip.ptr(self.ws), self.ws_bytes, stream()))
         else:
             self.power_owned()

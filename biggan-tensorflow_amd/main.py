@@ -103,7 +103,7 @@ def main(argv=None):
     gan = BigGAN(args)
     gan.build_model()
     if args.phase == 'train':
-        gan.train()
+        gan.train(samples=True)                           # sample grids every --print_freq iterations (BigGAN.py:1125)
         print(" [*] Training finished!")
     elif args.phase == 'test':
         gan.test()

@@ -149,6 +149,26 @@ class BigGAN(GANBase):
         self.d_tex_recon_patch_div = args.d_tex_recon_patch_div
         self.d_recon_bn_after_act = bool(args.d_recon_bn_after_act)
         self.d_save_recon_samples = bool(args.d_save_recon_samples)
+        # in-training sample grids (BigGAN.py:168-183)
+        self.sample_num = args.sample_num
+        self.static_sample_z = bool(args.static_sample_z)
+        self.static_sample_seed = args.static_sample_seed
+        self.z_trunc_sample = bool(args.z_trunc_sample)
+        self.save_morphs = bool(args.save_morphs)
+        self.save_cls_samples = bool(args.save_cls_samples)
+        self.sample_ema = args.sample_ema
+        if self.sample_ema not in ('ema', 'noema', 'both'):
+            raise ValueError('Invalid mode for sample_ema specified')
+        self.generate_noema_samples = self.sample_ema != 'ema'
+        self.generate_ema_samples = self.sample_ema != 'noema'
+        if self.save_morphs and int(math.floor(math.sqrt(self.sample_num))) < 2:
+            raise ValueError("--save_morphs needs --sample_num >= 4 (the blend weights divide by the grid side - 1)")
+        # fresh sample latents (--static_sample_z false) have a generator of their own: looking at samples never
+        # advances the draws of the training run (self.gen)
+        self.sample_gen = torch.Generator(device="cpu")
+        self.sample_gen.manual_seed((int(self.static_sample_seed) + 1) % (1 << 63))
+        self.labels = None                     # the dataset's label table (open_dataset); None: synthetic one-hots
+        self._static_set = None                # (z, class vectors) of the static sample set, drawn on first use
         self.recon_plan = self._recon_plan()
         self.deep = args.deep                                                          # BigGAN.py:20
         self.g_mixed_resblocks = args.g_mixed_resblocks                                # BigGAN.py:40-41
@@ -1393,17 +1413,19 @@ class BigGAN(GANBase):
         gc.collect()
         gc.freeze()
 
-    def train(self, data_fn=None, iterations=None, resume=True):
+    def train(self, data_fn=None, iterations=None, resume=True, samples=False):
         """BigGAN.py:1015-1118 training loop (synthetic data unless ``data_fn`` is given): resume from the
         latest checkpoint of ``checkpoint_dir`` if there is one, print the losses every iteration, save
-        every ``save_freq`` iterations of an epoch (rank 0 writes; replicas are identical)."""
+        every ``save_freq`` iterations of an epoch (rank 0 writes; replicas are identical).  ``samples``: write the
+        sample grids of ``save_samples`` every ``print_freq`` iterations of an epoch (BigGAN.py:1125; the command line
+        turns it on, programmatic callers opt in)."""
         loader = None
         if data_fn is None:
             loader = self.open_dataset()
             if loader is not None:
                 data_fn = lambda: next(loader)                                    # noqa: E731
         try:
-            return self._train_loop(data_fn, iterations, resume)
+            return self._train_loop(data_fn, iterations, resume, samples)
         finally:
             if loader is not None:
                 loader.close()
@@ -1420,12 +1442,13 @@ class BigGAN(GANBase):
                                     ignore_missing=self.args.ignore_missing_labels, n_labels=self.n_labels, root=root)
         if self.acgan and labels is None:
             raise ValueError("--n_labels > 0 needs --label_file")
+        self.labels = labels if self.acgan else None          # (the sampler draws its class vectors from these rows)
         print("# dataset number:", len(files))
         image_data = D.ImageData(self.img_size, self.c_dim, True, self.args.random_flip, seed=1234 + self.rank)
         return D.BatchLoader(files, labels if self.acgan else None, self.batch_size, image_data, self.device,
                              seed=4321, rank=self.rank, world=self.world)
 
-    def _train_loop(self, data_fn, iterations, resume):
+    def _train_loop(self, data_fn, iterations, resume, samples=False):
         could_load, checkpoint_counter = (self.load(self.checkpoint_dir) if resume else (False, 0))
         if could_load:
             start_epoch = int(checkpoint_counter / self.iterations_per_epoch)
@@ -1462,6 +1485,8 @@ class BigGAN(GANBase):
                     self.save_recon_samples(epoch, idx + 1)                            # BigGAN.py:1050-1074
                 if (idx + 1) % self.save_freq == 0:                                   # BigGAN.py:1121-1122
                     self.save(self.checkpoint_dir, self.counter)
+                if samples and (idx + 1) % self.print_freq == 0:                      # BigGAN.py:1125
+                    self.save_samples(epoch, idx + 1)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
 
@@ -1518,6 +1543,164 @@ class BigGAN(GANBase):
             if live is not None:
                 arena.params.copy_(live)
         return img
+
+    # ---- in-training sample grids (BigGAN.py:980-1008, 1125-1230, 1397-1445) ---------------------
+    def _generator_u(self):
+        """The spectral-norm ``u`` vectors of the generator: the only state a no-grad, is_training=False generator pass
+        writes (its power iteration advances them)."""
+        return [self.store.vars[u] for w, u in self.store.sn_pairs.items() if w.startswith("generator/")]
+
+    def generate(self, z, cls_z=None, ema=True, grid=None, gh=0, gw=0, _synced=False):
+        """BigGAN.py:1397-1445 (without ``with_discriminator``): images of a list of latents (and class vectors; None
+        with --n_labels: zeros).  The list is padded to a multiple of ``batch_size`` by repeating entry 0 and runs
+        ``batch_size`` at a time with is_training=False; ``ema`` reads the trainables from their moving averages,
+        swapped in once for the whole call.  With ``grid`` (uint8 [gh*S, gw*S, c_dim] on the device) each batch goes straight
+        into the byte grid at its tile offset (functional.image_tiles_u8) and the grid is returned: one batch of float
+        images is live at a time.  Without it: the concatenated images, trimmed to len(z).
+
+        Unlike ``sample()`` this leaves the model as it found it: the generator's ``u`` vectors are put back before
+        every batch and after the last, so each image is a function of its latent alone and the training run does not
+        depend on whether anybody looked at samples.  Under a sharded optimiser the caller runs
+        ``sync_sharded_state()`` on every rank first (``_synced``); the generator passes themselves are local."""
+        import numpy as np
+
+        def dev(a, width):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
+            return a.to(device=self.device, dtype=torch.float32).reshape(-1, width)
+        B = self.batch_size
+        z = dev(z, self.z_dim)
+        n = z.shape[0]
+        if n == 0:
+            raise ValueError("generate: no latents")
+        if self.acgan:
+            cls_z = (torch.zeros(n, self.n_labels, dtype=torch.float32, device=self.device) if cls_z is None
+                     else dev(cls_z, self.n_labels))
+            if cls_z.shape[0] != n:
+                raise ValueError("generate: %d latents but %d class vectors" % (n, cls_z.shape[0]))
+        else:
+            cls_z = None
+        pad = -n % B
+        if pad:
+            z = torch.cat([z, z[0:1].expand(pad, -1)])
+            if cls_z is not None:
+                cls_z = torch.cat([cls_z, cls_z[0:1].expand(pad, -1)])
+        z = z.reshape(-1, 1, 1, self.z_dim)
+        if not _synced:
+            self.sync_sharded_state()
+        self._wait_params("generator")
+        arena = self.g_arena
+        u_live = self._generator_u()
+        sn_batches = getattr(self, "sn_batches", {}).get("generator", ())
+        out = []
+        with torch.no_grad():
+            u_saved = [u.clone() for u in u_live]
+            live = None
+            if ema and arena.ema is not None:
+                live = arena.params.clone()
+                arena.params.copy_(arena.ema)
+            for sb in sn_batches:
+                sb.local_only = True              # (a weight-sharded power iteration would be a collective)
+            try:
+                S.set_default_store(self.store)
+                Fn.set_precision(self.precision)
+                for b in range(0, z.shape[0], B):
+                    if b and u_live:
+                        torch._foreach_copy_(u_live, u_saved)
+                    ops.begin_run(None, 1)
+                    img = self.generator(z[b:b + B], None if cls_z is None else cls_z[b:b + B], is_training=False,
+                                         reuse=True)
+                    if grid is not None:
+                        Fn.image_tiles_u8(img, grid, gh, gw, tile0=b)
+                    else:
+                        out.append(img)
+            finally:
+                for sb in sn_batches:
+                    sb.local_only = False
+                if u_live:
+                    torch._foreach_copy_(u_live, u_saved)
+                if live is not None:
+                    arena.params.copy_(live)
+        if grid is not None:
+            return grid
+        return torch.cat(out)[:n]
+
+    def static_sample_set(self):
+        """(z [rounded_n,1,1,z_dim], class vectors [rounded_n,n_labels] or None) as fp32 numpy arrays: the static sample
+        set of BigGAN.py:980-1002, drawn on first use (sampling.static_z / static_cls; --load_cls_samples_from replaces
+        the class vectors, --save_cls_samples_to writes them)."""
+        if self._static_set is None:
+            import numpy as np
+            from . import sampling as Sp
+            _, rounded_n, _ = Sp.grid_plan(self.sample_num, self.batch_size)
+            z = Sp.static_z(rounded_n, self.z_dim, self.static_sample_seed, self.z_trunc_sample).numpy()
+            cls = None
+            if self.acgan:
+                cls = Sp.static_cls(self._label_table(), rounded_n, self.static_sample_seed)
+                if self.args.load_cls_samples_from:
+                    _, vectors = Sp.read_vectors(self.args.load_cls_samples_from, expect=rounded_n)
+                    cls = np.asarray(vectors[:rounded_n], dtype=np.float32)
+                    if cls.ndim != 2 or cls.shape[1] != self.n_labels:
+                        raise ValueError("%s: class vectors of %s values, --n_labels is %d"
+                                         % (self.args.load_cls_samples_from, cls.shape[1:], self.n_labels))
+                if self.args.save_cls_samples_to and self.rank == 0:
+                    Sp.write_vectors(self.args.save_cls_samples_to, cls)
+            self._static_set = (z, cls)
+        return self._static_set
+
+    def _label_table(self):
+        from . import sampling as Sp
+        return self.labels if self.labels is not None else Sp.synthetic_label_table(self.n_labels)
+
+    def save_samples(self, epoch, idx):
+        """The sample grids of one ``print_freq`` event (BigGAN.py:1125-1230) into ``sample_dir``; returns their paths.
+        ``<model>_ema_EE_IIIII.png`` / ``_noema_`` (--sample_ema), ``_morph_`` (--save_morphs: a bilinear blend of four
+        static latents with an extrapolated border ring), ``_cls_EE_IIIII_TTT.png`` (--save_cls_samples with --n_labels:
+        the static latents under class vectors that carry tag TTT).  With --static_sample_z the ema / noema grids show
+        the static set, otherwise fresh latents from a generator of their own with zero class vectors.
+
+        Every rank calls it (``sync_sharded_state`` is collective); rank 0 runs the generator and writes.  Nothing the
+        training run reads is changed: parameters, moving averages, optimiser slots, statistics, every ``u``,
+        ``self.gen`` and ``self.counter`` are bit-identical afterwards.  The grids are assembled as bytes on the device
+        and cross to the host once, one byte per element."""
+        from . import sampling as Sp
+        from .utils import write_png, check_folder
+        self.sync_sharded_state()
+        if self.rank != 0:
+            return []
+        check_folder(self.sample_dir)
+        B = self.batch_size
+        dim, _, batches = Sp.grid_plan(self.sample_num, B)
+        rng = Sp.event_rng(self.static_sample_seed, epoch, self.iterations_per_epoch, idx)
+        paths = []
+
+        def write(name, z, cls_z, ema, side):
+            grid = torch.zeros(side * self.img_size, side * self.img_size, self.c_dim, dtype=torch.uint8,
+                               device=self.device)
+            self.generate(z, cls_z, ema=ema, grid=grid, gh=side, gw=side, _synced=True)
+            paths.append(write_png(grid.cpu().numpy(), os.path.join(self.sample_dir, name)))
+
+        def plain(kind, ema):
+            if self.static_sample_z:
+                zs, cs = self.static_sample_set()
+                z, cls_z = zs[:batches * B], (None if cs is None else cs[:batches * B])
+            else:                                                                      # BigGAN.py:1004-1008
+                z, cls_z = Sp.draw_z(batches * B, self.z_dim, self.sample_gen, self.z_trunc_sample), None
+            write(Sp.sample_names(self.model_name, epoch, idx)[kind], z, cls_z, ema, dim)
+        if self.generate_ema_samples:
+            plain("ema", True)
+        if self.generate_noema_samples:
+            plain("noema", False)
+        if self.save_morphs:                                                           # BigGAN.py:1169-1200
+            zs, cs = self.static_sample_set()
+            corners = Sp.morph_corners(self.sample_num, rng)
+            z, cls_z = Sp.morph_latents([zs[i] for i in corners], None if cs is None else [cs[i] for i in corners], dim)
+            write(Sp.sample_names(self.model_name, epoch, idx)["morph"], z, cls_z, True, dim + 2)
+        if self.acgan and self.save_cls_samples:                                       # BigGAN.py:1202-1230
+            zs, _ = self.static_sample_set()
+            tag, cls_z = Sp.cls_grid_vectors(self._label_table(), self.n_labels, dim * dim, rng)
+            write(Sp.sample_names(self.model_name, epoch, idx, tag)["cls"], zs[:dim * dim], cls_z, True, dim)
+        return paths
 
     def test(self):
         """--phase test (BigGAN.py:1372-1395): load the latest checkpoint and write ``test_num`` grids of

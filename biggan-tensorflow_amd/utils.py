@@ -60,18 +60,33 @@ def merge(images, size):
     raise ValueError('in merge(images,size) images parameter must have dimensions: HxW or HxWx3 or HxWx4')
 
 
-def imsave(images, size, path):
-    """utils.py:156-157 (imageio.imwrite): 8-bit PNG written with zlib only (no imaging library here)."""
-    import struct
-    import zlib
+def grid_u8(images, size):
+    """The 8-bit grid of [n, h, w, c] images in [0, 1]: merge (a float64 grid), x255, round to nearest even, clamp.
+    Returns uint8 [h, w, c] (c = 1 for grayscale).  ``functional.image_tiles_u8`` computes the same bytes on the device."""
     import numpy as np
     img = merge(images, size)
     a = np.clip(np.rint(img * 255.0), 0, 255).astype(np.uint8)
     if a.ndim == 2:
         a = a[:, :, None]
+    return a
+
+
+def write_png(a, path):
+    """uint8 [h, w] or [h, w, c] (c = 1, 3 or 4) -> 8-bit PNG written with zlib only (no imaging library here)."""
+    import struct
+    import zlib
+    import numpy as np
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError("write_png: expected uint8, got %s" % a.dtype)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
+        raise ValueError("write_png: expected [h, w] or [h, w, 1|3|4], got %s" % (a.shape,))
+    a = np.ascontiguousarray(a)
     h, w, c = a.shape
     color_type = {1: 0, 3: 2, 4: 6}[c]
-    raw = b"".join(b"\x00" + a[r].tobytes() for r in range(h))
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), a.reshape(h, w * c)], axis=1).tobytes()   # filter type 0 per row
 
     def chunk(tag, data):
         return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
@@ -80,6 +95,11 @@ def imsave(images, size, path):
     with open(path, "wb") as f:
         f.write(png)
     return path
+
+
+def imsave(images, size, path):
+    """utils.py:156-157 (imageio.imwrite)."""
+    return write_png(grid_u8(images, size), path)
 
 
 def save_images(images, size, image_path):

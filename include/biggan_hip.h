@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 8
+#define BG_ABI_VERSION 9
 
 enum { BG_OK = 0, BG_ERR_ARG = 1, BG_ERR_LAUNCH = 2, BG_ERR_UNSUPPORTED = 3 };
 enum { BG_PAD_REFLECT = 0, BG_PAD_ZERO = 1 };
@@ -700,6 +700,17 @@ int bg_recon_loss_sums(const float* y, const float* target, float* tanh_out, con
 int bg_recon_loss_finalize(const double* sum, double scale, float* loss, void* stream);
 int bg_recon_loss_bwd(const float* y, const float* target, const int32_t* off_y, const int32_t* off_x, int mode, int f,
                       const double* sum, double scale, const float* dloss, float* dy, int N, int h, int w, int S, int C,
+                      void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Sample grids (utils.py:133-161 save_images; csrc/sample.hip).
+ * bg_image_tiles_u8: x [n,H,W,C] (BG_F32 / BG_BF16, NHWC, nominally in [-1,1], C in {1,3,4}) -> bytes of the image grid
+ *   grid [gh*H, gw*W, C] uint8, row-major.  Image i goes to tile t = tile0 + i at grid row t / gw, column t % gw; images
+ *   whose tile is >= gh*gw are skipped; tiles without an image are left untouched (the caller zero-fills the grid once
+ *   and may fill it one generator batch at a time).  byte = clamp(rint((double)((x + 1.0f) * 0.5f) * 255.0), 0, 255),
+ *   bit-identical to the numpy host path; +-inf clamp, NaN writes 0.
+ * ------------------------------------------------------------------------------------------ */
+int bg_image_tiles_u8(const void* x, int x_dtype, int n, int H, int W, int C, uint8_t* grid, int gh, int gw, int tile0,
                       void* stream);
 
 /* --------------------------------------------------------------------------------------------
