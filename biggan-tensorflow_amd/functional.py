@@ -86,6 +86,27 @@ def image_tiles_u8(x, grid, gh, gw, tile0=0):
     return grid
 
 
+def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
+    """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
+    the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns
+    and x / 127.5 - 1, bit-identical to data.ImageData.image_processing (csrc/input.hip).  ``raw_bytes`` (default: all
+    of raw) bounds what the kernel may read: an entry that does not fit gives a NaN image.  ``out``: write into this
+    contiguous fp32 tensor instead of a new one.  No autograd."""
+    if raw.dtype != torch.uint8 or raw.dim() != 1:
+        raise RuntimeError("image_batch_u8: raw must be uint8 [bytes], got %s %s" % (raw.dtype, tuple(raw.shape)))
+    if table.dtype != torch.int32 or tuple(table.shape) != (n, 8):
+        raise RuntimeError("image_batch_u8: table must be int32 [%d,8], got %s %s" % (n, table.dtype, tuple(table.shape)))
+    nb = raw.numel() if raw_bytes is None else int(raw_bytes)
+    if nb > raw.numel():
+        raise RuntimeError("image_batch_u8: raw_bytes %d > the %d bytes of raw" % (nb, raw.numel()))
+    if out is None:
+        out = torch.empty((n, size, size, channels), dtype=torch.float32, device=raw.device)
+    elif tuple(out.shape) != (n, size, size, channels):
+        raise RuntimeError("image_batch_u8: out must be [%d,%d,%d,%d], got %s" % (n, size, size, channels, tuple(out.shape)))
+    check(lib().bg_image_batch_u8(hip.ptr(raw), nb, i32(table), n, size, channels, f32(out), stream()))
+    return out
+
+
 def weight_packs(w):
     """(pack_p, pack_t): the bf16 K-contiguous copies of a conv / transposed-conv kernel [k,k,A,B]: pack_p keeps the
     variable's order [k*k][A][B], pack_t is [k*k][B][A].  Spectrally normalised kernels get them from the

@@ -12,7 +12,7 @@ import torch
 
 _LIB = None
 LIB_NAME = "libbiggan_hip.so"
-ABI_VERSION = 9
+ABI_VERSION = 10
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 PAD_REFLECT, PAD_ZERO = 0, 1
@@ -233,6 +233,7 @@ SIGNATURES = {
     "bg_recon_loss_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_double, _P, _P, c_int, c_int, c_int, c_int, c_int,
                                   _P]),
     "bg_image_tiles_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
+    "bg_image_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

@@ -1430,10 +1430,11 @@ class BigGAN(GANBase):
             if loader is not None:
                 loader.close()
 
-    def open_dataset(self, root="./dataset"):
+    def open_dataset(self, root="./dataset", device_preprocess=None):
         """BigGAN.py:195-212, 768-787: the files of ``<root>/<--dataset>/`` (+ ``--label_file``) behind the
         reference's shuffle / decode / resize / flip / batch pipeline; None when that folder does not exist
-        (the training loop then runs on synthetic batches)."""
+        (the training loop then runs on synthetic batches).  ``device_preprocess``: BatchLoader's switch (None: resize,
+        flip and normalise on the GPU unless BG_DEVICE_INPUT=0)."""
         from . import data as D
         folder = os.path.join(root, self.dataset_name)
         if not os.path.isdir(folder):
@@ -1446,7 +1447,7 @@ class BigGAN(GANBase):
         print("# dataset number:", len(files))
         image_data = D.ImageData(self.img_size, self.c_dim, True, self.args.random_flip, seed=1234 + self.rank)
         return D.BatchLoader(files, labels if self.acgan else None, self.batch_size, image_data, self.device,
-                             seed=4321, rank=self.rank, world=self.world)
+                             seed=4321, rank=self.rank, world=self.world, device_preprocess=device_preprocess)
 
     def _train_loop(self, data_fn, iterations, resume, samples=False):
         could_load, checkpoint_counter = (self.load(self.checkpoint_dir) if resume else (False, 0))

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 9
+#define BG_ABI_VERSION 10
 
 enum { BG_OK = 0, BG_ERR_ARG = 1, BG_ERR_LAUNCH = 2, BG_ERR_UNSUPPORTED = 3 };
 enum { BG_PAD_REFLECT = 0, BG_PAD_ZERO = 1 };
@@ -711,6 +711,30 @@ int bg_recon_loss_bwd(const float* y, const float* target, const int32_t* off_y,
  *   bit-identical to the numpy host path; +-inf clamp, NaN writes 0.
  * ------------------------------------------------------------------------------------------ */
 int bg_image_tiles_u8(const void* x, int x_dtype, int n, int H, int W, int C, uint8_t* grid, int gh, int gw, int tile0,
+                      void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Input batches (utils.py:12-38 image_processing, BigGAN.py:768-787; csrc/input.hip).
+ * bg_image_batch_u8: the decoded pixels of n images -> the training batch out [n,S,S,C] fp32 in [-1,1], C in {1,3,4}.
+ *   raw    one packed uint8 buffer of raw_bytes bytes; image i is [h,w,C] row-major at table[i].offset, a multiple of 16
+ *   table  n entries of 32 bytes on the device (data.pack_batch builds them as int32 [n,8], little-endian):
+ *            word 0-1 offset (int64)   2 h   3 w   4 flip (0 / 1)   5 scale_y   6 scale_x (fp32 bits)   7 reserved (0)
+ *          with scale = (float)((double)n_in / (double)S), computed on the host
+ *   Per element, each step one correctly rounded fp32 operation (bit-identical to the numpy host path, no fma):
+ *     src = i * scale, lo = floor(src), hi = min(lo + 1, n_in - 1), f = src - lo;
+ *     top = a * (1 - fx) + b * fx, bot likewise; v = top * (1 - fy) + bot * fy; out = v / 127.5f - 1.0f.
+ *   flip mirrors the output columns: out[:, x] = resized[:, S - 1 - x].
+ *   The library cannot read the table: an entry with h or w < 1, an offset that is negative or no multiple of 16, or an
+ *   extent offset + h*w*C > raw_bytes reads nothing and fills its image with NaN.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct BgImageEntry {
+    int64_t offset;
+    int32_t h, w;
+    int32_t flip;
+    float   scale_y, scale_x;
+    int32_t reserved;
+} BgImageEntry;
+int bg_image_batch_u8(const uint8_t* raw, int64_t raw_bytes, const BgImageEntry* table, int n, int S, int C, float* out,
                       void* stream);
 
 /* --------------------------------------------------------------------------------------------
