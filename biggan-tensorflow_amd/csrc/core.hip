@@ -134,6 +134,38 @@ int bg_png_unfilter(const unsigned char* raw, int h, int stride, int bpp, unsign
     return BG_OK;
 }
 
+// Host helper of the event-file writer (trainlog.py): CRC-32C, slicing-by-8 over tables built on first use.
+uint32_t bg_crc32c(const void* data, size_t n, uint32_t crc) {
+    struct Tables {
+        uint32_t t[8][256];
+        Tables() {
+            for (uint32_t i = 0; i < 256; ++i) {
+                uint32_t c = i;
+                for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
+                t[0][i] = c;
+            }
+            for (uint32_t i = 0; i < 256; ++i)
+                for (int j = 1; j < 8; ++j) t[j][i] = (t[j - 1][i] >> 8) ^ t[0][t[j - 1][i] & 255u];
+        }
+    };
+    static const Tables T;
+    const unsigned char* p = static_cast<const unsigned char*>(data);
+    uint32_t c = ~crc;
+    if (!p) return crc;
+    while (n >= 8) {
+        uint32_t lo, hi;
+        memcpy(&lo, p, 4);
+        memcpy(&hi, p + 4, 4);
+        lo ^= c;
+        c = T.t[7][lo & 255u] ^ T.t[6][(lo >> 8) & 255u] ^ T.t[5][(lo >> 16) & 255u] ^ T.t[4][lo >> 24] ^
+            T.t[3][hi & 255u] ^ T.t[2][(hi >> 8) & 255u] ^ T.t[1][(hi >> 16) & 255u] ^ T.t[0][hi >> 24];
+        p += 8;
+        n -= 8;
+    }
+    while (n--) c = (c >> 8) ^ T.t[0][(c ^ *p++) & 255u];
+    return ~c;
+}
+
 void bg_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(bg::g_prof_mu);
     bg::g_prof_on = on != 0;

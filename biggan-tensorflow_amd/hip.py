@@ -6,7 +6,8 @@ computes on the host.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32,
+                    c_void_p)
 
 import torch
 
@@ -76,6 +77,11 @@ class BgAttn16Desc(Structure):
     _fields_ = [(n, c_int32) for n in ("B", "N", "Nk", "d", "dv", "reserved")] + \
                [(n, c_int64) for n in ("ldq", "sq", "ldk", "sk", "ldv", "sv", "ldo", "so",
                                        "ldg", "sg", "lddq", "sdq", "lddk", "sdk", "lddv", "sdv")]
+
+
+class BgHistItem(Structure):
+    """One variable of bg_var_hist_plan: a device view of n fp32 elements at any 4-byte offset."""
+    _fields_ = [("x", c_void_p), ("n", c_int64)]
 
 
 _P = c_void_p
@@ -234,6 +240,12 @@ SIGNATURES = {
                                   _P]),
     "bg_image_tiles_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
     "bg_image_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
+    "bg_crc32c": (c_uint32, [c_char_p, c_size_t, c_uint32]),
+    "bg_var_hist_plan_chunks": (c_int, [_P, c_int, _P]),               # (BgHistItem*, n, int* n_chunks)
+    "bg_var_hist_plan_bytes": (c_size_t, [c_int, c_int]),
+    "bg_var_hist_plan": (c_int, [_P, c_int, _P, c_size_t]),
+    "bg_var_hist_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "bg_var_hist": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

@@ -103,6 +103,7 @@ def main(argv=None):
     gan = BigGAN(args)
     gan.build_model()
     if args.phase == 'train':
+        gan.log_events = True                             # loss scalars and variable histograms into <log_dir>/<model_dir>/
         gan.train(samples=True)                           # sample grids every --print_freq iterations (BigGAN.py:1125)
         print(" [*] Training finished!")
     elif args.phase == 'test':

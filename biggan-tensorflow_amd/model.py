@@ -45,6 +45,8 @@ class GANBase(object):
         self.virtual_batches = args.virtual_batches
         self.print_freq = args.print_freq
         self.save_freq = args.save_freq
+        self.histogram_freq = int(getattr(args, "histogram_freq", 0) or 0)
+        self.log_events = False               # train() writes the event file of trainlog.py only when this is set
         self.img_size = args.img_size
         self.bn_options = {"type": args.bn_type, "momentum": args.bn_momentum}       # GANBase.py:39-47
         if self.bn_options["type"] == 'batch_renorm':
@@ -1418,15 +1420,19 @@ class BigGAN(GANBase):
         latest checkpoint of ``checkpoint_dir`` if there is one, print the losses every iteration, save
         every ``save_freq`` iterations of an epoch (rank 0 writes; replicas are identical).  ``samples``: write the
         sample grids of ``save_samples`` every ``print_freq`` iterations of an epoch (BigGAN.py:1125; the command line
-        turns it on, programmatic callers opt in)."""
+        turns it on, programmatic callers opt in).  With ``self.log_events`` set (the command line sets it, programmatic
+        callers opt in) rank 0 writes a TensorBoard event file under ``<log_dir>/<model_dir>/`` (BigGAN.py:1019): every
+        loss as a scalar each iteration and, every ``histogram_freq`` iterations, a histogram of every variable
+        (trainlog.py)."""
         loader = None
         if data_fn is None:
             loader = self.open_dataset()
             if loader is not None:
                 data_fn = lambda: next(loader)                                    # noqa: E731
         try:
-            return self._train_loop(data_fn, iterations, resume, samples)
+            return self._train_loop(data_fn, iterations, resume, samples, bool(getattr(self, "log_events", False)))
         finally:
+            self._close_log()
             if loader is not None:
                 loader.close()
 
@@ -1449,8 +1455,35 @@ class BigGAN(GANBase):
         return D.BatchLoader(files, labels if self.acgan else None, self.batch_size, image_data, self.device,
                              seed=4321, rank=self.rank, world=self.world, device_preprocess=device_preprocess)
 
-    def _train_loop(self, data_fn, iterations, resume, samples=False):
+    def _open_log(self):
+        """A new event file per run, resumed runs included (tf.summary.FileWriter, BigGAN.py:1019).  Rank 0 only: replicas
+        are identical, and the histogram kernel involves no collective."""
+        from . import trainlog
+        self._log_writer = trainlog.EventWriter(os.path.join(self.log_dir, self.model_dir))
+        self._log_hists = trainlog.VariableHistograms(self.store, self.device) if self.histogram_freq else None
+
+    def _close_log(self):
+        writer = getattr(self, "_log_writer", None)
+        self._log_writer = self._log_hists = None
+        if writer is not None:
+            writer.close()
+
+    def _log_iteration(self, vals):
+        """Summaries of the iteration that just ran; its step is the reference's counter before the increment.  Reads
+        variables and the losses already fetched: no draw from ``self.gen``, nothing written, outside the HIP graphs."""
+        step = self.counter - 1
+        self._log_writer.add_scalars(step, vals)                                       # utils.py:291-294
+        if self._log_hists is not None and step % self.histogram_freq == 0:           # BigGAN.py:1100-1101
+            self._wait_params()               # (sharded update: the all-gather of the new parameters may be in flight)
+            self._log_writer.add_histograms(step, self._log_hists.compute())
+        if self.counter % self.print_freq == 0:
+            self._log_writer.flush()
+
+    def _train_loop(self, data_fn, iterations, resume, samples=False, log=False):
         could_load, checkpoint_counter = (self.load(self.checkpoint_dir) if resume else (False, 0))
+        self._log_writer = self._log_hists = None
+        if log and self.rank == 0:
+            self._open_log()
         if could_load:
             start_epoch = int(checkpoint_counter / self.iterations_per_epoch)
             start_batch_id = checkpoint_counter - start_epoch * self.iterations_per_epoch
@@ -1482,14 +1515,20 @@ class BigGAN(GANBase):
                     print_str += ", " + name + ": %.4f" % val
                 if self.rank == 0:
                     print(print_str, flush=True)
+                if self._log_writer is not None:
+                    self._log_iteration(vals)
                 if self.d_save_recon_samples and self.counter % self.print_freq == 0 and self.rank == 0:
                     self.save_recon_samples(epoch, idx + 1)                            # BigGAN.py:1050-1074
                 if (idx + 1) % self.save_freq == 0:                                   # BigGAN.py:1121-1122
                     self.save(self.checkpoint_dir, self.counter)
+                    if self._log_writer is not None:
+                        self._log_writer.flush()
                 if samples and (idx + 1) % self.print_freq == 0:                      # BigGAN.py:1125
                     self.save_samples(epoch, idx + 1)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
+            if self._log_writer is not None:
+                self._log_writer.flush()
 
     def save_recon_samples(self, epoch, idx):
         """--d_save_recon_samples (BigGAN.py:1050-1074): the targets and the reconstructions of the last D step as image

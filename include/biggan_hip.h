@@ -48,6 +48,11 @@ const char* bg_target_arch(void);
  * image on the CPU.  raw: h rows of 1 filter byte + stride bytes (the inflated IDAT stream); out: h * stride. */
 int bg_png_unfilter(const unsigned char* raw, int h, int stride, int bpp, unsigned char* out);
 
+/* Host-side helper of the event-file writer (trainlog.py; TF's lib/io/record_writer.cc frames every record with two
+ * of these): CRC-32C (Castagnoli, reflected polynomial 0x82F63B78, initial value and final xor 0xFFFFFFFF) of n bytes.
+ * crc is the CRC of the bytes before them (0 to start), so that a buffer can be fed in pieces. */
+uint32_t bg_crc32c(const void* data, size_t n, uint32_t crc);
+
 /* --------------------------------------------------------------------------------------------
  * Convolution geometry shared by conv / transposed conv (ops.py:49-139).
  *   conv   : x[N,H,W,Cin]  -> y[N,Ho,Wo,Cout],  Ho = (H + pad_lo + pad_hi - k)/stride + 1
@@ -736,6 +741,38 @@ typedef struct BgImageEntry {
 } BgImageEntry;
 int bg_image_batch_u8(const uint8_t* raw, int64_t raw_bytes, const BgImageEntry* table, int n, int S, int C, float* out,
                       void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Variable histograms (utils.py:322-333 tf.summary.histogram of every global variable; csrc/varhist.hip).
+ * One call histograms every variable of the model by the rule of TF 1.x's histogram.cc:
+ *   counts[i][b] = number of finite elements x of item i with upper_bound(limits, (double)x) == b, i.e. b is the first
+ *                  index whose limit is strictly greater than x, compared in double against the uploaded table;
+ *   stats[i]     = min, max, num, sum, sum_squares over the finite elements (sums in double) and, in stats[i][5], the
+ *                  number of non-finite elements (NaN, +-Inf), which enter neither the buckets nor the statistics;
+ *                  without a finite element min = DBL_MAX and max = -DBL_MAX (Histogram::Clear()).
+ *   counts, min, max and num are exact; everything is bit-identical from run to run (bucket counts are merged with
+ *   integer atomics, the sums through per-chunk partial rows in the workspace, added in a fixed order).
+ * The item table does not change after VariableStore.pack(), so it is compiled once, on the host, into a plan that the
+ * caller uploads and keeps (no allocation and no host-to-device copy inside bg_var_hist):
+ *   bg_var_hist_plan_chunks  number of chunks of the plan (no chunk crosses an item boundary); BG_ERR_ARG for
+ *                            n_items < 1, an item with n < 0 or n >= 2^32, a NULL or not 4-byte aligned pointer
+ *   bg_var_hist_plan_bytes   size of the plan
+ *   bg_var_hist_plan         writes the plan into a HOST buffer (8-byte aligned); items are device views at any 4-byte
+ *                            offset, adjacent arena segments included
+ *   bg_var_hist              plan: the DEVICE copy; limits: n_limits doubles on the device, ascending, odd count with
+ *                            0.0 in the middle (TF's table has 1551), n_limits <= 2048; counts [n_items][n_limits] uint32
+ *                            (zeroed by the call); stats [n_items][6] double; ws of bg_var_hist_workspace_bytes
+ * ------------------------------------------------------------------------------------------ */
+typedef struct BgHistItem {
+    const float* x;
+    int64_t      n;
+} BgHistItem;
+int    bg_var_hist_plan_chunks(const BgHistItem* items, int n_items, int* n_chunks);
+size_t bg_var_hist_plan_bytes(int n_items, int n_chunks);
+int    bg_var_hist_plan(const BgHistItem* items, int n_items, void* plan, size_t plan_bytes);
+size_t bg_var_hist_workspace_bytes(int n_items, int n_chunks);
+int    bg_var_hist(const void* plan, int n_items, int n_chunks, const double* limits, int n_limits, uint32_t* counts,
+                   double* stats, void* ws, size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
