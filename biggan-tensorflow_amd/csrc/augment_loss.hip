@@ -656,7 +656,7 @@ int bg_diffaugment_fwd(const float* x, float* y, const float* u_b, const float* 
     DaArgs a{u_b, u_s, u_c, t_x, t_y, o_x, o_y, N, S, C, policy};
     const int64_t px = (int64_t)S * S;
     if (policy & 1) {
-        if (hipMemsetAsync(mean_ws, 0, sizeof(double) * N, s) != hipSuccess) {
+        if (zero_async(mean_ws, sizeof(double) * N, s) != hipSuccess) {
             set_error("bg_diffaugment_fwd: memset failed");
             return BG_ERR_LAUNCH;
         }
@@ -688,7 +688,7 @@ int bg_diffaugment_bwd(const float* dy, float* dx, const float* u_s, const float
     DaArgs a{nullptr, u_s, u_c, t_x, t_y, o_x, o_y, N, S, C, policy};
     const int64_t px = (int64_t)S * S;
     if (policy & 1) {
-        if (hipMemsetAsync(mean_ws, 0, sizeof(double) * N, s) != hipSuccess) {
+        if (zero_async(mean_ws, sizeof(double) * N, s) != hipSuccess) {
             set_error("bg_diffaugment_bwd: memset failed");
             return BG_ERR_LAUNCH;
         }
@@ -821,7 +821,7 @@ int bg_gp_penalty(const float* g, int N, int64_t per, double count_global, float
                   float* v, void* stream) {
     BG_REQUIRE(g && ws && loss && v && N > 0 && per > 0 && count_global > 0, "bg_gp_penalty: bad argument");
     hipStream_t st = as_stream(stream);
-    if (hipMemsetAsync(ws, 0, sizeof(double) * 2 * (size_t)N, st) != hipSuccess) {
+    if (zero_async(ws, sizeof(double) * 2 * (size_t)N, st) != hipSuccess) {
         set_error("bg_gp_penalty: memset failed");
         return BG_ERR_LAUNCH;
     }

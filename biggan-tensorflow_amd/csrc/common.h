@@ -59,6 +59,22 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh /* >= 4 floats
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
+// Zeroing of an accumulator of 4- or 8-byte elements as a KERNEL, so that a stream capture records a kernel node.
+// (hipMemsetAsync nodes of a few bytes at 4-byte-aligned addresses - the bias gradients' slots of a flat arena - came back
+// with garbage in some elements when a captured training step was replayed in a process that had run other work.)
+__global__ static void zero_words_kernel(uint32_t* __restrict__ p, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+}
+static inline hipError_t zero_async(void* p, size_t bytes, hipStream_t s) {
+    if (bytes == 0) return hipSuccess;
+    if ((bytes & 3) || (reinterpret_cast<uintptr_t>(p) & 3)) return hipMemsetAsync(p, 0, bytes, s);
+    const size_t n = bytes >> 2;
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s,
+                       static_cast<uint32_t*>(p), n);
+    return hipGetLastError();
+}
+
 // profiling hooks (core.hip): HIP events on the launch stream around one C-ABI call of a GEMM-family op.
 //   flops / bytes = the ALGORITHMIC work of the call (each activation once in its stored type,
 //   weights once, weight gradients written once in fp32); prof_kernel() names the kernel instantiation the launcher

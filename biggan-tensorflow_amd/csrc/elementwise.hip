@@ -2220,7 +2220,7 @@ struct PartialRowsFn {
 };
 
 int launch_partial_colsum(const float* part, double* sums, int64_t rows, int cols, hipStream_t s) {
-    if (hipMemsetAsync(sums, 0, sizeof(double) * (size_t)cols, s) != hipSuccess) {
+    if (zero_async(sums, sizeof(double) * (size_t)cols, s) != hipSuccess) {
         set_error("partial column sums: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2255,7 +2255,7 @@ int bg_bn_finalize(const double* sums, double count, float eps, float momentum, 
 
 int bg_chan_dots3(const float* p, const float* q, const float* r, double* sums, int64_t rows, int C, void* stream) {
     BG_REQUIRE(p && q && sums && rows > 0 && C > 0, "bg_chan_dots3: bad argument");
-    if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * (size_t)C, as_stream(stream)) != hipSuccess) {
+    if (zero_async(sums, sizeof(double) * 3 * (size_t)C, as_stream(stream)) != hipSuccess) {
         set_error("bg_chan_dots3: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2353,7 +2353,7 @@ int bg_bn_apply_act_bwd_reduce(const float* x, const float* dy, const float* mea
                                int N, int HW, int C, void* stream) {
     BG_REQUIRE(x && dy && mean && rstd && gamma && beta && part && N > 0 && HW > 0 && C > 0,
                "bg_bn_apply_act_bwd_reduce: bad argument");
-    if (hipMemsetAsync(part, 0, sizeof(float) * 3 * (size_t)N * C, as_stream(stream)) != hipSuccess) {
+    if (zero_async(part, sizeof(float) * 3 * (size_t)N * C, as_stream(stream)) != hipSuccess) {
         set_error("bg_bn_apply_act_bwd_reduce: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2482,7 +2482,7 @@ int bg_prelu_bwd(const float* x, const float* dy, const float* alpha, float* dx,
 
 int bg_bias_grad(const float* dy, float* db, int64_t rows, int C, void* stream) {
     BG_REQUIRE(dy && db && rows > 0 && C > 0, "bg_bias_grad: bad argument");
-    if (hipMemsetAsync(db, 0, sizeof(float) * (size_t)C, as_stream(stream)) != hipSuccess) {
+    if (zero_async(db, sizeof(float) * (size_t)C, as_stream(stream)) != hipSuccess) {
         set_error("bg_bias_grad: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2595,7 +2595,7 @@ int bg_maxpool2_gather(const float* x, const float* t, float* y, int N, int H, i
 int bg_prelu_tangent_dalpha(const float* x, const float* xdot, const float* dy, float* dalpha, int64_t rows, int C,
                             void* stream) {
     BG_REQUIRE(x && xdot && dy && dalpha && rows > 0 && C > 0, "bg_prelu_tangent_dalpha: bad argument");
-    if (hipMemsetAsync(dalpha, 0, sizeof(float) * (size_t)C, as_stream(stream)) != hipSuccess) {
+    if (zero_async(dalpha, sizeof(float) * (size_t)C, as_stream(stream)) != hipSuccess) {
         set_error("bg_prelu_tangent_dalpha: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2710,7 +2710,7 @@ int bg_spectral_norm_fwd(const float* w, const float* u_in, float* u_out, float*
     double* scr = reinterpret_cast<double*>(ws);
     double* uraw = scr + 4;
     float* vraw = reinterpret_cast<float*>(uraw + cols);
-    if (hipMemsetAsync(scr, 0, bg_spectral_norm_workspace_bytes(rows, cols), s) != hipSuccess) {
+    if (zero_async(scr, bg_spectral_norm_workspace_bytes(rows, cols), s) != hipSuccess) {
         set_error("bg_spectral_norm_fwd: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2743,7 +2743,7 @@ int bg_spectral_norm_bwd(const float* g_wnorm, const float* w_norm, const float*
                "bg_spectral_norm_bwd: pointers must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     float* scr = reinterpret_cast<float*>(ws);
-    if (hipMemsetAsync(scr, 0, 16, s) != hipSuccess) {
+    if (zero_async(scr, 16, s) != hipSuccess) {
         set_error("bg_spectral_norm_bwd: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2776,7 +2776,7 @@ static int sn_batch_phases(const BgSnItem* items_dev, int n_items, void* ws, siz
     hipStream_t s = as_stream(stream);
     char* w8 = reinterpret_cast<char*>(ws);
     if (phase != BG_SN_NORMALIZE) {
-        if (hipMemsetAsync(ws, 0, ws_bytes, s) != hipSuccess) {
+        if (zero_async(ws, ws_bytes, s) != hipSuccess) {
             set_error("%s: memset failed", who);
             return BG_ERR_LAUNCH;
         }
@@ -2816,7 +2816,7 @@ int bg_spectral_norm_batch_bwd(const BgSnItem* items_dev, int n_items, const uin
     SnMask en, acc;
     sn_masks(enable_mask, n_items, &en, true);
     sn_masks(accumulate_mask, n_items, &acc, false);
-    if (hipMemsetAsync(ws, 0, sizeof(double) * (size_t)n_items, s) != hipSuccess) {
+    if (zero_async(ws, sizeof(double) * (size_t)n_items, s) != hipSuccess) {
         set_error("bg_spectral_norm_batch_bwd: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -2961,7 +2961,7 @@ int bg_bn_apply_act_bwd_reduce_t(const void* x, int x_dtype, const void* dy, int
                                  const float* alpha, float* part, int N, int HW, int C, void* stream) {
     BG_REQUIRE(x && dy && mean && rstd && gamma && beta && part && N > 0 && HW > 0 && C > 0 && BG_DT_OK(x_dtype) &&
                    BG_DT_OK(y_dtype), "bg_bn_apply_act_bwd_reduce_t: bad argument");
-    if (hipMemsetAsync(part, 0, sizeof(float) * 3 * (size_t)N * C, as_stream(stream)) != hipSuccess) {
+    if (zero_async(part, sizeof(float) * 3 * (size_t)N * C, as_stream(stream)) != hipSuccess) {
         set_error("bg_bn_apply_act_bwd_reduce_t: memset failed");
         return BG_ERR_LAUNCH;
     }
@@ -3060,7 +3060,7 @@ int bg_prelu_bwd_t(const void* x, int x_dtype, const void* dy, int y_dtype, cons
 
 int bg_bias_grad_t(const void* dy, int dtype, float* db, int64_t rows, int C, void* stream) {
     BG_REQUIRE(dy && db && rows > 0 && C > 0 && BG_DT_OK(dtype), "bg_bias_grad_t: bad argument");
-    if (hipMemsetAsync(db, 0, sizeof(float) * (size_t)C, as_stream(stream)) != hipSuccess) {
+    if (zero_async(db, sizeof(float) * (size_t)C, as_stream(stream)) != hipSuccess) {
         set_error("bg_bias_grad_t: memset failed");
         return BG_ERR_LAUNCH;
     }

@@ -322,7 +322,7 @@ int bg_var_hist(const void* plan, int n_items, int n_chunks, const double* limit
     const VhItem* items = reinterpret_cast<const VhItem*>(plan);
     const VhChunk* chunks = reinterpret_cast<const VhChunk*>(items + n_items);
     double* part = reinterpret_cast<double*>(ws);
-    if (hipMemsetAsync(counts, 0, (size_t)n_items * n_limits * sizeof(uint32_t), s) != hipSuccess) {
+    if (zero_async(counts, (size_t)n_items * n_limits * sizeof(uint32_t), s) != hipSuccess) {
         set_error("bg_var_hist: cannot zero counts");
         (void)hipGetLastError();
         return BG_ERR_LAUNCH;

@@ -2522,6 +2522,53 @@ class SigmoidCeLossFn(Function):
         return None, out, None, None, None, None
 
 
+class LabelLossFn(Function):
+    """cls_loss_fn(type, w)(truth, answer) * loss_weight for 'euclidean' and the sliced "N-type,M-type,..." specs
+    (utils.py:339-375): per-slice fp64 sums of this rank's rows, one all-reduce of that buffer, then the loss and
+    dlogits = d(global loss)/d(local logits) - the convention of SigmoidCeLossFn.  ``slices`` int32 [S, 2] and
+    ``col_slice`` int32 [n] are the device-resident slice description of include/biggan_hip.h."""
+
+    @staticmethod
+    def forward(ctx, truth, logits, weights, slices, col_slice, loss_weight, reduce_fn, world):
+        truth, logits = _c(truth), _c(logits)
+        B, n = logits.shape
+        S = slices.shape[0]
+        if truth.shape != logits.shape or weights.numel() != n or col_slice.numel() != n:
+            raise ValueError("label loss: truth %s, logits %s, %d weights, %d mapped columns"
+                             % (tuple(truth.shape), tuple(logits.shape), weights.numel(), col_slice.numel()))
+        dev = logits.device
+        L = lib()
+        sums = zeros(S, torch.float64, dev)
+        check(L.bg_label_loss_sums(f32(logits), f32(truth), f32(weights), i32(slices), i32(col_slice), hip.ptr(sums),
+                                   B, n, S, stream()))
+        if reduce_fn is not None:
+            reduce_fn(sums)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dl = torch.empty_like(logits)
+        check(L.bg_label_loss_finish(f32(logits), f32(truth), f32(weights), i32(slices), i32(col_slice), hip.ptr(sums),
+                                     float(B * world), float(loss_weight), f32(loss), f32(dl), B, n, S, stream()))
+        ctx.dl = dl
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _c(g)
+        out = torch.empty_like(ctx.dl)
+        check(lib().bg_scale_dev(f32(ctx.dl), f32(g), f32(out), out.numel(), stream()))
+        return None, out, None, None, None, None, None, None
+
+
+def gather_rows(table, idx):
+    """out[b, :] = table[idx[b], :], bit-exact: ``table`` fp32 [rows, n] and ``idx`` int64 [B] on the device (the draw of
+    the generator's labels from the dataset's label table, BigGAN.py:1447-1455).  No gradient."""
+    if idx.dtype != torch.int64 or table.dim() != 2:
+        raise ValueError("gather_rows: table [rows, n] fp32 and idx int64 [B], got %s %s" % (tuple(table.shape), idx.dtype))
+    rows, n = table.shape
+    out = torch.empty((idx.numel(), n), dtype=torch.float32, device=table.device)
+    check(lib().bg_gather_rows(f32(table), hip.ptr(_c(idx)), f32(out), rows, n, idx.numel(), stream()))
+    return out
+
+
 class OrthoCosineRegFn(Function):
     """orthogonal_regularizer(scale, 'ortho_cosine')(w) (utils.py:180-235): scale * l2_loss(R).
     The weight gradient dW = W (dA + dA^T) is produced in backward."""

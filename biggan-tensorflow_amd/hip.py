@@ -190,6 +190,9 @@ SIGNATURES = {
     "bg_gan_loss_grad": (c_int, [c_int, c_int, _P, _P, _P, _P, c_double, c_double, c_float, _P, _P, _P, c_int, c_int,
                                  _P]),
     "bg_sigmoid_ce": (c_int, [_P, _P, _P, c_float, _P, _P, c_int, c_int, _P]),
+    "bg_label_loss_sums": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "bg_label_loss_finish": (c_int, [_P, _P, _P, _P, _P, _P, c_double, c_float, _P, _P, c_int, c_int, c_int, _P]),
+    "bg_gather_rows": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "bg_ortho_cosine_fwd_bwd": (c_int, [_P, c_float, _P, _P, c_int, _P]),
     "bg_ortho_identity_fwd_bwd": (c_int, [_P, c_float, _P, _P, c_int, _P]),
     "bg_gemv_rows": (c_int, [_P, _P, _P, c_int, c_int, _P]),

@@ -23,7 +23,8 @@ from .ops import (fully_connected, resblock_up_condition, resblock_down, resbloc
                   prelu, relu, lrelu, tanh, alpha_helper_tanh, alpha_mask, global_sum_pooling, discriminator_loss,
                   generator_loss, glu, up_sample)
 from .DiffAugment import DiffAugment, draw as draw_augment
-from .utils import orthogonal_regularizer, orthogonal_regularizer_fc, l2_regularizer, round_up, cls_loss_fn
+from .utils import (orthogonal_regularizer, orthogonal_regularizer_fc, l2_regularizer, round_up, cls_loss_fn,
+                    parse_cls_loss_type)
 
 
 def _meta_2d(B, width):
@@ -170,6 +171,7 @@ class BigGAN(GANBase):
         self.sample_gen = torch.Generator(device="cpu")
         self.sample_gen.manual_seed((int(self.static_sample_seed) + 1) % (1 << 63))
         self.labels = None                     # the dataset's label table (open_dataset); None: synthetic one-hots
+        self.label_table = None                # the same table as a device fp32 [rows, n_labels] (draw_labels)
         self._static_set = None                # (z, class vectors) of the static sample set, drawn on first use
         self.recon_plan = self._recon_plan()
         self.deep = args.deep                                                          # BigGAN.py:20
@@ -189,6 +191,7 @@ class BigGAN(GANBase):
         self.virtual_batches = max(int(args.virtual_batches), 1)
         if self.acgan:                                                                 # BigGAN.py:91-100
             self.cls_loss_type = args.cls_loss_type
+            parse_cls_loss_type(self.cls_loss_type, self.n_labels)     # utils.py:339-375: a bad spec fails here
             self.d_cls_loss_weight = args.d_cls_loss_weight
             self.g_cls_loss_weight = args.g_cls_loss_weight
             self.d_compat_use_sn_in_classification = args.d_compat_use_sn_in_classification
@@ -1072,7 +1075,7 @@ class BigGAN(GANBase):
         if z is None:
             z = self.sample_z(B)
         if self.acgan and cls_z is None:
-            cls_z = self.synthetic_labels(B)                                           # rnd_cls_feed_dict, BigGAN.py:1454
+            cls_z = self.draw_labels(B)                                                # rnd_cls_feed_dict, BigGAN.py:1454
         with torch.no_grad():
             fake = self.generator(z, cls_z, is_training=True)
         real_aug = DiffAugment(real, policy=self.da_policy, draws=draws_real, generator=self.gen)
@@ -1103,6 +1106,7 @@ class BigGAN(GANBase):
         if self.acgan:
             if labels is None:
                 raise ValueError("n_labels > 0: d_forward needs the labels of the real batch")
+            out["cls_z"] = cls_z                    # the generator's labels of this run (drawn or given)
             real_cls = d_out["cls"][:B]             # (a no-op slice when D ran on the real batch alone)
             d_cls = self._cls_loss()(labels, real_cls, self.d_cls_loss_weight, self._reduce_fn(), self.world)
             out["d_cls_loss"] = d_cls
@@ -1195,7 +1199,7 @@ class BigGAN(GANBase):
         if z is None:
             z = self.sample_z(B)
         if self.acgan and cls_z is None:
-            cls_z = self.synthetic_labels(B)
+            cls_z = self.draw_labels(B)
         fake = self.generator(z, cls_z, is_training=True)
         if after_generator is not None:
             after_generator()               # e.g. the deferred D update: must precede any use of the discriminator
@@ -1225,6 +1229,7 @@ class BigGAN(GANBase):
         if self.acgan:
             g_cls = self._cls_loss()(cls_z, d_out["cls"], self.g_cls_loss_weight, self._reduce_fn(), self.world)
             out["g_cls_loss"] = g_cls
+            out["cls_z"] = cls_z
             g_adv = Fn.AddFn.apply(g_adv, g_cls)
         out["g_adv"] = g_adv
         out["regs"] = ops.get_regularization_losses() if self.g_regularization_method != 'none' else []
@@ -1392,12 +1397,21 @@ class BigGAN(GANBase):
         return losses
 
     def synthetic_labels(self, B):
-        """Synthetic one-hot labels, uniform classes (the reference draws tags from its label file,
-        BigGAN.py:1446-1455)."""
+        """Synthetic one-hot labels, uniform classes: the labels of a run without a label file (with one, the reference
+        draws tags from it, BigGAN.py:1446-1455, and so does ``draw_labels``)."""
         idx = torch.randint(0, self.n_labels, (B,), device=self.device, generator=self.gen)
         lab = torch.zeros(B, self.n_labels, dtype=torch.float32, device=self.device)
         lab[torch.arange(B, device=self.device), idx] = 1.0
         return lab
+
+    def draw_labels(self, B):
+        """The generator's labels of one run of d_ops / g_ops (rnd_cls_feed_dict, BigGAN.py:1447-1455): ``B`` rows drawn
+        with replacement from the dataset's label table, on the device (randint on ``self.gen`` + bg_gather_rows: both are
+        captured, so a replayed graph draws fresh rows).  Without a table (synthetic data): ``synthetic_labels``."""
+        if self.label_table is None:
+            return self.synthetic_labels(B)
+        idx = torch.randint(0, self.label_table.shape[0], (B,), device=self.device, generator=self.gen)
+        return Fn.gather_rows(self.label_table, idx)
 
     def synthetic_batch(self, B=None):
         """Synthetic images U(-1,1) [B,S,S,c_dim] on the device (the reference reads PNG files)."""
@@ -1449,7 +1463,19 @@ class BigGAN(GANBase):
                                     ignore_missing=self.args.ignore_missing_labels, n_labels=self.n_labels, root=root)
         if self.acgan and labels is None:
             raise ValueError("--n_labels > 0 needs --label_file")
+        if self.acgan:
+            for path, row in zip(files, labels):
+                if len(row) != self.n_labels:
+                    raise ValueError("label file %s: %s has %d labels, --n_labels is %d"
+                                     % (self.args.label_file, os.path.basename(path), len(row), self.n_labels))
         self.labels = labels if self.acgan else None          # (the sampler draws its class vectors from these rows)
+        # ... and so does every training run of G, on the device (draw_labels)
+        # (one fp32 row per listed file, so --weight_file's copies repeat their row, as in the reference's self.labels)
+        self.label_table = None
+        if self.acgan:
+            import numpy as np
+            self.label_table = torch.from_numpy(np.asarray(labels, dtype=np.float32).reshape(len(labels), self.n_labels)
+                                                ).to(self.device)
         print("# dataset number:", len(files))
         image_data = D.ImageData(self.img_size, self.c_dim, True, self.args.random_flip, seed=1234 + self.rank)
         return D.BatchLoader(files, labels if self.acgan else None, self.batch_size, image_data, self.device,

@@ -137,18 +137,62 @@ def orthogonal_regularizer_fc(scale, type='ortho'):
 ##################################################################################
 # Class-label loss (utils.py:323-377)
 ##################################################################################
+CLS_LOSS_KINDS = {'logistic': 0, 'euclidean': 1}          # the kind codes of include/biggan_hip.h
+
+
+def parse_cls_loss_type(type, n_labels):
+    """The grammar of utils.py:339-375 -> [(kind, size), ...], one entry per column slice, sizes summing to
+    ``n_labels``.  'logistic' / 'euclidean' are one slice of every column; a spec containing ',' is a list of
+    ``size-type`` parts.  ValueError (naming the spec) for an unknown type - a ``size-type`` spec without a comma, such as
+    '10-logistic', is one: it takes the reference's "Invalid label loss type" branch -, for a part that is not
+    ``size-type`` with a size >= 1, and for sizes that do not sum to ``n_labels`` (the reference's tf.split fails)."""
+    spec = str(type)
+    if ',' not in spec:
+        if spec not in CLS_LOSS_KINDS:
+            raise ValueError("Invalid label loss type: " + spec)
+        return [(spec, int(n_labels))]
+    out = []
+    for part in spec.split(','):
+        pieces = part.split('-')
+        if len(pieces) != 2 or not pieces[0].strip().isdigit() or int(pieces[0]) < 1:
+            raise ValueError("Invalid label loss type: '%s' (part '%s' is not size-type)" % (spec, part))
+        if pieces[1] not in CLS_LOSS_KINDS:
+            raise ValueError("Invalid label loss type: '%s' (unknown type '%s')" % (spec, pieces[1]))
+        out.append((pieces[1], int(pieces[0])))
+    if sum(size for _, size in out) != int(n_labels):
+        raise ValueError("Invalid label loss type: the slice sizes of '%s' sum to %d, not to n_labels = %d"
+                         % (spec, sum(size for _, size in out), int(n_labels)))
+    return out
+
+
 def cls_loss_fn(type, cls_weights):
-    """utils.py:366-369: loss(truth, answer) = mean(sigmoid_cross_entropy_with_logits(truth, answer) * w).
-    ``cls_weights`` is a device tensor [n_labels] (or None = ones).  The returned callable takes an
-    optional ``loss_weight`` folded into the kernel (BigGAN.py:853,894)."""
-    if type != 'logistic':
-        if type == 'euclidean' or '-' in str(type):
-            raise NotImplementedError("cls_loss_type '%s' is outside the hot path (only 'logistic')" % type)
-        raise ValueError("Invalid label loss type: " + str(type))
+    """utils.py:339-375.  ``cls_weights`` is a tensor [n_labels]; the returned callable
+    ``loss(truth, answer, loss_weight, reduce_fn, world)`` folds ``loss_weight`` into the kernel (BigGAN.py:853,894).
+      'logistic'   mean(sigmoid_cross_entropy_with_logits(truth, answer) * w) over [B_global, n_labels] (bg_sigmoid_ce)
+      'euclidean'  ||(answer - truth) * w||_2 over the whole block: one norm, not a mean
+      'N-type,...' truth / answer / w split column-wise by the sizes; the sum of the slice losses, a logistic slice
+                   averaging over its own B_global * size elements
+    Everything but plain 'logistic' runs the two launches of csrc/labels.hip (functional.LabelLossFn).  Where a euclidean
+    slice's sum of squares is exactly 0 the gradient is 0 (TensorFlow's sqrt gradient gives NaN there)."""
+    import torch
+    if cls_weights is None and str(type) != 'logistic':
+        raise ValueError("cls_loss_type '%s' needs the label weights (their length is n_labels)" % type)
+    slices = parse_cls_loss_type(type, 0 if cls_weights is None else cls_weights.shape[0])
+    if str(type) == 'logistic':
+        def loss(truth, answer, loss_weight=1.0, reduce_fn=None, world=1):
+            from . import functional as Fn
+            return Fn.SigmoidCeLossFn.apply(truth, answer, cls_weights, loss_weight, reduce_fn, world)
+        return loss
+    # device-resident slice description, uploaded once: (kind, size) per slice and the slice index of every column
+    dev = cls_weights.device
+    slice_tab = torch.tensor([[CLS_LOSS_KINDS[k], size] for k, size in slices], dtype=torch.int32).to(dev)
+    col_slice = torch.tensor([i for i, (_, size) in enumerate(slices) for _ in range(size)], dtype=torch.int32).to(dev)
+    weights = cls_weights.to(torch.float32).contiguous()
 
     def loss(truth, answer, loss_weight=1.0, reduce_fn=None, world=1):
         from . import functional as Fn
-        return Fn.SigmoidCeLossFn.apply(truth, answer, cls_weights, loss_weight, reduce_fn, world)
+        return Fn.LabelLossFn.apply(truth, answer, weights, slice_tab, col_slice, loss_weight, reduce_fn, world)
+    loss.slices = slices
     return loss
 
 

@@ -632,6 +632,35 @@ int bg_sigmoid_ce(const float* logits, const float* truth, const float* weights,
                   float* dlogits, int B, int n, void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Labelled datasets (csrc/labels.hip): the sliced label loss of --cls_loss_type (utils.py:339-375) and the draw of the
+ * generator's fake labels from the dataset's label table (BigGAN.py:1447-1455).
+ *   A spec "N-type,M-type,..." (or a plain 'logistic' / 'euclidean' = one slice of all n columns) splits the columns of
+ *   logits / truth [B, n] and weights [n] into n_slices contiguous slices.  Device-resident description, uploaded once:
+ *     slices    int32 [n_slices, 2] = (kind, size), kind 0 = logistic, 1 = euclidean;
+ *     col_slice int32 [n]           = slice index of every column, non-decreasing.
+ *   With rows_global = the batch of all ranks, the loss is loss_weight * sum_s L_s,
+ *     logistic : L_s = sum_{b,j in s} sigmoid_cross_entropy_with_logits(t, x)[b,j] * w_j / (rows_global * size_s)
+ *     euclidean: L_s = sqrt(sum_{b,j in s} ((x[b,j] - t[b,j]) * w_j)^2)                 (one norm, not a mean)
+ * bg_label_loss_sums: sums[s] += this rank's share of the weighted cross-entropy sum (logistic) or of the sum of squares
+ *   (euclidean): fp32 terms, fp64 accumulators.  sums [n_slices] fp64 must be zero on entry; a data-parallel run
+ *   all-reduces it (SUM) between the two calls, so the square root is taken of the global sum of squares.
+ * bg_label_loss_finish: *loss_out = loss_weight * sum_s L_s (the same value on every rank) and the derivative of that
+ *   global loss with respect to the local logits,
+ *     dlogits[b,j] = loss_weight * w_j * (sigmoid(x) - t) / (rows_global * size_s)        logistic
+ *                  = loss_weight * w_j^2 * (x - t) / sqrt(sums[s])                        euclidean,
+ *   0 where sums[s] == 0 (TensorFlow's sqrt gradient gives NaN there).
+ * Neither call synchronises or reads anything back; both can be captured.
+ * bg_gather_rows: out[b, :] = table[idx[b], :], bit-exact; table fp32 [rows, n], idx int64 [B] on the device, any
+ *   n >= 1 and rows >= 1.  An index outside [0, rows) is clamped into the table.
+ * ------------------------------------------------------------------------------------------ */
+int bg_label_loss_sums(const float* logits, const float* truth, const float* weights, const int32_t* slices,
+                       const int32_t* col_slice, double* sums, int B, int n, int n_slices, void* stream);
+int bg_label_loss_finish(const float* logits, const float* truth, const float* weights, const int32_t* slices,
+                         const int32_t* col_slice, const double* sums, double rows_global, float loss_weight,
+                         float* loss_out, float* dlogits, int B, int n, int n_slices, void* stream);
+int bg_gather_rows(const float* table, const int64_t* idx, float* out, int rows, int n, int B, void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Orthogonal-cosine regulariser (utils.py:180-235) from the Gram matrix A = W^T W [c,c]
  * (computed with bg_gemm), using R[i,j] = (sum_k Ahat[i,k] - Ahat[i,j]) / sqrt(c-1):
  *   fwd: loss_accum[0] += scale/2 * sum R^2 ; bwd: dA (so that dW = W (dA + dA^T), via bg_gemm).
