@@ -9,7 +9,8 @@ resize, the flip and the normalisation on the device, bit-identical to ``ImageDa
 the reference implementation and the fallback (``BG_DEVICE_INPUT=0``, a CPU device, an array that is not uint8).
 
 Only what the reference's custom-dataset branch needs is provided: 8-bit non-interlaced PNG files (grey,
-RGB, palette, with or without alpha) and ``.npy`` arrays ``[H, W, C]`` uint8; ``mnist`` / ``cifar10`` (Keras
+RGB, palette, with or without alpha), 8-bit Huffman sequential JPEG files (``decode_jpeg``; recognised by content, as
+TensorFlow's decoder does) and ``.npy`` arrays ``[H, W, C]`` uint8; ``mnist`` / ``cifar10`` (Keras
 downloads) raise ``NotImplementedError``.
 """
 import csv
@@ -127,6 +128,357 @@ def decode_png(data, channels=3):
     raise ValueError("decode_png: channels must be 1, 3 or 4")
 
 
+# ------------------------------------------------------------------------------------------
+# JPEG (ITU-T T.81): 8-bit Huffman sequential (SOF0 / SOF1), 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0
+# ------------------------------------------------------------------------------------------
+# Integer arithmetic throughout, the one of libjpeg's defaults (slow-integer inverse DCT, "fancy" chroma upsampling,
+# 16-bit fixed-point colour transform).  ``decode_jpeg`` below is the specification: csrc/jpeg.hip (dequantisation,
+# IDCT, upsampling, colour on the device) and csrc/jpeg_entropy.hip (the marker walk and the Huffman decode, host C)
+# reproduce it exactly, and it is the fallback of both.
+JPEG_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20,
+                        13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52,
+                        45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63], np.int64)
+JPEG_SAMPLINGS = ((1, 1), (2, 1), (2, 2))               # luma h x v that the decoder takes; chroma is 1 x 1
+
+
+def _jpeg_parse(data):
+    """The marker walk up to the first scan: frame header, tables, restart interval, start of the entropy-coded data.
+    ValueError for malformed data, NotImplementedError for what ``decode_jpeg`` documents as unsupported."""
+    n = len(data)
+    if n < 2 or data[0] != 0xFF or data[1] != 0xD8:
+        raise ValueError("not a JPEG file")
+    qt, huff, frame, restart, pos = {}, {}, None, 0, 2
+    while True:
+        if pos + 2 > n:
+            raise ValueError("JPEG: truncated before the scan")
+        if data[pos] != 0xFF:
+            raise ValueError("JPEG: marker expected at byte %d" % pos)
+        m = data[pos + 1]
+        if m == 0xFF:                                   # fill byte
+            pos += 1
+            continue
+        pos += 2
+        if m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9 or m == 0x00:
+            raise ValueError("JPEG: marker %02X before the scan" % m)
+        if pos + 2 > n:
+            raise ValueError("JPEG: truncated segment")
+        ln = (data[pos] << 8) | data[pos + 1]
+        if ln < 2 or pos + ln > n:
+            raise ValueError("JPEG: truncated segment")
+        seg, end = pos + 2, pos + ln
+        if m == 0xDB:                                   # DQT
+            while seg < end:
+                pq, tq = data[seg] >> 4, data[seg] & 15
+                if pq > 1 or tq > 3 or seg + 1 + 64 * (pq + 1) > end:
+                    raise ValueError("JPEG: bad quantisation table")
+                seg += 1
+                t = np.zeros(64, np.int32)
+                for k in range(64):
+                    t[JPEG_ZIGZAG[k]] = ((data[seg] << 8) | data[seg + 1]) if pq else data[seg]
+                    seg += 1 + pq
+                qt[tq] = t
+        elif m == 0xC4:                                 # DHT
+            while seg < end:
+                if seg + 17 > end:
+                    raise ValueError("JPEG: bad Huffman table")
+                tc, th = data[seg] >> 4, data[seg] & 15
+                counts = [data[seg + 1 + i] for i in range(16)]
+                total = sum(counts)
+                if tc > 1 or th > 3 or total > 256 or seg + 17 + total > end:
+                    raise ValueError("JPEG: bad Huffman table")
+                table, code, k = {}, 0, seg + 17
+                for length in range(1, 17):
+                    for _ in range(counts[length - 1]):
+                        if code >= (1 << length):
+                            raise ValueError("JPEG: bad Huffman table")
+                        table[(length, code)] = data[k]
+                        code += 1
+                        k += 1
+                    code <<= 1
+                huff[(tc, th)] = table
+                seg = k
+        elif m == 0xDD:                                 # DRI
+            if ln != 4:
+                raise ValueError("JPEG: bad restart interval")
+            restart = (data[seg] << 8) | data[seg + 1]
+        elif m in (0xC0, 0xC1):                         # SOF0 / SOF1
+            if frame is not None or ln < 8:
+                raise ValueError("JPEG: bad frame header")
+            prec, h, w, nc = data[seg], (data[seg + 1] << 8) | data[seg + 2], (data[seg + 3] << 8) | data[seg + 4], data[seg + 5]
+            if prec != 8:
+                raise NotImplementedError("JPEG: %d-bit samples (8 only)" % prec)
+            if ln != 8 + 3 * nc or h < 1 or w < 1:
+                raise ValueError("JPEG: bad frame header")
+            if nc not in (1, 3):
+                raise NotImplementedError("JPEG: %d components (1 or 3)" % nc)
+            comps = [(data[seg + 6 + 3 * i], data[seg + 7 + 3 * i] >> 4, data[seg + 7 + 3 * i] & 15, data[seg + 8 + 3 * i])
+                     for i in range(nc)]
+            if any(c[3] > 3 or c[1] < 1 or c[2] < 1 for c in comps):
+                raise ValueError("JPEG: bad frame header")
+            if nc == 1:
+                hs, vs = 1, 1                           # one component: the MCU is one block whatever the header says
+            else:
+                hs, vs = comps[0][1], comps[0][2]
+                if (hs, vs) not in JPEG_SAMPLINGS or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+                    raise NotImplementedError("JPEG: sampling %s (luma 1x1, 2x1 or 2x2 with chroma 1x1)"
+                                              % ", ".join("%dx%d" % (c[1], c[2]) for c in comps))
+            frame = dict(w=w, h=h, ncomp=nc, hs=hs, vs=vs, ids=[c[0] for c in comps], tq=[c[3] for c in comps])
+        elif 0xC2 <= m <= 0xCF and m != 0xC8:           # C4 was taken above; CC is DAC
+            raise NotImplementedError("JPEG: %s (Huffman sequential files only)"
+                                      % {0xC2: "progressive", 0xCC: "arithmetic coding"}.get(m, "frame type SOF%d" % (m - 0xC0)))
+        elif m == 0xDA:                                 # SOS
+            if frame is None:
+                raise ValueError("JPEG: scan before the frame header")
+            ns = data[seg] if ln >= 3 else 0
+            if ns < 1 or ns > 4 or ln != 6 + 2 * ns:
+                raise ValueError("JPEG: bad scan header")
+            if ns != frame["ncomp"] or any(data[seg + 1 + 2 * i] != frame["ids"][i] for i in range(ns)):
+                raise NotImplementedError("JPEG: a scan that does not interleave all components in frame order")
+            tabs = [(data[seg + 2 + 2 * i] >> 4, data[seg + 2 + 2 * i] & 15) for i in range(ns)]
+            if data[seg + 1 + 2 * ns] != 0 or data[seg + 2 + 2 * ns] != 63 or data[seg + 3 + 2 * ns] != 0:
+                raise ValueError("JPEG: bad scan header")
+            for i, (td, ta) in enumerate(tabs):
+                if td > 3 or ta > 3 or (0, td) not in huff or (1, ta) not in huff or frame["tq"][i] not in qt:
+                    raise ValueError("JPEG: the scan names a table that was not defined")
+            w, h, hs, vs = frame["w"], frame["h"], frame["hs"], frame["vs"]
+            mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+            grids = [(mx * hs, my * vs)] + [(mx, my)] * (frame["ncomp"] - 1)      # (blocks per row, block rows)
+            blocks = sum(a * b for a, b in grids)
+            if blocks > 4 * (n - end):                  # a block takes two bits at the least
+                raise ValueError("JPEG: truncated scan")
+            frame.update(mx=mx, my=my, grids=grids, blocks=blocks, restart=restart, scan=end,
+                         dc=[huff[(0, t[0])] for t in tabs], ac=[huff[(1, t[1])] for t in tabs],
+                         q=[qt[t] for t in frame["tq"]])
+            return frame
+        pos = end
+
+
+def _jpeg_coefficients_py(data, f):
+    """The entropy decode in Python: int16 [blocks, 64], de-zigzagged, not dequantised; component by component, block-row
+    major."""
+    n, pos = len(data), f["scan"]
+    out = np.zeros((f["blocks"], 64), np.int16)
+    acc = nbits = 0
+
+    def bit():
+        nonlocal pos, acc, nbits
+        if nbits == 0:
+            if pos >= n:
+                raise ValueError("JPEG: truncated scan")
+            acc = data[pos]
+            pos += 1
+            if acc == 0xFF:
+                if pos >= n or data[pos] != 0:
+                    raise ValueError("JPEG: truncated scan (marker in the entropy-coded data)")
+                pos += 1
+            nbits = 8
+        nbits -= 1
+        return (acc >> nbits) & 1
+
+    def symbol(table):
+        code = 0
+        for length in range(1, 17):
+            code = (code << 1) | bit()
+            s = table.get((length, code))
+            if s is not None:
+                return s
+        raise ValueError("JPEG: bad Huffman code")
+
+    def receive(s):
+        v = 0
+        for _ in range(s):
+            v = (v << 1) | bit()
+        return v if v >= (1 << (s - 1)) else v - (1 << s) + 1
+
+    hs, vs, mx, my, nc = f["hs"], f["vs"], f["mx"], f["my"], f["ncomp"]
+    base, b0 = [], 0
+    for bw, bh in f["grids"]:
+        base.append(b0)
+        b0 += bw * bh
+    pred, rst = [0] * nc, 0
+    for mcu in range(mx * my):
+        if f["restart"] and mcu and mcu % f["restart"] == 0:
+            nbits = 0                                   # the marker is byte aligned
+            if pos + 2 > n or data[pos] != 0xFF or data[pos + 1] != 0xD0 + rst:
+                raise ValueError("JPEG: restart marker %d expected" % rst)
+            pos += 2
+            rst = (rst + 1) & 7
+            pred = [0] * nc
+        mr, mc = divmod(mcu, mx)
+        for c in range(nc):
+            ch, cv = (hs, vs) if c == 0 else (1, 1)
+            for by in range(cv):
+                for bx in range(ch):
+                    blk = out[base[c] + (mr * cv + by) * f["grids"][c][0] + mc * ch + bx]
+                    s = symbol(f["dc"][c])
+                    if s > 11:
+                        raise ValueError("JPEG: bad DC category")
+                    if s:
+                        pred[c] += receive(s)
+                    if not -32768 <= pred[c] <= 32767:
+                        raise ValueError("JPEG: DC value out of range")
+                    blk[0] = pred[c]
+                    k = 1
+                    while k < 64:
+                        rs = symbol(f["ac"][c])
+                        r, s = rs >> 4, rs & 15
+                        if s == 0:
+                            if r != 15:
+                                break
+                            k += 16
+                            continue
+                        k += r
+                        if k > 63 or s > 10:
+                            raise ValueError("JPEG: bad AC coefficient")
+                        blk[JPEG_ZIGZAG[k]] = receive(s)
+                        k += 1
+    while pos < n and data[pos] == 0xFF and pos + 1 < n and data[pos + 1] == 0xFF:
+        pos += 1
+    if pos + 2 > n or data[pos] != 0xFF or data[pos + 1] != 0xD9:
+        raise ValueError("JPEG: no end-of-image marker after the scan")
+    return out
+
+
+def jpeg_entropy_decode(data, use_lib=True):
+    """JPEG bytes -> ``(info, coef)``: ``info`` the header (w, h, ncomp, hs, vs, grids = per component (blocks per row,
+    block rows), q = per component the int32 [64] quantisation table in natural order, blocks) and ``coef`` int16
+    [blocks, 64].  The C helper of libbiggan_hip.so does the work (host code, no GPU involved); without the library, or
+    with ``use_lib=False``, the Python decoder does."""
+    data = bytes(data)
+    if use_lib:
+        try:
+            from . import hip
+            L = hip.lib()
+        except ImportError:                             # library not built: pure-Python fallback (slow)
+            L = None
+        if L is not None:
+            def call(rc):
+                if rc == 3:                             # BG_ERR_UNSUPPORTED
+                    raise NotImplementedError(L.bg_last_error().decode())
+                if rc != 0:
+                    raise ValueError(L.bg_last_error().decode())
+            hdr = hip.BgJpegInfo()
+            call(L.bg_jpeg_info(data, len(data), hip.byref(hdr)))
+            nc = hdr.ncomp
+            info = dict(w=hdr.width, h=hdr.height, ncomp=nc, hs=hdr.hs, vs=hdr.vs, blocks=int(hdr.blocks),
+                        grids=[(hdr.bw[c], hdr.bh[c]) for c in range(nc)],
+                        q=[np.array(hdr.q[c][:], np.int32) for c in range(nc)])
+            coef = np.empty((info["blocks"], 64), np.int16)
+            call(L.bg_jpeg_coefficients(data, len(data), coef.ctypes.data_as(hip.c_void_p), coef.size))
+            return info, coef
+    f = _jpeg_parse(data)
+    info = {k: f[k] for k in ("w", "h", "ncomp", "hs", "vs", "blocks", "grids", "q")}
+    return info, _jpeg_coefficients_py(data, f)
+
+
+def _fix(x):
+    return np.int32(round(x * 8192))
+
+
+def _idct_pass(v, shift):
+    """libjpeg's slow-integer butterfly on eight int32 arrays; int32 arithmetic that wraps like the device's."""
+    in0, in1, in2, in3, in4, in5, in6, in7 = v
+    z1 = (in2 + in6) * _fix(0.541196100)
+    t2 = z1 - in6 * _fix(1.847759065)
+    t3 = z1 + in2 * _fix(0.765366865)
+    t0 = (in0 + in4) * np.int32(8192)
+    t1 = (in0 - in4) * np.int32(8192)
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    a, b, c, d = in7, in5, in3, in1
+    z1, z2, z3, z4 = a + d, b + c, a + c, b + d
+    z5 = (z3 + z4) * _fix(1.175875602)
+    a = a * _fix(0.298631336)
+    b = b * _fix(2.053119869)
+    c = c * _fix(3.072711026)
+    d = d * _fix(1.501321110)
+    z1 = z1 * -_fix(0.899976223)
+    z2 = z2 * -_fix(2.562915447)
+    z3 = z3 * -_fix(1.961570560) + z5
+    z4 = z4 * -_fix(0.390180644) + z5
+    a, b, c, d = a + z1 + z3, b + z2 + z4, c + z2 + z3, d + z1 + z4
+    r = np.int32(1 << (shift - 1))
+    return [(x + r) >> shift for x in (t10 + d, t11 + c, t12 + b, t13 + a, t13 - a, t12 - b, t11 - c, t10 - d)]
+
+
+def jpeg_planes(info, coef):
+    """Dequantisation and inverse DCT: per component the uint8 plane [block rows * 8, blocks per row * 8] (whole MCUs)."""
+    planes, b0 = [], 0
+    with np.errstate(over="ignore"):
+        for (bw, bh), q in zip(info["grids"], info["q"]):
+            blk = coef[b0:b0 + bw * bh].astype(np.int32).reshape(-1, 8, 8) * q.astype(np.int32).reshape(1, 8, 8)
+            b0 += bw * bh
+            ws = np.stack(_idct_pass([blk[:, k, :] for k in range(8)], 11), axis=1)        # pass 1: columns
+            px = np.stack(_idct_pass([ws[:, :, k] for k in range(8)], 18), axis=2)         # pass 2: rows
+            px = np.clip(px + 128, 0, 255).astype(np.uint8)
+            planes.append(px.reshape(bh, bw, 8, 8).transpose(0, 2, 1, 3).reshape(bh * 8, bw * 8))
+    return planes
+
+
+def _jpeg_upsample(p, hs, vs):
+    """libjpeg's "fancy" (triangle) upsampling of a cropped chroma plane by hs x vs; the neighbour of an edge sample is
+    the sample itself, which is what its edge rules amount to."""
+    p = p.astype(np.int32)
+    if (hs, vs) == (1, 1):
+        return p
+    ch, cw = p.shape
+    left, right = np.maximum(np.arange(cw) - 1, 0), np.minimum(np.arange(cw) + 1, cw - 1)
+    out = np.empty((ch * vs, cw * 2), np.int32)
+    if vs == 1:
+        out[:, 0::2] = (3 * p + p[:, left] + 1) >> 2
+        out[:, 1::2] = (3 * p + p[:, right] + 2) >> 2
+        return out
+    up, down = np.maximum(np.arange(ch) - 1, 0), np.minimum(np.arange(ch) + 1, ch - 1)
+    r = np.empty((ch * 2, cw), np.int32)
+    r[0::2] = 3 * p + p[up]
+    r[1::2] = 3 * p + p[down]
+    out[:, 0::2] = (3 * r + r[:, left] + 8) >> 4
+    out[:, 1::2] = (3 * r + r[:, right] + 7) >> 4
+    return out
+
+
+def _jfix(x):
+    return int(x * 65536 + 0.5)
+
+
+def jpeg_pixels(info, planes, channels):
+    """Crop, upsample, colour transform and ``channels``: uint8 [h, w, channels]."""
+    w, h, hs, vs = info["w"], info["h"], info["hs"], info["vs"]
+    y = planes[0][:h, :w]
+    if channels == 1 or info["ncomp"] == 1:
+        return np.repeat(y[:, :, None], channels, axis=2)
+    cw, ch = -(-w // hs), -(-h // vs)
+    cb = _jpeg_upsample(planes[1][:ch, :cw], hs, vs)[:h, :w] - 128
+    cr = _jpeg_upsample(planes[2][:ch, :cw], hs, vs)[:h, :w] - 128
+    y = y.astype(np.int32)
+    r = y + ((_jfix(1.402) * cr + 32768) >> 16)
+    b = y + ((_jfix(1.772) * cb + 32768) >> 16)
+    g = y + ((-_jfix(0.34414) * cb + 32768 - _jfix(0.71414) * cr) >> 16)
+    return np.clip(np.stack([r, g, b], axis=2), 0, 255).astype(np.uint8)
+
+
+def decode_jpeg(data, channels=3, use_lib=True):
+    """tf.image.decode_jpeg(contents, channels) with its defaults (slow-integer DCT, fancy upscaling): uint8
+    [H, W, channels], channels 1 or 3.  A grey file at channels=3 replicates Y; a colour file at channels=1 is its Y
+    plane (libjpeg's greyscale output).  8-bit Huffman sequential files with 1 or 3 components, luma sampling 1x1, 2x1
+    or 2x2 with chroma 1x1, one interleaved scan, restart intervals; progressive, arithmetic-coded, 12-bit, four-component
+    files and other samplings raise NotImplementedError, malformed data ValueError."""
+    if channels not in (1, 3):
+        raise ValueError("decode_jpeg: channels must be 1 or 3 (JPEG has no alpha)")
+    info, coef = jpeg_entropy_decode(data, use_lib)
+    return jpeg_pixels(info, jpeg_planes(info, coef), channels)
+
+
+def decode_image(data, channels=3):
+    """tf.image.decode_image: dispatch on the magic bytes (JPEG, PNG)."""
+    if data[:2] == b"\xff\xd8":
+        return decode_jpeg(data, channels)
+    if data[:8] == b"\x89PNG\r\n\x1a\n":
+        return decode_png(data, channels)
+    raise ValueError("neither a PNG nor a JPEG file")
+
+
 def resize_bilinear_legacy(img, size):
     """tf.image.resize_images(img, [size, size]) of TF 1.x: bilinear, align_corners=False, no half-pixel
     centres: source coordinate = destination index * (in / out)."""
@@ -166,7 +518,7 @@ class ImageData:
             x_decode = np.load(filename)
         else:
             with open(filename, "rb") as f:
-                x_decode = decode_png(f.read(), channels=self.channels)
+                x_decode = decode_image(f.read(), channels=self.channels)
         img = resize_bilinear_legacy(x_decode, self.load_size)
         if self.flip:                                    # tf.image.random_flip_left_right
             with self._lock:
@@ -234,10 +586,50 @@ TABLE_DTYPE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("flip", 
                         ("scale_x", "<f4"), ("reserved", "<i4")])
 
 
+# BgJpegEntry of include/biggan_hip.h: 480 bytes, shipped as int32 [n_jpeg, 120]
+JPEG_COMP_DTYPE = np.dtype([("coef", "<i8"), ("bw", "<i4"), ("bh", "<i4")])
+JPEG_TABLE_DTYPE = np.dtype([("slot", "<i8"), ("w", "<i4"), ("h", "<i4"), ("channels", "<i4"), ("ncomp", "<i4"),
+                             ("hs", "<i4"), ("vs", "<i4"), ("block0", "<i4"), ("image", "<i4"), ("reserved", "<i4", (2,)),
+                             ("comp", JPEG_COMP_DTYPE, (3,)), ("q", "<u2", (3, 64))])
+assert TABLE_DTYPE.itemsize == 32 and JPEG_TABLE_DTYPE.itemsize == 480
+
+
+class JpegImage:
+    """An entropy-decoded JPEG file on its way to the device: the header (``jpeg_entropy_decode``) and the int16
+    coefficients [blocks, 64].  ``shape`` / ``size`` are those of the pixels it decodes to; ``decode()`` finishes it on
+    the host with the arithmetic bg_jpeg_batch_u8 would use."""
+
+    def __init__(self, info, coef, channels):
+        if channels not in (1, 3):
+            raise ValueError("decode_jpeg: channels must be 1 or 3 (JPEG has no alpha)")
+        self.info, self.coef, self.channels = info, coef, channels
+        self.shape = (info["h"], info["w"], channels)
+        self.size = info["h"] * info["w"] * channels
+        self.upload_bytes = coef.nbytes + JPEG_TABLE_DTYPE.itemsize
+
+    def decode(self):
+        return jpeg_pixels(self.info, jpeg_planes(self.info, self.coef), self.channels)
+
+
 def packable(img, channels):
-    """True for what ``pack_batch`` takes: a uint8 array [h, w, channels] with h, w >= 1."""
+    """True for what ``pack_batch`` takes: a uint8 array [h, w, channels] with h, w >= 1, or a ``JpegImage`` of as many
+    channels."""
+    if isinstance(img, JpegImage):
+        return img.channels == channels
     return (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == channels
             and img.shape[0] >= 1 and img.shape[1] >= 1)
+
+
+def upload_bytes(img):
+    """Bytes of a decoded image that cross the bus on the device path: its slot, or a JPEG's coefficients and entry."""
+    return img.upload_bytes if isinstance(img, JpegImage) else -(-img.size // RAW_ALIGN) * RAW_ALIGN
+
+
+def switch_bytes(images):
+    """The uploaded bytes of a batch as ``device_path_pays`` is to count them: a JPEG's bytes weigh RAW_OVER_OUT_MAX /
+    JPEG_OVER_OUT_MAX of a decoded image's, so that the one rule holds both thresholds in a mixed batch."""
+    return sum(upload_bytes(a) * (RAW_OVER_OUT_MAX / JPEG_OVER_OUT_MAX if isinstance(a, JpegImage) else 1.0)
+               for a in images)
 
 
 def pack_batch(images, flips, size, channels=None, pin=False):
@@ -245,7 +637,13 @@ def pack_batch(images, flips, size, channels=None, pin=False):
     ``functional.image_batch_u8``: ``raw`` uint8 [raw_bytes] with image i at ``geom["offsets"][i]`` (a multiple of 16,
     padding zeroed), ``table`` int32 [n, 8] (``TABLE_DTYPE``: offset, h, w, flip, and the two scales
     ``float32(n_in / size)`` of ``resize_bilinear_legacy``), ``geom`` the validated geometry.  ``pin``: pinned host
-    tensors (the target is a GPU).  ``channels`` defaults to the first image's.  Raises ValueError for anything else."""
+    tensors (the target is a GPU).  ``channels`` defaults to the first image's.  Raises ValueError for anything else.
+
+    A ``JpegImage`` gets a slot and a table entry like any other image, but its slot arrives empty (zeroed):
+    ``geom["jpeg"]`` (None without JPEG images) holds what ``functional.jpeg_batch_u8`` fills it from: ``coef`` int16
+    [64 * blocks], the images' coefficients back to back, ``table`` int32 [n_jpeg, 120] (``JPEG_TABLE_DTYPE``: slot, w, h,
+    channels, ncomp, luma sampling, first block, index in ``table``, per component coefficient offset and block grid,
+    quantisation tables), ``n``, ``blocks``, ``max_pixels`` and ``images`` (their indices in the batch)."""
     images = list(images)
     if not images:
         raise ValueError("pack_batch: no images")
@@ -254,7 +652,7 @@ def pack_batch(images, flips, size, channels=None, pin=False):
     if size < 1:
         raise ValueError("pack_batch: size %d" % size)
     if channels is None:
-        channels = images[0].shape[2] if isinstance(images[0], np.ndarray) and images[0].ndim == 3 else 0
+        channels = images[0].shape[2] if isinstance(images[0], (np.ndarray, JpegImage)) and len(images[0].shape) == 3 else 0
     if channels not in (1, 3, 4):
         raise ValueError("pack_batch: %s channels (1, 3 or 4)" % (channels,))
     table = np.zeros(len(images), TABLE_DTYPE)
@@ -270,14 +668,55 @@ def pack_batch(images, flips, size, channels=None, pin=False):
     view = raw.numpy()
     for e, img in zip(table, images):
         off, nb = int(e["offset"]), img.size
+        if isinstance(img, JpegImage):
+            view[off:off + -(-nb // RAW_ALIGN) * RAW_ALIGN] = 0
+            continue
         view[off:off + nb] = img.reshape(-1)
         view[off + nb:off + -(-nb // RAW_ALIGN) * RAW_ALIGN] = 0
+    jpeg = _pack_jpegs(images, table, channels, pin)
     tab = torch.from_numpy(table.view("<i4").reshape(len(images), 8))
     if pin:
         tab = tab.pin_memory()
     geom = dict(n=len(images), size=int(size), channels=int(channels), raw_bytes=int(pos),
-                offsets=[int(o) for o in table["offset"]], shapes=[tuple(img.shape[:2]) for img in images])
+                offsets=[int(o) for o in table["offset"]], shapes=[tuple(img.shape[:2]) for img in images], jpeg=jpeg)
     return raw, tab, geom
+
+
+def _pack_jpegs(images, table, channels, pin):
+    """The coefficient buffer and the per-JPEG table of ``pack_batch`` (None without a ``JpegImage``), validated here:
+    the kernel checks every entry again, but a header that does not add up is an error of the host."""
+    which = [i for i, img in enumerate(images) if isinstance(img, JpegImage)]
+    if not which:
+        return None
+    jt = np.zeros(len(which), JPEG_TABLE_DTYPE)
+    block0 = 0
+    for e, i in zip(jt, which):
+        img, info = images[i], images[i].info
+        w, h, hs, vs, nc = info["w"], info["h"], info["hs"], info["vs"], info["ncomp"]
+        mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+        grids = [(mx * hs, my * vs)] + [(mx, my)] * (nc - 1)
+        if (nc not in (1, 3) or (hs, vs) not in JPEG_SAMPLINGS or (nc == 1 and (hs, vs) != (1, 1))
+                or [tuple(g) for g in info["grids"]] != grids or len(info["q"]) != nc
+                or img.coef.dtype != np.int16 or img.coef.shape != (sum(a * b for a, b in grids), 64)):
+            raise ValueError("pack_batch: image %d: the JPEG header and its coefficients do not agree" % i)
+        e["slot"], e["w"], e["h"], e["channels"], e["ncomp"] = table[i]["offset"], w, h, channels, nc
+        e["hs"], e["vs"], e["block0"], e["image"] = hs, vs, block0, i
+        for c, (bw, bh) in enumerate(grids):
+            e["comp"][c] = (64 * block0, bw, bh)
+            e["q"][c] = info["q"][c]
+            block0 += bw * bh
+    if block0 >= 2 ** 31 - 64:
+        raise ValueError("pack_batch: %d JPEG blocks in one batch" % block0)
+    coef = torch.empty(64 * block0, dtype=torch.int16, pin_memory=bool(pin))
+    cv = coef.numpy()
+    for e, i in zip(jt, which):
+        c0 = 64 * int(e["block0"])
+        cv[c0:c0 + images[i].coef.size] = images[i].coef.reshape(-1)
+    tab = torch.from_numpy(jt.view("<i4").reshape(len(which), 120))
+    if pin:
+        tab = tab.pin_memory()
+    return dict(coef=coef, table=tab, n=len(which), blocks=int(block0), images=which,
+                max_pixels=max(images[i].info["w"] * images[i].info["h"] for i in which))
 
 
 def device_input_enabled(device, option=None):
@@ -290,6 +729,11 @@ def device_input_enabled(device, option=None):
 
 
 RAW_OVER_OUT_MAX = 1.0      # the automatic switch packs a batch only while its uint8 bytes are at most its fp32 bytes
+# ... and a batch of JPEG files while its coefficients and entries are at most 40 x its fp32 bytes: what the device path
+# saves there is the host's IDCT, upsampling and colour, which cost per SOURCE pixel as the upload does.  Measured
+# (JPEG input): 7 - 20 x the host path at uploaded / out = 0.39, 0.78, 4, 8, 16 and 32, with no trend towards
+# a crossing; past the last measured point the host path is kept.
+JPEG_OVER_OUT_MAX = 40.0
 
 
 def device_path_pays(raw_bytes, n, size, channels):
@@ -301,14 +745,18 @@ def device_path_pays(raw_bytes, n, size, channels):
     return raw_bytes <= RAW_OVER_OUT_MAX * (n * size * size * channels * 4)
 
 
-def decode_file(image_data, filename):
-    """The decode step of ``ImageData.image_processing`` alone."""
+def decode_file(image_data, filename, entropy_only=False):
+    """The decode step of ``ImageData.image_processing`` alone.  ``entropy_only``: a JPEG file that the device path can
+    take (1 or 3 channels) comes back as a ``JpegImage``, entropy-decoded only."""
     if not image_data.custom_dataset:
         return np.asarray(filename)
     if str(filename).endswith(".npy"):
         return np.load(filename)
     with open(filename, "rb") as f:
-        return decode_png(f.read(), channels=image_data.channels)
+        data = f.read()
+    if entropy_only and data[:2] == b"\xff\xd8" and image_data.channels in (1, 3):
+        return JpegImage(*jpeg_entropy_decode(data), channels=image_data.channels)
+    return decode_image(data, channels=image_data.channels)
 
 
 def finish_on_host(x_decode, size, flip):
@@ -317,6 +765,11 @@ def finish_on_host(x_decode, size, flip):
     if flip:
         img = img[:, ::-1]
     return (img / 127.5 - 1).astype(np.float32)
+
+
+def finish_decode(x):
+    """The pixels of what ``decode_file`` returned."""
+    return x.decode() if isinstance(x, JpegImage) else x
 
 
 class PackedBatch:
@@ -331,6 +784,10 @@ class PackedBatch:
         with torch.cuda.device(device):                 # the kernel goes to the current stream of the current device
             raw = self.raw.to(device, non_blocking=True)
             table = self.table.to(device, non_blocking=True)
+            j = g.get("jpeg")
+            if j is not None:                           # fills the JPEG slots of raw from their coefficients
+                Fn.jpeg_batch_u8(j["coef"].to(device, non_blocking=True), j["table"].to(device, non_blocking=True),
+                                 j["n"], j["blocks"], j["max_pixels"], raw, table, g["n"])
             return Fn.image_batch_u8(raw, table, g["n"], g["size"], g["channels"])
 
 
@@ -345,7 +802,11 @@ class BatchLoader:
     with one worker, and the same at any worker count - and packs; ``__next__`` copies the bytes and launches
     ``bg_image_batch_u8`` on the current stream.  A batch with an array that is not uint8 [h, w, C] is finished on the
     host with the same flips, and so is, under None, a batch whose packed bytes exceed its fp32 bytes
-    (``device_path_pays``: large sources); True packs every batch, False none.  Both paths give the same bits."""
+    (``device_path_pays``: large sources); True packs every batch, False none.  Both paths give the same bits.
+
+    A JPEG file is only entropy-decoded by the pool (``decode_file(entropy_only=True)``, the C helper): its coefficients
+    travel with the batch and ``bg_jpeg_batch_u8`` fills its slot on the device before the resize; in a batch that is
+    finished on the host it is decoded there from the same coefficients (``JpegImage.decode``)."""
 
     def __init__(self, files, labels, batch_size, image_data, device, seed=0, rank=0, world=1, depth=4, workers=8,
                  device_preprocess=None):
@@ -400,17 +861,17 @@ class BatchLoader:
 
     def _decode_and_pack(self, idx):
         idata = self.image_data
-        arrs = list(self.pool.map(lambda i: decode_file(idata, self.files[i]), idx))
+        arrs = list(self.pool.map(lambda i: decode_file(idata, self.files[i], entropy_only=True), idx))
         if idata.flip:
             with idata._lock:
                 flips = [bool(idata.rng.random() < 0.5) for _ in arrs]
         else:
             flips = [False] * len(arrs)
-        pays = not self._by_ratio or device_path_pays(sum(-(-a.size // RAW_ALIGN) * RAW_ALIGN for a in arrs), len(arrs),
-                                                      idata.load_size, idata.channels)
+        pays = not self._by_ratio or device_path_pays(switch_bytes(arrs), len(arrs), idata.load_size, idata.channels)
         if pays and all(packable(a, idata.channels) for a in arrs):
             return PackedBatch(*pack_batch(arrs, flips, idata.load_size, idata.channels, pin=True))
-        imgs = np.stack(list(self.pool.map(lambda af: finish_on_host(af[0], idata.load_size, af[1]), zip(arrs, flips))))
+        imgs = np.stack(list(self.pool.map(lambda af: finish_on_host(finish_decode(af[0]), idata.load_size, af[1]),
+                                           zip(arrs, flips))))
         return torch.from_numpy(imgs)
 
     def __iter__(self):

@@ -107,6 +107,38 @@ def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     return out
 
 
+def jpeg_batch_u8(coef, jpegs, n_jpeg, blocks, max_pixels, raw, table, n, raw_bytes=None, ws=None):
+    """The JPEG images of a packed batch (data.pack_batch: coef int16 [64 * blocks], jpegs int32 [n_jpeg,120], raw uint8
+    [bytes] and table int32 [n,8], all on the device): dequantisation, inverse DCT, chroma upsampling and colour
+    transform, bit-identical to data.decode_jpeg (csrc/jpeg.hip), into the images' slots of ``raw``, in place; run
+    ``image_batch_u8`` on raw and table afterwards.  An entry that does not fit its buffers writes nothing and marks
+    its image in ``table`` (h = 0: a NaN image).  ``ws``: a uint8 workspace of ``jpeg_batch_workspace_bytes`` to reuse.
+    No autograd."""
+    if coef.dtype != torch.int16 or coef.dim() != 1:
+        raise RuntimeError("jpeg_batch_u8: coef must be int16 [values], got %s %s" % (coef.dtype, tuple(coef.shape)))
+    if jpegs.dtype != torch.int32 or tuple(jpegs.shape) != (n_jpeg, 120):
+        raise RuntimeError("jpeg_batch_u8: jpegs must be int32 [%d,120], got %s %s" % (n_jpeg, jpegs.dtype, tuple(jpegs.shape)))
+    if raw.dtype != torch.uint8 or raw.dim() != 1:
+        raise RuntimeError("jpeg_batch_u8: raw must be uint8 [bytes], got %s %s" % (raw.dtype, tuple(raw.shape)))
+    if table.dtype != torch.int32 or tuple(table.shape) != (n, 8):
+        raise RuntimeError("jpeg_batch_u8: table must be int32 [%d,8], got %s %s" % (n, table.dtype, tuple(table.shape)))
+    nb = raw.numel() if raw_bytes is None else int(raw_bytes)
+    if nb > raw.numel():
+        raise RuntimeError("jpeg_batch_u8: raw_bytes %d > the %d bytes of raw" % (nb, raw.numel()))
+    need = jpeg_batch_workspace_bytes(n_jpeg, blocks)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=raw.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need:
+        raise RuntimeError("jpeg_batch_u8: ws must be uint8 [>= %d]" % need)
+    check(lib().bg_jpeg_batch_u8(hip.ptr(coef), coef.numel(), i32(jpegs), n_jpeg, int(blocks), int(max_pixels), hip.ptr(raw),
+                                 nb, i32(table), n, hip.ptr(ws), ws.numel(), stream()))
+    return raw
+
+
+def jpeg_batch_workspace_bytes(n_jpeg, blocks):
+    return int(lib().bg_jpeg_batch_workspace_bytes(int(n_jpeg), int(blocks)))
+
+
 def weight_packs(w):
     """(pack_p, pack_t): the bf16 K-contiguous copies of a conv / transposed-conv kernel [k,k,A,B]: pack_p keeps the
     variable's order [k*k][A][B], pack_t is [k*k][B][A].  Spectrally normalised kernels get them from the

@@ -6,8 +6,8 @@ computes on the host.
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32,
-                    c_void_p)
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint16,
+                    c_uint32, c_void_p)
 
 import torch
 
@@ -84,6 +84,12 @@ class BgHistItem(Structure):
     _fields_ = [("x", c_void_p), ("n", c_int64)]
 
 
+class BgJpegInfo(Structure):
+    """What bg_jpeg_info reads from a JPEG file's headers (host memory)."""
+    _fields_ = [(n, c_int32) for n in ("width", "height", "ncomp", "hs", "vs", "restart")] + \
+               [("bw", c_int32 * 3), ("bh", c_int32 * 3), ("blocks", c_int64), ("q", (c_uint16 * 64) * 3)]
+
+
 _P = c_void_p
 _AD = POINTER(BgAttn16Desc)
 _CD = POINTER(BgConvDesc)
@@ -95,6 +101,8 @@ SIGNATURES = {
     "bg_last_error": (c_char_p, []),
     "bg_target_arch": (c_char_p, []),
     "bg_png_unfilter": (c_int, [c_char_p, c_int, c_int, c_int, _P]),
+    "bg_jpeg_info": (c_int, [c_char_p, c_size_t, _P]),
+    "bg_jpeg_coefficients": (c_int, [c_char_p, c_size_t, _P, c_size_t]),
     "bg_conv2d_fwd_workspace_bytes": (c_size_t, [_CD]),
     "bg_conv2d_fwd": (c_int, [_CD, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_conv2d_fwd_d2s_supported": (c_int, [_CD, c_int]),
@@ -243,6 +251,8 @@ SIGNATURES = {
                                   _P]),
     "bg_image_tiles_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
     "bg_image_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
+    "bg_jpeg_batch_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "bg_jpeg_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int64, c_int, _P, c_int64, _P, c_int, _P, c_size_t, _P]),
     "bg_crc32c": (c_uint32, [c_char_p, c_size_t, c_uint32]),
     "bg_var_hist_plan_chunks": (c_int, [_P, c_int, _P]),               # (BgHistItem*, n, int* n_chunks)
     "bg_var_hist_plan_bytes": (c_size_t, [c_int, c_int]),

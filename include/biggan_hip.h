@@ -48,6 +48,25 @@ const char* bg_target_arch(void);
  * image on the CPU.  raw: h rows of 1 filter byte + stride bytes (the inflated IDAT stream); out: h * stride. */
 int bg_png_unfilter(const unsigned char* raw, int h, int stride, int bpp, unsigned char* out);
 
+/* Host-side helpers of the input pipeline (tf.image.decode_jpeg behind utils.py:27; csrc/jpeg_entropy.hip): the serial
+ * part of decoding an 8-bit Huffman sequential JPEG (SOF0 / SOF1; 1 or 3 components; luma sampling 1x1, 2x1 or 2x2 with
+ * chroma 1x1; one interleaved scan; restart intervals) on the CPU.  data[0:n] is untrusted: nothing outside it is read.
+ *   bg_jpeg_info          the headers: size, components, luma sampling hs x vs (1 x 1 for one component), per component
+ *                         the block grid bw x bh (whole MCUs) and its quantisation table in natural (row-major) order,
+ *                         blocks = sum of bw * bh
+ *   bg_jpeg_coefficients  the Huffman decode with DC prediction: coef[64 * blocks] int16, de-zigzagged, NOT dequantised;
+ *                         component by component, each block-row major, 64 values a block; coef_count must be 64 * blocks
+ * BG_ERR_ARG: truncated or corrupt data (or a NULL argument); BG_ERR_UNSUPPORTED: progressive, arithmetic-coded, 12-bit,
+ * two- or four-component files, other samplings, non-interleaved scans. */
+typedef struct BgJpegInfo {
+    int32_t  width, height, ncomp, hs, vs, restart;
+    int32_t  bw[3], bh[3];
+    int64_t  blocks;
+    uint16_t q[3][64];
+} BgJpegInfo;
+int bg_jpeg_info(const unsigned char* data, size_t n, BgJpegInfo* info);
+int bg_jpeg_coefficients(const unsigned char* data, size_t n, int16_t* coef, size_t coef_count);
+
 /* Host-side helper of the event-file writer (trainlog.py; TF's lib/io/record_writer.cc frames every record with two
  * of these): CRC-32C (Castagnoli, reflected polynomial 0x82F63B78, initial value and final xor 0xFFFFFFFF) of n bytes.
  * crc is the CRC of the bytes before them (0 to start), so that a buffer can be fed in pieces. */
@@ -770,6 +789,51 @@ typedef struct BgImageEntry {
 } BgImageEntry;
 int bg_image_batch_u8(const uint8_t* raw, int64_t raw_bytes, const BgImageEntry* table, int n, int S, int C, float* out,
                       void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * JPEG images of an input batch (tf.image.decode_jpeg with its defaults behind utils.py:27; csrc/jpeg.hip).
+ * bg_jpeg_batch_u8: entropy-decoded coefficients (bg_jpeg_coefficients) -> the uint8 pixels [h,w,channels] of the JPEG
+ *   images' slots in raw, the buffer that bg_image_batch_u8 reads next.  Slots of other images are not touched.
+ *   coef    int16 [coef_count], 16-byte aligned; 64 values a block, de-zigzagged, not dequantised
+ *   jpegs   n_jpeg entries of 480 bytes on the device, 16-byte aligned, in ascending block0 (data.pack_batch builds them
+ *           as int32 [n_jpeg,120]):
+ *             slot      byte offset of the image in raw (a multiple of 16)
+ *             w, h      image size; channels 1 or 3 = what the slot holds; ncomp 1 or 3; hs x vs the luma sampling
+ *             block0    number of the image's first block among the batch's blocks (sum of its predecessors' blocks);
+ *                       the image's component planes live at 64 * block0 of the workspace's plane area
+ *             image     index of the image's BgImageEntry in table, whose offset, h and w must be slot, h and w
+ *             comp[c]   coef = first int16 of the component in coef (a multiple of 8), bw x bh = its block grid, which
+ *                       must be the one of w, h, hs, vs: whole MCUs of hs x vs luma blocks and one block per chroma
+ *             q[c]      the component's quantisation table in natural order
+ *   total_blocks  blocks of all entries; max_pixels  the largest w * h (sizes the grid only)
+ *   table   the n BgImageEntry of the batch: see below
+ *   ws      bg_jpeg_batch_workspace_bytes(n_jpeg, total_blocks) bytes, 16-byte aligned
+ *   Integer arithmetic, bit-identical to data.decode_jpeg: coefficient * q; libjpeg's slow-integer inverse DCT (13-bit
+ *   constants; columns, (v + 2^10) >> 11; rows, (v + 2^17) >> 18; + 128; clamp); the planes cropped to
+ *   ceil(w / hs) x ceil(h / vs); "fancy" upsampling, 2x1: (3 p[i] + p[i-1] + 1) >> 2, (3 p[i] + p[i+1] + 2) >> 2, 2x2:
+ *   r = 3 p[j] + p[j-1 | j+1], then (3 r[i] + r[i-1] + 8) >> 4, (3 r[i] + r[i+1] + 7) >> 4, an edge sample being its own
+ *   neighbour; R = Y + ((91881 Cr + 32768) >> 16), B = Y + ((116130 Cb + 32768) >> 16),
+ *   G = Y + ((-22554 Cb + 32768 - 46802 Cr) >> 16) with Cb, Cr less 128; clamp.  channels = 1 stores Y, one component at
+ *   channels = 3 stores Y three times.
+ *   The library cannot read the tables: an entry whose sampling, block grid, coefficient extent, block range (inside
+ *   total_blocks and not below the end of an earlier entry's) or slot extent is not as described reads and writes
+ *   nothing for that image, and table[image] gets h = 0, so that bg_image_batch_u8 fills that image with NaN.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct BgJpegComp {
+    int64_t coef;
+    int32_t bw, bh;
+} BgJpegComp;
+typedef struct BgJpegEntry {
+    int64_t    slot;
+    int32_t    w, h, channels, ncomp, hs, vs;
+    int32_t    block0, image, reserved[2];
+    BgJpegComp comp[3];
+    uint16_t   q[3][64];
+} BgJpegEntry;
+size_t bg_jpeg_batch_workspace_bytes(int n_jpeg, int64_t total_blocks);
+int    bg_jpeg_batch_u8(const int16_t* coef, int64_t coef_count, const BgJpegEntry* jpegs, int n_jpeg, int64_t total_blocks,
+                        int max_pixels, uint8_t* raw, int64_t raw_bytes, BgImageEntry* table, int n, void* ws,
+                        size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Variable histograms (utils.py:322-333 tf.summary.histogram of every global variable; csrc/varhist.hip).
