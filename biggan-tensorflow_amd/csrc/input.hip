@@ -21,6 +21,8 @@
 
 #pragma clang fp contract(off)
 
+#include "input_resize.h"      // InAxis, in_axis, in_pixel: shared with dataset.hip
+
 namespace bg {
 
 #define IN_BLOCK 256
@@ -33,31 +35,6 @@ struct InGeom {
     int64_t raw_bytes;
     int S;
 };
-
-struct InAxis {
-    int lo, hi;
-    float f, g;         // weight of hi, weight of lo = fl32(1 - f)
-};
-
-__device__ __forceinline__ InAxis in_axis(int i, float scale, int n_in) {
-    const float src = (float)i * scale;
-    const float fl = floorf(src);
-    int lo = (int)fl;
-    lo = lo < 0 ? 0 : (lo > n_in - 1 ? n_in - 1 : lo);      // (never fires where the host path succeeds: bounds only)
-    InAxis a;
-    a.lo = lo;
-    a.hi = lo + 1 < n_in ? lo + 1 : n_in - 1;
-    a.f = src - fl;
-    a.g = 1.0f - a.f;
-    return a;
-}
-
-__device__ __forceinline__ float in_pixel(float a, float b, float c, float d, const InAxis& ax, const InAxis& ay) {
-    const float top = a * ax.g + b * ax.f;
-    const float bot = c * ax.g + d * ax.f;
-    const float v = top * ay.g + bot * ay.f;
-    return v / 127.5f - 1.0f;
-}
 
 // VEC (C = 4 only): raw 4-byte aligned and out 16-byte aligned.
 template <int C, bool VEC>

@@ -8,6 +8,10 @@ pinned buffer with a table of per-image geometry, and ``functional.image_batch_u
 resize, the flip and the normalisation on the device, bit-identical to ``ImageData.image_processing``, which stays
 the reference implementation and the fallback (``BG_DEVICE_INPUT=0``, a CPU device, an array that is not uint8).
 
+With ``BG_DEVICE_DATASET_GB`` set (opt-in) the loader keeps the dataset on the GPU: every file is decoded once, stored in
+one arena in the smaller of two forms (its uint8 pixels, or the finished fp32 image), and every later batch is one
+``functional.dataset_batch`` launch (csrc/dataset.hip) from the batch's indices and flips - the same batches, bit for bit.
+
 Only what the reference's custom-dataset branch needs is provided: 8-bit non-interlaced PNG files (grey,
 RGB, palette, with or without alpha), 8-bit Huffman sequential JPEG files (``decode_jpeg``; recognised by content, as
 TensorFlow's decoder does) and ``.npy`` arrays ``[H, W, C]`` uint8; ``mnist`` / ``cifar10`` (Keras
@@ -778,7 +782,8 @@ class PackedBatch:
     def __init__(self, raw, table, geom):
         self.raw, self.table, self.geom = raw, table, geom
 
-    def to_device(self, device):
+    def upload(self, device):
+        """``(raw, table)`` on the device, the JPEG slots of raw filled: the decoded uint8 pixels of every image."""
         from . import functional as Fn
         g = self.geom
         with torch.cuda.device(device):                 # the kernel goes to the current stream of the current device
@@ -788,7 +793,313 @@ class PackedBatch:
             if j is not None:                           # fills the JPEG slots of raw from their coefficients
                 Fn.jpeg_batch_u8(j["coef"].to(device, non_blocking=True), j["table"].to(device, non_blocking=True),
                                  j["n"], j["blocks"], j["max_pixels"], raw, table, g["n"])
+            return raw, table
+
+    def to_device(self, device):
+        from . import functional as Fn
+        g = self.geom
+        with torch.cuda.device(device):
+            raw, table = self.upload(device)
             return Fn.image_batch_u8(raw, table, g["n"], g["size"], g["channels"])
+
+
+# ------------------------------------------------------------------------------------------
+# device-resident dataset: decode every file once, keep it on the GPU, gather batches by index (csrc/dataset.hip)
+# ------------------------------------------------------------------------------------------
+# BgDatasetEntry of include/biggan_hip.h: 32 bytes, shipped as int32 [n_entries, 8]
+ENTRY_DTYPE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("kind", "<i4"), ("scale_y", "<f4"),
+                        ("scale_x", "<f4"), ("reserved", "<i4")])
+assert ENTRY_DTYPE.itemsize == 32
+KIND_U8, KIND_F32 = 0, 1    # the cached form of an image: its decoded uint8 pixels [h,w,C] / the finished fp32 [S,S,C]
+CACHE_DEPTH = 4             # scratch arenas for images past the budget: one per slot of the loader's queue
+
+
+def dataset_cache_bytes(device, option=None):
+    """The loader's ``cache_bytes`` switch resolved to the byte budget of the arena; 0 is off.  None reads
+    BG_DEVICE_DATASET_GB (GiB, a float; unset, empty or 0: off); a device that is not a GPU is always off."""
+    if torch.device(device).type != "cuda":
+        return 0
+    if option is None:
+        text = os.environ.get("BG_DEVICE_DATASET_GB", "").strip()
+        if not text:
+            return 0
+        gib = float(text)
+        if not 0 <= gib < float("inf"):
+            raise ValueError("BG_DEVICE_DATASET_GB=%s: a budget in GiB, 0 or more" % text)
+        return int(gib * (1 << 30))
+    if option < 0:
+        raise ValueError("cache_bytes %r: 0 or more" % (option,))
+    return int(option)
+
+
+def _align(n):
+    return -(-int(n) // RAW_ALIGN) * RAW_ALIGN
+
+
+def _jpeg_frame(data):
+    """The marker walk up to the frame header: ``(h, w, components)``, None for what ``decode_jpeg`` would refuse, or
+    "more" when ``data`` (a prefix of the file) ends before the frame header."""
+    n, pos = len(data), 2
+    if n < 2 or data[0] != 0xFF or data[1] != 0xD8:
+        return None
+    while True:
+        if pos + 2 > n:
+            return "more"
+        if data[pos] != 0xFF:
+            return None
+        m = data[pos + 1]
+        if m == 0xFF:
+            pos += 1
+            continue
+        pos += 2
+        if m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m in (0xD9, 0x00, 0xDA) or (0xC2 <= m <= 0xCF and m not in (0xC4, 0xC8)):
+            return None                                 # no frame header before the scan, or not Huffman sequential
+        if pos + 2 > n:
+            return "more"
+        ln = (data[pos] << 8) | data[pos + 1]
+        if ln < 2:
+            return None
+        if m in (0xC0, 0xC1):
+            if pos + 8 > n:
+                return "more"
+            prec, h, w, nc = data[pos + 2], (data[pos + 3] << 8) | data[pos + 4], (data[pos + 5] << 8) | data[pos + 6], data[pos + 7]
+            if prec != 8 or h < 1 or w < 1 or nc not in (1, 3):
+                return None
+            return h, w, nc
+        pos += ln
+
+
+HEADER_PREFIX = 4096                                    # bytes of a file that the planner reads first
+
+
+def image_header(image_data, filename):
+    """``(h, w, channels)`` of what ``decode_file`` would return, from the file's header alone: the IHDR chunk of a PNG
+    file, the markers up to the frame header of a JPEG file, the header of an ``.npy`` file.  None for a file that the
+    dataset cache cannot hold (an array that is not uint8 [h, w, channels], a channel count that ``packable`` refuses,
+    a file that the decoders refuse)."""
+    C = image_data.channels
+    if not image_data.custom_dataset or C not in (1, 3, 4):
+        return None
+    if str(filename).endswith(".npy"):
+        with open(filename, "rb") as f:
+            try:
+                major, _ = np.lib.format.read_magic(f)
+                read = np.lib.format.read_array_header_1_0 if major == 1 else np.lib.format.read_array_header_2_0
+                shape, _, dtype = read(f)
+            except ValueError:
+                return None
+        if dtype != np.uint8 or len(shape) != 3 or shape[2] != C or shape[0] < 1 or shape[1] < 1:
+            return None
+        return int(shape[0]), int(shape[1]), C
+    with open(filename, "rb") as f:
+        data = f.read(HEADER_PREFIX)
+        if data[:2] == b"\xff\xd8":
+            frame = _jpeg_frame(data)
+            if frame == "more":
+                frame = _jpeg_frame(data + f.read())
+            if frame is None or frame == "more" or C not in (1, 3):
+                return None
+            return frame[0], frame[1], C
+    if data[:8] == b"\x89PNG\r\n\x1a\n" and len(data) >= 33 and data[12:16] == b"IHDR":
+        w, h, depth, ctype, _, _, interlace = struct.unpack(">IIBBBBB", data[16:29])
+        if depth != 8 or interlace != 0 or ctype not in (0, 2, 3, 4, 6) or h < 1 or w < 1:
+            return None
+        return int(h), int(w), C
+    return None
+
+
+def entry_kind(h, w, size):
+    """The cached form with fewer bytes, by the comparison ``device_path_pays`` makes (RAW_OVER_OUT_MAX = 1.0): the uint8
+    source while its bytes are at most those of the finished fp32 image."""
+    return KIND_U8 if h * w <= 4 * RAW_OVER_OUT_MAX * size * size else KIND_F32
+
+
+class EntryPlan:
+    """What ``plan_entries`` returns; see there."""
+
+
+def plan_entries(shapes, size, channels, budget, batch_size=0, depth=CACHE_DEPTH, force_kind=None):
+    """The arena layout for images of ``shapes`` [(h, w), ...] in cache order.  Pure host arithmetic:
+
+    kinds        per image, ``entry_kind`` (or ``force_kind`` for all)
+    nbytes       per image, the bytes of its cached form: h * w * C, or 4 * S * S * C
+    n_cached     the longest prefix whose 16-byte aligned slots fit ``budget`` bytes; later images are never cached
+    offsets      per image, the arena offset of its slot (a multiple of 16), -1 past the prefix
+    cached_bytes the end of the prefix = the start of the scratch tail
+    slot_bytes   the largest aligned slot of an image past the prefix (0 without one); the scratch tail is ``depth``
+                 arenas of ``batch_size`` such slots, so that any batch finds room for all its uncached images
+    arena_bytes  cached_bytes + depth * batch_size * slot_bytes (at least 16)
+    table        ENTRY_DTYPE [n + depth * batch_size] (just [n] without a scratch tail): rows of cached images are final,
+                 rows of uncached images stay zero (h = 0: refused by the kernel), scratch rows are written per batch"""
+    S, C = int(size), int(channels)
+    if S < 1 or C not in (1, 3, 4):
+        raise ValueError("plan_entries: size %s, channels %s" % (size, channels))
+    if force_kind not in (None, KIND_U8, KIND_F32):
+        raise ValueError("plan_entries: force_kind %r" % (force_kind,))
+    n = len(shapes)
+    p = EntryPlan()
+    p.size, p.channels, p.depth, p.batch_size, p.n = S, C, int(depth), int(batch_size), n
+    p.shapes = [(int(h), int(w)) for h, w in shapes]
+    if any(h < 1 or w < 1 for h, w in p.shapes):
+        raise ValueError("plan_entries: an image without pixels")
+    p.kinds = np.array([entry_kind(h, w, S) if force_kind is None else force_kind for h, w in p.shapes], np.int32)
+    p.nbytes = np.array([h * w * C if k == KIND_U8 else 4 * S * S * C for (h, w), k in zip(p.shapes, p.kinds)], np.int64)
+    ends = np.cumsum([_align(b) for b in p.nbytes]) if n else np.zeros(0, np.int64)
+    p.n_cached = int(np.searchsorted(ends, int(budget), side="right"))
+    p.cached_bytes = int(ends[p.n_cached - 1]) if p.n_cached else 0
+    p.offsets = np.full(n, -1, np.int64)
+    p.offsets[:p.n_cached] = np.concatenate([[0], ends[:p.n_cached]])[:p.n_cached]
+    p.slot_bytes = max((_align(b) for b in p.nbytes[p.n_cached:]), default=0)
+    rows = p.depth * p.batch_size if p.slot_bytes else 0
+    if p.slot_bytes and p.batch_size < 1:
+        raise ValueError("plan_entries: images past the budget need batch_size for the scratch tail")
+    p.scratch_bytes = p.batch_size * p.slot_bytes       # of one of the depth scratch arenas
+    p.arena_bytes = max(p.cached_bytes + p.depth * p.scratch_bytes, RAW_ALIGN)
+    p.table = np.zeros(n + rows, ENTRY_DTYPE)
+    for i in range(p.n_cached):
+        p.table[i] = entry_row(p, i, p.offsets[i])
+    return p
+
+
+def entry_row(p, i, offset):
+    """The BgDatasetEntry of image ``i`` of a plan at ``offset``."""
+    h, w = p.shapes[i]
+    if p.kinds[i] == KIND_F32:
+        return (offset, p.size, p.size, KIND_F32, 0.0, 0.0, 0)
+    return (offset, h, w, KIND_U8, np.float32(h / float(p.size)), np.float32(w / float(p.size)), 0)
+
+
+def plan_dataset(files, image_data, budget, batch_size, pool=None, force_kind=None, depth=CACHE_DEPTH):
+    """The plan of the dataset cache for a file list, or None when a file cannot be cached by its header (the cache is
+    then off for the whole dataset).  Reads only the headers of the unique files (``image_header``, in ``pool``): a path
+    that ``--weight_file`` lists several times is one entry, and entries are numbered in first-occurrence order.
+    Returns ``plan_entries``' plan with ``files`` (the unique paths), ``entry_of`` (int64 [len(files)]: file list index
+    -> entry).  Returns ``(plan, None)``, or ``(None, name)`` with the first file that did not fit."""
+    first, entry_of = {}, np.empty(len(files), np.int64)
+    for i, f in enumerate(files):
+        entry_of[i] = first.setdefault(str(f) if image_data.custom_dataset else id(f), len(first))
+    unique = [None] * len(first)
+    for i, f in enumerate(files):
+        if unique[entry_of[i]] is None:
+            unique[entry_of[i]] = f
+    heads = list((pool.map if pool is not None else map)(lambda f: image_header(image_data, f), unique))
+    for f, hd in zip(unique, heads):
+        if hd is None:
+            return None, (str(f) if image_data.custom_dataset else "an in-memory array")
+    p = plan_entries([hd[:2] for hd in heads], image_data.load_size, image_data.channels, budget, batch_size, depth,
+                     force_kind)
+    p.files, p.entry_of = unique, entry_of
+    return p, None
+
+
+class CachedBatch:
+    """One batch of the dataset cache on its way to ``functional.dataset_batch``: the staged images that the arena does
+    not hold yet (``stages``: per source buffer its kind, the pinned host data and the int64 [m,4] copy segments),
+    the scratch rows of the entry table for images past the budget, and ``sel`` int32 [n,2] (entry row, flip)."""
+
+    def __init__(self, cache, stages, rows, sel):
+        self.cache, self.stages, self.rows, self.sel = cache, stages, rows, sel
+
+    def to_device(self, device):
+        from . import functional as Fn
+        c, p = self.cache, self.cache.plan
+        with torch.cuda.device(device):                 # everything goes to the current stream of the current device
+            for kind, host, segs in self.stages:
+                if kind == KIND_U8:
+                    src = host.upload(device)[0]        # the decoded uint8 pixels, JPEG slots filled on the device
+                elif isinstance(host, PackedBatch):
+                    src = host.to_device(device)        # fp32 [m,S,S,C], flips 0: resized and normalised on the device
+                else:
+                    src = host.to(device, non_blocking=True)
+                Fn.dataset_store(src, segs.to(device, non_blocking=True), c.arena)
+            if self.rows is not None:
+                row0, piece = self.rows
+                c.table[row0:row0 + piece.shape[0]].copy_(piece, non_blocking=True)
+            sel = self.sel.to(device, non_blocking=True)
+            return Fn.dataset_batch(c.arena, c.table, sel, sel.shape[0], p.size, p.channels)
+
+
+class DatasetCache:
+    """The device-resident dataset of a ``BatchLoader``: one uint8 arena of exactly the planned size, the entry table
+    (uploaded once) and the host bookkeeping.  ``schedule`` runs on the loader's worker thread, ``CachedBatch.to_device``
+    on the consumer's.
+
+    Ordering invariant: the worker marks an entry ``scheduled`` when it STAGES the image, long before the copy into the
+    arena runs.  That is safe because items leave the loader's queue first in, first out, and ``__next__`` puts every
+    launch of an item on one stream: the store of batch k precedes the gather of batch k + 1 (and the gather of batch k
+    itself) in stream order, so a later batch that finds the flag set reads a slot that is filled by then.  The flag
+    array belongs to the worker thread alone.  A consumer that changes streams between two ``next()`` calls has to order
+    them itself, as for any tensor."""
+
+    def __init__(self, plan, image_data, device, pool, device_preprocess, by_ratio):
+        self.plan, self.image_data, self.device, self.pool = plan, image_data, torch.device(device), pool
+        self.device_preprocess, self.by_ratio = device_preprocess, by_ratio
+        self.arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=self.device)
+        self.table = torch.from_numpy(plan.table.view("<i4").reshape(-1, 8)).to(self.device)
+        self.scheduled = np.zeros(plan.n, bool)
+        self.turn = 0                                   # batches with images past the budget: picks the scratch arena
+
+    def describe(self, listed):
+        p = self.plan
+        return ("# dataset cache: %d of %d files cached (%d listed), %d bytes (+ %d scratch), %d as uint8 source, %d as "
+                "finished fp32" % (p.n_cached, p.n, listed, p.cached_bytes, p.arena_bytes - p.cached_bytes,
+                                   int((p.kinds[:p.n_cached] == KIND_U8).sum()), int((p.kinds[:p.n_cached] == KIND_F32).sum())))
+
+    def schedule(self, idx, flips):
+        """The ``CachedBatch`` of file indices ``idx`` with ``flips`` drawn by the caller.  Decodes, with the loader's
+        existing machinery and flips forced to 0, only the images that no earlier batch has staged (and those past the
+        budget, every time)."""
+        p, idata, S, C = self.plan, self.image_data, self.plan.size, self.plan.channels
+        ents = [int(e) for e in p.entry_of[np.asarray(idx)]]
+        missing = [e for e in dict.fromkeys(ents) if e >= p.n_cached or not self.scheduled[e]]
+        arrs = list(self.pool.map(lambda e: decode_file(idata, p.files[e], entropy_only=True), missing))
+        row_of, piece, scratch0 = {}, [], 0
+        if any(e >= p.n_cached for e in missing):
+            slot = self.turn % p.depth
+            self.turn += 1
+            scratch0 = p.cached_bytes + slot * p.scratch_bytes
+            row0 = p.n + slot * p.batch_size
+        groups = {KIND_U8: ([], []), KIND_F32: ([], [])}      # kind -> (decoded images, arena offsets)
+        for e, a in zip(missing, arrs):
+            if not packable(a, C) or tuple(a.shape[:2]) != p.shapes[e]:
+                raise ValueError("dataset cache: %s decodes to %s %s, its header said uint8 %s"
+                                 % (p.files[e], getattr(a, "dtype", type(a).__name__), tuple(getattr(a, "shape", ())),
+                                    p.shapes[e] + (C,)))
+            if e < p.n_cached:
+                dst = int(p.offsets[e])
+            else:
+                dst = scratch0 + len(piece) * p.slot_bytes
+                row_of[e] = row0 + len(piece)
+                piece.append(entry_row(p, e, dst))
+            groups[int(p.kinds[e])][0].append(a)
+            groups[int(p.kinds[e])][1].append(dst)
+        stages = []
+        imgs, dsts = groups[KIND_U8]
+        if imgs:
+            raw, tab, geom = pack_batch(imgs, [False] * len(imgs), S, C, pin=True)
+            segs = [(off, dst, _align(a.size), 0) for off, dst, a in zip(geom["offsets"], dsts, imgs)]
+            stages.append((KIND_U8, PackedBatch(raw, tab, geom), torch.tensor(segs, dtype=torch.int64).pin_memory()))
+        imgs, dsts = groups[KIND_F32]
+        if imgs:
+            one = 4 * S * S * C
+            pays = self.device_preprocess and (not self.by_ratio or device_path_pays(switch_bytes(imgs), len(imgs), S, C))
+            if pays:
+                host = PackedBatch(*pack_batch(imgs, [False] * len(imgs), S, C, pin=True))
+            else:
+                host = torch.from_numpy(np.ascontiguousarray(np.stack(list(self.pool.map(      # (the resize's fancy
+                    lambda a: finish_on_host(finish_decode(a), S, False), imgs))))).pin_memory()   # indexing sets strides)
+            segs = [(i * one, dst, one, 0) for i, dst in enumerate(dsts)]
+            stages.append((KIND_F32, host, torch.tensor(segs, dtype=torch.int64).pin_memory()))
+        for e in missing:
+            if e < p.n_cached:
+                self.scheduled[e] = True
+        sel = np.array([(row_of.get(e, e), 1 if f else 0) for e, f in zip(ents, flips)], np.int32).reshape(len(ents), 2)
+        rows = None
+        if piece:
+            rows = (row0, torch.from_numpy(np.array(piece, ENTRY_DTYPE).view("<i4").reshape(len(piece), 8)).pin_memory())
+        return CachedBatch(self, stages, rows, torch.from_numpy(sel).pin_memory())
 
 
 class BatchLoader:
@@ -806,10 +1117,18 @@ class BatchLoader:
 
     A JPEG file is only entropy-decoded by the pool (``decode_file(entropy_only=True)``, the C helper): its coefficients
     travel with the batch and ``bg_jpeg_batch_u8`` fills its slot on the device before the resize; in a batch that is
-    finished on the host it is decoded there from the same coefficients (``JpegImage.decode``)."""
+    finished on the host it is decoded there from the same coefficients (``JpegImage.decode``).
+
+    ``cache_bytes`` (None: BG_DEVICE_DATASET_GB in GiB; 0, or a device that is not a GPU: off, and nothing below
+    happens): the byte budget of a device-resident dataset (``DatasetCache``, csrc/dataset.hip).  The constructor reads
+    the files' headers and plans one arena; the worker then decodes and stages an image only the first time a batch names
+    it, and ``__next__`` copies the staged images into the arena (``bg_dataset_store``) and builds the batch with one
+    ``bg_dataset_batch`` launch from the indices and flips, which are drawn exactly as without the cache.  Same seeds,
+    same batches, bit for bit.  Files past the budget are streamed through a scratch tail of the arena every time; a
+    dataset with a file that cannot be cached by its header runs without the cache."""
 
     def __init__(self, files, labels, batch_size, image_data, device, seed=0, rank=0, world=1, depth=4, workers=8,
-                 device_preprocess=None):
+                 device_preprocess=None, cache_bytes=None):
         if len(files) < batch_size * world:
             raise ValueError("dataset has %d files, fewer than one global batch (%d)" % (len(files), batch_size * world))
         self.files, self.labels = list(files), labels
@@ -823,6 +1142,10 @@ class BatchLoader:
         self.rng = np.random.default_rng(seed)          # same seed on every rank: identical permutations
         from concurrent.futures import ThreadPoolExecutor
         self.pool = ThreadPoolExecutor(max_workers=workers)     # zlib, the C unfilter and numpy release the GIL
+        self.cache = None
+        budget = dataset_cache_bytes(self.device, cache_bytes)
+        if budget > 0:
+            self._open_cache(budget)
         self.q = queue.Queue(maxsize=depth)
         self.stop = threading.Event()
         self.thread = threading.Thread(target=self._work, daemon=True)
@@ -839,7 +1162,9 @@ class BatchLoader:
                 per_step = self.batch_size * self.world
                 for s in range(0, len(order) - per_step + 1, per_step):
                     idx = order[s + self.rank * self.batch_size: s + (self.rank + 1) * self.batch_size]
-                    if self.device_preprocess:
+                    if self.cache is not None:
+                        item = [self.cache.schedule(idx, self._draw_flips(len(idx)))]
+                    elif self.device_preprocess:
                         item = [self._decode_and_pack(idx)]
                     else:
                         imgs = np.stack(list(self.pool.map(lambda i: self.image_data.image_processing(self.files[i]), idx)))
@@ -847,7 +1172,7 @@ class BatchLoader:
                     if self.labels is not None:
                         item.append(torch.tensor(np.asarray([self.labels[i] for i in idx], np.float32)))
                     if self.device.type == "cuda":
-                        item = [t if isinstance(t, PackedBatch) else t.pin_memory() for t in item]
+                        item = [t if isinstance(t, (PackedBatch, CachedBatch)) else t.pin_memory() for t in item]
                     while not self.stop.is_set():
                         try:
                             self.q.put(item, timeout=0.2)
@@ -859,14 +1184,29 @@ class BatchLoader:
         except Exception as e:                          # surface worker failures in the consumer
             self.q.put(e)
 
+    def _open_cache(self, budget):
+        import time
+        t0 = time.perf_counter()
+        plan, refused = plan_dataset(self.files, self.image_data, budget, self.batch_size, self.pool, depth=CACHE_DEPTH)
+        if plan is None:
+            print("# dataset cache: off, %s cannot be cached by its header" % refused)
+            return
+        self.cache = DatasetCache(plan, self.image_data, self.device, self.pool, self.device_preprocess, self._by_ratio)
+        self.cache.plan_seconds = time.perf_counter() - t0
+        print(self.cache.describe(len(self.files)))
+
+    def _draw_flips(self, n):
+        """One draw per image in batch order from ``image_data.rng``, under its lock."""
+        idata = self.image_data
+        if not idata.flip:
+            return [False] * n
+        with idata._lock:
+            return [bool(idata.rng.random() < 0.5) for _ in range(n)]
+
     def _decode_and_pack(self, idx):
         idata = self.image_data
         arrs = list(self.pool.map(lambda i: decode_file(idata, self.files[i], entropy_only=True), idx))
-        if idata.flip:
-            with idata._lock:
-                flips = [bool(idata.rng.random() < 0.5) for _ in arrs]
-        else:
-            flips = [False] * len(arrs)
+        flips = self._draw_flips(len(arrs))
         pays = not self._by_ratio or device_path_pays(switch_bytes(arrs), len(arrs), idata.load_size, idata.channels)
         if pays and all(packable(a, idata.channels) for a in arrs):
             return PackedBatch(*pack_batch(arrs, flips, idata.load_size, idata.channels, pin=True))
@@ -881,7 +1221,7 @@ class BatchLoader:
         item = self.q.get()
         if isinstance(item, Exception):
             raise item
-        out = [t.to_device(self.device) if isinstance(t, PackedBatch) else t.to(self.device, non_blocking=True)
+        out = [t.to_device(self.device) if isinstance(t, (PackedBatch, CachedBatch)) else t.to(self.device, non_blocking=True)
                for t in item]
         return out[0] if self.labels is None else tuple(out)
 

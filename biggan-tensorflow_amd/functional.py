@@ -135,6 +135,50 @@ def jpeg_batch_u8(coef, jpegs, n_jpeg, blocks, max_pixels, raw, table, n, raw_by
     return raw
 
 
+def dataset_store(src, segs, arena, src_bytes=None, arena_bytes=None):
+    """Copy segments of a staged device buffer into the dataset arena (csrc/dataset.hip): ``src`` any contiguous tensor,
+    ``segs`` int64 [k,4] (src, dst, bytes, reserved; byte offsets, multiples of 4), ``arena`` uint8 [bytes], all on the
+    device.  ``src_bytes`` / ``arena_bytes`` (default: all of either) bound what the kernel may touch: a segment that
+    does not fit, or is misaligned, is skipped whole.  No autograd."""
+    if segs.dtype != torch.int64 or segs.dim() != 2 or segs.shape[1] != 4 or segs.shape[0] < 1:
+        raise RuntimeError("dataset_store: segs must be int64 [k,4], got %s %s" % (segs.dtype, tuple(segs.shape)))
+    if arena.dtype != torch.uint8 or arena.dim() != 1:
+        raise RuntimeError("dataset_store: arena must be uint8 [bytes], got %s %s" % (arena.dtype, tuple(arena.shape)))
+    have = src.numel() * src.element_size()
+    sb = have if src_bytes is None else int(src_bytes)
+    ab = arena.numel() if arena_bytes is None else int(arena_bytes)
+    if sb > have or ab > arena.numel():
+        raise RuntimeError("dataset_store: src_bytes %d / arena_bytes %d exceed the %d / %d bytes of the tensors"
+                           % (sb, ab, have, arena.numel()))
+    check(lib().bg_dataset_store(hip.ptr(src), sb, hip.ptr(segs), segs.shape[0], hip.ptr(arena), ab, stream()))
+    return arena
+
+
+def dataset_batch(arena, entries, sel, n, size, channels, arena_bytes=None, out=None):
+    """One training batch [n,size,size,channels] fp32 in [-1,1] out of the dataset arena (csrc/dataset.hip): ``arena``
+    uint8 [bytes], ``entries`` int32 [n_entries,8] (data.ENTRY_DTYPE), ``sel`` int32 [n,2] (entry index, flip), all on the
+    device.  Bit-identical to data.ImageData.image_processing for both cached kinds.  ``arena_bytes`` (default: all of
+    arena) bounds what the kernel may read: a sel row or an entry that does not fit gives a NaN image.  ``out``: write
+    into this contiguous fp32 tensor instead of a new one.  No autograd."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1:
+        raise RuntimeError("dataset_batch: arena must be uint8 [bytes], got %s %s" % (arena.dtype, tuple(arena.shape)))
+    if entries.dtype != torch.int32 or entries.dim() != 2 or entries.shape[1] != 8 or entries.shape[0] < 1:
+        raise RuntimeError("dataset_batch: entries must be int32 [n_entries,8], got %s %s"
+                           % (entries.dtype, tuple(entries.shape)))
+    if sel.dtype != torch.int32 or tuple(sel.shape) != (n, 2):
+        raise RuntimeError("dataset_batch: sel must be int32 [%d,2], got %s %s" % (n, sel.dtype, tuple(sel.shape)))
+    ab = arena.numel() if arena_bytes is None else int(arena_bytes)
+    if ab > arena.numel():
+        raise RuntimeError("dataset_batch: arena_bytes %d > the %d bytes of arena" % (ab, arena.numel()))
+    if out is None:
+        out = torch.empty((n, size, size, channels), dtype=torch.float32, device=arena.device)
+    elif tuple(out.shape) != (n, size, size, channels):
+        raise RuntimeError("dataset_batch: out must be [%d,%d,%d,%d], got %s" % (n, size, size, channels, tuple(out.shape)))
+    check(lib().bg_dataset_batch(hip.ptr(arena), ab, i32(entries), entries.shape[0], i32(sel), n, size, channels, f32(out),
+                                 stream()))
+    return out
+
+
 def jpeg_batch_workspace_bytes(n_jpeg, blocks):
     return int(lib().bg_jpeg_batch_workspace_bytes(int(n_jpeg), int(blocks)))
 

@@ -253,6 +253,8 @@ SIGNATURES = {
     "bg_image_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
     "bg_jpeg_batch_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "bg_jpeg_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int64, c_int, _P, c_int64, _P, c_int, _P, c_size_t, _P]),
+    "bg_dataset_store": (c_int, [_P, c_int64, _P, c_int, _P, c_int64, _P]),
+    "bg_dataset_batch": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "bg_crc32c": (c_uint32, [c_char_p, c_size_t, c_uint32]),
     "bg_var_hist_plan_chunks": (c_int, [_P, c_int, _P]),               # (BgHistItem*, n, int* n_chunks)
     "bg_var_hist_plan_bytes": (c_size_t, [c_int, c_int]),

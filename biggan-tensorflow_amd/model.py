@@ -1450,11 +1450,12 @@ class BigGAN(GANBase):
             if loader is not None:
                 loader.close()
 
-    def open_dataset(self, root="./dataset", device_preprocess=None):
+    def open_dataset(self, root="./dataset", device_preprocess=None, cache_bytes=None):
         """BigGAN.py:195-212, 768-787: the files of ``<root>/<--dataset>/`` (+ ``--label_file``) behind the
         reference's shuffle / decode / resize / flip / batch pipeline; None when that folder does not exist
         (the training loop then runs on synthetic batches).  ``device_preprocess``: BatchLoader's switch (None: resize,
-        flip and normalise on the GPU unless BG_DEVICE_INPUT=0)."""
+        flip and normalise on the GPU unless BG_DEVICE_INPUT=0).  ``cache_bytes``: BatchLoader's budget of the
+        device-resident dataset (None: BG_DEVICE_DATASET_GB; 0: off)."""
         from . import data as D
         folder = os.path.join(root, self.dataset_name)
         if not os.path.isdir(folder):
@@ -1479,7 +1480,8 @@ class BigGAN(GANBase):
         print("# dataset number:", len(files))
         image_data = D.ImageData(self.img_size, self.c_dim, True, self.args.random_flip, seed=1234 + self.rank)
         return D.BatchLoader(files, labels if self.acgan else None, self.batch_size, image_data, self.device,
-                             seed=4321, rank=self.rank, world=self.world, device_preprocess=device_preprocess)
+                             seed=4321, rank=self.rank, world=self.world, device_preprocess=device_preprocess,
+                             cache_bytes=cache_bytes)
 
     def _open_log(self):
         """A new event file per run, resumed runs included (tf.summary.FileWriter, BigGAN.py:1019).  Rank 0 only: replicas

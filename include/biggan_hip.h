@@ -836,6 +836,41 @@ int    bg_jpeg_batch_u8(const int16_t* coef, int64_t coef_count, const BgJpegEnt
                         size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Device-resident dataset (data.DatasetCache; csrc/dataset.hip): every file is decoded once and kept in one arena on the
+ * GPU; every later batch is one gather launch from an index list.  The cached form of an image is one of two kinds:
+ *   kind 0  the decoded uint8 pixels [h,w,C], exactly the bytes of its slot in bg_image_batch_u8's raw buffer;
+ *   kind 1  the finished fp32 image [S,S,C]: resized and normalised, NOT flipped.
+ * bg_dataset_store: a guarded batched copy of n_segs segments from src (src_bytes bytes, staged on the device) into the
+ *   arena.  segs: n_segs entries of 32 bytes on the device (int64 [n_segs,4]: src, dst, bytes, reserved).  A segment whose
+ *   src, dst and bytes are all multiples of 16 moves in 16-byte words (where src and arena are so aligned), any other in
+ *   4-byte words.  A segment with a negative src, dst or bytes, one that is no multiple of 4, or an extent outside
+ *   src_bytes / arena_bytes is skipped whole: nothing of it is copied.  Segments must not overlap in the arena.
+ * bg_dataset_batch: out [n,S,S,C] fp32, C in {1,3,4}, from sel int32 [n,2] (entry index, flip) and entries, n_entries
+ *   entries of 32 bytes on the device (int32 [n_entries,8], little-endian):
+ *     word 0-1 offset (int64)   2 h   3 w   4 kind   5 scale_y   6 scale_x (fp32 bits, kind 0)   7 reserved (0)
+ *   kind 0: the arithmetic of bg_image_batch_u8 step for step, scale = (float)((double)n_in / (double)S), the flip
+ *   mirroring the output columns.  kind 1: out[y][x][:] = cached[y][flip ? S-1-x : x][:] (pixels mirrored, channels in
+ *   order).  Both are bit-identical to data.ImageData.image_processing.
+ *   The library cannot read the tables: a sel index outside [0, n_entries), a kind other than 0 or 1, h or w < 1, kind 1
+ *   with h or w != S, an offset that is negative or no multiple of 16, or an extent past arena_bytes reads nothing and
+ *   fills that image with NaN; other images are unaffected.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct BgDatasetEntry {
+    int64_t offset;               /* in the arena, multiple of 16 */
+    int32_t h, w;                 /* kind 1: both must equal S */
+    int32_t kind;                 /* 0 u8 source, 1 finished fp32 */
+    float   scale_y, scale_x;     /* kind 0: (float)((double)n_in / S) */
+    int32_t reserved;
+} BgDatasetEntry;
+typedef struct BgCopySeg {
+    int64_t src, dst, bytes, reserved;   /* multiples of 4 */
+} BgCopySeg;
+int bg_dataset_store(const void* src, int64_t src_bytes, const BgCopySeg* segs, int n_segs, uint8_t* arena,
+                     int64_t arena_bytes, void* stream);
+int bg_dataset_batch(const uint8_t* arena, int64_t arena_bytes, const BgDatasetEntry* entries, int n_entries,
+                     const int32_t* sel, int n, int S, int C, float* out, void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Variable histograms (utils.py:322-333 tf.summary.histogram of every global variable; csrc/varhist.hip).
  * One call histograms every variable of the model by the rule of TF 1.x's histogram.cc:
  *   counts[i][b] = number of finite elements x of item i with upper_bound(limits, (double)x) == b, i.e. b is the first
