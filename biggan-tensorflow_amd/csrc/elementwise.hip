@@ -247,6 +247,10 @@ static void launch_colreduce(Fn fn, OutT* out, int64_t qstride, int64_t rows_per
     }
 }
 
+// VEC consecutive elements of an fp32 or bf16 tensor <-> fp32 registers (16-byte float4 / 8-byte bf16x4 accesses for
+// VEC == 4).  The kernels below are templates over the element types of their activation tensors: the arithmetic is
+// fp32 in registers either way, and the `float` instantiation is the fp32 path (BASELINE configs 1-2), `__bf16` the
+// bf16-resident one (configs 3-5).
 template <int VEC>
 __device__ __forceinline__ void loadv(const float* p, float (&v)[VEC]) {
     if constexpr (VEC == 4) {
@@ -264,12 +268,60 @@ __device__ __forceinline__ void loadv(const float* p, float (&v)[VEC]) {
         for (int j = 0; j < VEC; ++j) v[j] = p[j];
     }
 }
+template <int VEC>
+__device__ __forceinline__ void loadv(const __bf16* p, float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        const uint2 r = *reinterpret_cast<const uint2*>(p);
+        v[0] = __builtin_bit_cast(float, r.x << 16);
+        v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
+        v[2] = __builtin_bit_cast(float, r.y << 16);
+        v[VEC - 1] = __builtin_bit_cast(float, r.y & 0xffff0000u);
+    } else if constexpr (VEC == 8) {
+        const uint4 r = *reinterpret_cast<const uint4*>(p);
+        v[0] = __builtin_bit_cast(float, r.x << 16); v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
+        v[2] = __builtin_bit_cast(float, r.y << 16); v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
+        v[4] = __builtin_bit_cast(float, r.z << 16); v[5] = __builtin_bit_cast(float, r.z & 0xffff0000u);
+        v[6] = __builtin_bit_cast(float, r.w << 16); v[VEC - 1] = __builtin_bit_cast(float, r.w & 0xffff0000u);
+    } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[j] = (float)p[j];
+    }
+}
+__device__ __forceinline__ uint32_t bf16_pack2(float a, float b) {
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    bf16x2_t v;
+    v[0] = (__bf16)a;
+    v[1] = (__bf16)b;
+    return __builtin_bit_cast(uint32_t, v);
+}
+template <int VEC>
+__device__ __forceinline__ void storev(float* p, const float (&v)[VEC]) {
+    if constexpr (VEC == 4)
+        stg4(p, make_float4(v[0], v[1], v[2], v[VEC - 1]));
+    else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) p[j] = v[j];
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void storev(__bf16* p, const float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        uint2 r;
+        r.x = bf16_pack2(v[0], v[1]);
+        r.y = bf16_pack2(v[2], v[VEC - 1]);
+        *reinterpret_cast<uint2*>(p) = r;
+    } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) p[j] = (__bf16)v[j];
+    }
+}
 
 // ------------------------------------------------------------------------------------------
 // batch statistics (tf.nn.moments, ops.py:630)
 // ------------------------------------------------------------------------------------------
-struct BnStatsFn {
-    const float* x;
+template <class TX>
+struct BnStatsFnT {
+    const TX* x;
     int C;
     template <int VEC>
     __device__ __forceinline__ void operator()(int, int64_t r, int c, float (&acc)[2][VEC]) const {
@@ -447,14 +499,14 @@ __device__ __forceinline__ float prelu_f(float v, float a) { return v > 0.f ? v 
 // TF gradient of relu(x) + a*(x-|x|)/2: 1 for x>0, a for x<0, a/2 at x==0
 __device__ __forceinline__ float prelu_d(float v, float a) { return v > 0.f ? 1.f : (v < 0.f ? a : 0.5f * a); }
 
-template <int VEC>
-__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_fwd_kernel(const float* __restrict__ x,
-                                                                     const float* __restrict__ mean,
-                                                                     const float* __restrict__ rstd,
-                                                                     const float* __restrict__ gamma,
-                                                                     const float* __restrict__ beta, int per_sample,
-                                                                     const float* __restrict__ alpha,
-                                                                     float* __restrict__ y, int N, int HW, int C) {
+template <int VEC, class TX, class TY>
+__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_fwd_t_kernel(const TX* __restrict__ x,
+                                                                       const float* __restrict__ mean,
+                                                                       const float* __restrict__ rstd,
+                                                                       const float* __restrict__ gamma,
+                                                                       const float* __restrict__ beta, int per_sample,
+                                                                       const float* __restrict__ alpha,
+                                                                       TY* __restrict__ y, int N, int HW, int C) {
     const int CV = C / VEC;
     const int64_t total = (int64_t)N * HW * CV;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
@@ -471,19 +523,19 @@ __global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_fwd_kernel(const float*
         if (alpha) loadv<VEC>(alpha + c, al);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float inv = rs[j] * ga[j];                  // tf.nn.batch_normalization: inv = rsqrt(var+eps)*scale
-            float v = xv[j] * inv + (be[j] - mu[j] * inv);    //   x*inv + (offset - mean*inv)
+            const float inv = rs[j] * ga[j];
+            float v = xv[j] * inv + (be[j] - mu[j] * inv);
             out[j] = alpha ? prelu_f(v, al[j]) : v;
         }
-        if constexpr (VEC == 4)
-            stg4(y + i * 4, make_float4(out[0], out[1], out[2], out[VEC - 1]));
-        else
-            y[i] = out[0];
+        storev<VEC>(y + i * VEC, out);
     }
 }
 
-struct BnBwdReduceFn {
-    const float *x, *dy, *mean, *rstd, *gamma, *beta, *alpha;
+template <class TX, class TY>
+struct BnBwdReduceFnT {
+    const TX* x;
+    const TY* dy;
+    const float *mean, *rstd, *gamma, *beta, *alpha;
     int per_sample, HW, C;
     template <int VEC>
     __device__ __forceinline__ void operator()(int n, int64_t r, int c, float (&acc)[3][VEC]) const {
@@ -508,11 +560,11 @@ struct BnBwdReduceFn {
     }
 };
 
-template <int VEC>
-__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_bwd_dx_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
+template <int VEC, class TX, class TY>
+__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_bwd_dx_t_kernel(
+    const TX* __restrict__ x, const TY* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta, int per_sample,
-    const float* __restrict__ alpha, const float* __restrict__ cm, float* __restrict__ dx, int N, int HW, int C) {
+    const float* __restrict__ alpha, const float* __restrict__ cm, TX* dx, const TX* add, int N, int HW, int C) {
     const int CV = C / VEC;
     const int64_t total = (int64_t)N * HW * CV;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
@@ -535,10 +587,13 @@ __global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_bwd_dx_kernel(
             const float g = alpha ? dv[j] * prelu_d(pre, al[j]) : dv[j];
             out[j] = rs[j] * (g * ga[j] - m1[j] - xh * m2[j]);
         }
-        if constexpr (VEC == 4)
-            stg4(dx + i * 4, make_float4(out[0], out[1], out[2], out[VEC - 1]));
-        else
-            dx[i] = out[0];
+        if (add) {
+            float av[VEC];
+            loadv<VEC>(add + i * VEC, av);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) out[j] += av[j];
+        }
+        storev<VEC>(dx + i * VEC, out);
     }
 }
 
@@ -601,49 +656,211 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     cm[C + c] = (float)(g1 / count);
 }
 
+// ---- bf16 fast forms of batch-norm apply (+PReLU) and its input gradient --------------------------------------
+// The generic kernels above spend two 64-bit divisions and five to nine 16-byte coefficient loads per 8 bytes of
+// activation (measured r02: 2.9 - 3.3 TB/s of tensor traffic, ~10 % of a config-3 iteration).  Here a thread keeps ONE
+// group of 8 channels for its whole walk - the grid stride is a multiple of C / 8 - so the per-channel coefficients
+// sit in registers (reloaded only when a conditional batch norm moves to the next sample) and an item is one 16-byte
+// load, 8 FMAs + PReLU, one 16-byte store.
+__device__ __forceinline__ void bf16x8_load(const __bf16* p, float (&v)[8]) {
+    const uint4 r = *reinterpret_cast<const uint4*>(p);
+    v[0] = __builtin_bit_cast(float, r.x << 16); v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
+    v[2] = __builtin_bit_cast(float, r.y << 16); v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
+    v[4] = __builtin_bit_cast(float, r.z << 16); v[5] = __builtin_bit_cast(float, r.z & 0xffff0000u);
+    v[6] = __builtin_bit_cast(float, r.w << 16); v[7] = __builtin_bit_cast(float, r.w & 0xffff0000u);
+}
+__device__ __forceinline__ void bf16x8_store(__bf16* p, const float (&v)[8]) {
+    uint4 r;
+    r.x = bf16_pack2(v[0], v[1]); r.y = bf16_pack2(v[2], v[3]); r.z = bf16_pack2(v[4], v[5]); r.w = bf16_pack2(v[6], v[7]);
+    *reinterpret_cast<uint4*>(p) = r;
+}
+__device__ __forceinline__ void f32x8_load(const float* p, float (&v)[8]) {
+    const float4 a = ldg4(p), b = ldg4(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+// rows = N * HW pixels of C = 8 CV channels; (gridDim.x * EW_BLOCK) % CV == 0
+__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_fwd_bf16x8_kernel(
+    const __bf16* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ gamma, const float* __restrict__ beta, int per_sample, const float* __restrict__ alpha,
+    __bf16* __restrict__ y, int rows, int HW, int CV) {
+    const int gtid = blockIdx.x * EW_BLOCK + threadIdx.x;
+    const int cv = gtid % CV, c = cv * 8, C = CV * 8;
+    const int rstep = (gridDim.x * EW_BLOCK) / CV;
+    float mu[8], rs[8], al[8], inv[8], sh[8];
+    f32x8_load(mean + c, mu);
+    f32x8_load(rstd + c, rs);
+    if (alpha) f32x8_load(alpha + c, al);
+    int r_end = 0;                       // rows [.., r_end) share the coefficients in registers
+    for (int r = gtid / CV; r < rows; r += rstep) {
+        if (r >= r_end) {
+            const int n = per_sample ? r / HW : 0;
+            r_end = per_sample ? (n + 1) * HW : rows;
+            float ga[8], be[8];
+            f32x8_load(gamma + (int64_t)n * C * per_sample + c, ga);
+            f32x8_load(beta + (int64_t)n * C * per_sample + c, be);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                inv[j] = rs[j] * ga[j];
+                sh[j] = be[j] - mu[j] * inv[j];
+            }
+        }
+        float xv[8], out[8];
+        bf16x8_load(x + (int64_t)r * C + c, xv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float v = xv[j] * inv[j] + sh[j];
+            out[j] = alpha ? prelu_f(v, al[j]) : v;
+        }
+        bf16x8_store(y + (int64_t)r * C + c, out);
+    }
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_bwd_dx_bf16x8_kernel(
+    const __bf16* __restrict__ x, const __bf16* __restrict__ dy, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta, int per_sample,
+    const float* __restrict__ alpha, const float* __restrict__ cm, __bf16* dx, const __bf16* add, int rows, int HW,
+    int CV) {
+    // add (may alias dx): dx = add + gradient - the sum with the other branch of a forked tensor, fused (ops.py:253/263)
+    const int gtid = blockIdx.x * EW_BLOCK + threadIdx.x;
+    const int cv = gtid % CV, c = cv * 8, C = CV * 8;
+    const int rstep = (gridDim.x * EW_BLOCK) / CV;
+    float mu[8], rs[8], al[8], m1[8], m2[8], ga[8], be[8];
+    f32x8_load(mean + c, mu);
+    f32x8_load(rstd + c, rs);
+    f32x8_load(cm + c, m1);
+    f32x8_load(cm + C + c, m2);
+    if (alpha) f32x8_load(alpha + c, al);
+    int r_end = 0;
+    for (int r = gtid / CV; r < rows; r += rstep) {
+        if (r >= r_end) {
+            const int n = per_sample ? r / HW : 0;
+            r_end = per_sample ? (n + 1) * HW : rows;
+            f32x8_load(gamma + (int64_t)n * C * per_sample + c, ga);
+            f32x8_load(beta + (int64_t)n * C * per_sample + c, be);
+        }
+        float xv[8], dv[8], out[8];
+        bf16x8_load(x + (int64_t)r * C + c, xv);
+        bf16x8_load(dy + (int64_t)r * C + c, dv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float xh = (xv[j] - mu[j]) * rs[j];
+            const float pre = xh * ga[j] + be[j];
+            const float g = alpha ? dv[j] * prelu_d(pre, al[j]) : dv[j];
+            out[j] = rs[j] * (g * ga[j] - m1[j] - xh * m2[j]);
+        }
+        if (add) {
+            float av[8];
+            bf16x8_load(add + (int64_t)r * C + c, av);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) out[j] += av[j];
+        }
+        bf16x8_store(dx + (int64_t)r * C + c, out);
+    }
+}
+
+// stand-alone PReLU (ops.py:532) and its input gradient, same scheme
+template <bool BWD>
+__global__ __launch_bounds__(EW_BLOCK) void prelu_bf16x8_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ dy,
+                                                                 const float* __restrict__ alpha, __bf16* out,
+                                                                 const __bf16* add, int rows, int CV) {
+    const int gtid = blockIdx.x * EW_BLOCK + threadIdx.x;
+    const int c = (gtid % CV) * 8, C = CV * 8;
+    const int rstep = (gridDim.x * EW_BLOCK) / CV;
+    float al[8];
+    f32x8_load(alpha + c, al);
+    for (int r = gtid / CV; r < rows; r += rstep) {
+        float xv[8], dv[8], o[8];
+        bf16x8_load(x + (int64_t)r * C + c, xv);
+        if (BWD) bf16x8_load(dy + (int64_t)r * C + c, dv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = BWD ? dv[j] * prelu_d(xv[j], al[j]) : prelu_f(xv[j], al[j]);
+        if (BWD && add) {
+            float av[8];
+            bf16x8_load(add + (int64_t)r * C + c, av);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] += av[j];
+        }
+        bf16x8_store(out + (int64_t)r * C + c, o);
+    }
+}
+
+// y = sa a + sb b on bf16 tensors, 16 bytes per operand and item
+__global__ __launch_bounds__(EW_BLOCK) void lincomb_bf16x8_kernel(const __bf16* __restrict__ a, const float* sa_dev, float sa,
+                                                                   const __bf16* __restrict__ b, float sb,
+                                                                   __bf16* __restrict__ y, int64_t n8) {
+    const float s = sa_dev ? *sa_dev : sa;
+    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n8; i += (int64_t)gridDim.x * EW_BLOCK) {
+        float av[8], bv[8], o[8];
+        bf16x8_load(a + i * 8, av);
+        if (b) {
+            bf16x8_load(b + i * 8, bv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = s * av[j] + sb * bv[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = s * av[j];
+        }
+        bf16x8_store(y + i * 8, o);
+    }
+}
+
+// grid for the x8 kernels: enough blocks to fill the chip, a multiple of CV / gcd(CV, EW_BLOCK)
+static inline int bn_x8_grid(int64_t rows, int CV) {
+    int a = CV, b = EW_BLOCK;
+    while (b) { const int t = a % b; a = b; b = t; }
+    const int unit = CV / a;
+    int64_t want = (rows * CV + EW_BLOCK - 1) / EW_BLOCK;
+    if (want > 4096) want = 4096;
+    if (want < 1) want = 1;
+    return (int)((want + unit - 1) / unit * unit);
+}
+
 // ------------------------------------------------------------------------------------------
 // stand-alone PReLU
 // ------------------------------------------------------------------------------------------
-template <int VEC>
-__global__ __launch_bounds__(EW_BLOCK) void prelu_fwd_kernel(const float* __restrict__ x,
-                                                              const float* __restrict__ alpha, float* __restrict__ y,
-                                                              int64_t total_v, int C) {
+template <int VEC, class TX, class TY>
+__global__ __launch_bounds__(EW_BLOCK) void prelu_fwd_t_kernel(const TX* __restrict__ x, const float* __restrict__ alpha,
+                                                                TY* __restrict__ y, int64_t total_v, int C) {
     const int CV = C / VEC;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total_v; i += (int64_t)gridDim.x * EW_BLOCK) {
         const int c = (int)(i % CV) * VEC;
-        float xv[VEC], al[VEC];
+        float xv[VEC], al[VEC], out[VEC];
         loadv<VEC>(x + i * VEC, xv);
         loadv<VEC>(alpha + c, al);
-        if constexpr (VEC == 4)
-            stg4(y + i * 4, make_float4(prelu_f(xv[0], al[0]), prelu_f(xv[1], al[1]), prelu_f(xv[2], al[2]),
-                                        prelu_f(xv[VEC - 1], al[VEC - 1])));
-        else
-            y[i] = prelu_f(xv[0], al[0]);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) out[j] = prelu_f(xv[j], al[j]);
+        storev<VEC>(y + i * VEC, out);
     }
 }
 
-template <int VEC>
-__global__ __launch_bounds__(EW_BLOCK) void prelu_bwd_dx_kernel(const float* __restrict__ x,
-                                                                 const float* __restrict__ dy,
-                                                                 const float* __restrict__ alpha,
-                                                                 float* __restrict__ dx, int64_t total_v, int C) {
+template <int VEC, class TX, class TY>
+__global__ __launch_bounds__(EW_BLOCK) void prelu_bwd_dx_t_kernel(const TX* __restrict__ x, const TY* __restrict__ dy,
+                                                                   const float* __restrict__ alpha, TX* dx, const TX* add,
+                                                                   int64_t total_v, int C) {
     const int CV = C / VEC;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total_v; i += (int64_t)gridDim.x * EW_BLOCK) {
         const int c = (int)(i % CV) * VEC;
-        float xv[VEC], dv[VEC], al[VEC];
+        float xv[VEC], dv[VEC], al[VEC], out[VEC];
         loadv<VEC>(x + i * VEC, xv);
         loadv<VEC>(dy + i * VEC, dv);
         loadv<VEC>(alpha + c, al);
-        if constexpr (VEC == 4)
-            stg4(dx + i * 4, make_float4(dv[0] * prelu_d(xv[0], al[0]), dv[1] * prelu_d(xv[1], al[1]),
-                                         dv[2] * prelu_d(xv[2], al[2]), dv[VEC - 1] * prelu_d(xv[VEC - 1], al[VEC - 1])));
-        else
-            dx[i] = dv[0] * prelu_d(xv[0], al[0]);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) out[j] = dv[j] * prelu_d(xv[j], al[j]);
+        if (add) {
+            float av[VEC];
+            loadv<VEC>(add + i * VEC, av);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) out[j] += av[j];
+        }
+        storev<VEC>(dx + i * VEC, out);
     }
 }
 
-struct PreluDalphaFn {
-    const float *x, *dy;
+template <class TX, class TY>
+struct PreluDalphaFnT {
+    const TX* x;
+    const TY* dy;
     int C;
     template <int VEC>
     __device__ __forceinline__ void operator()(int, int64_t r, int c, float (&acc)[1][VEC]) const {
@@ -655,8 +872,9 @@ struct PreluDalphaFn {
     }
 };
 
-struct BiasGradFn {
-    const float* dy;
+template <class T>
+struct BiasGradFnT {
+    const T* dy;
     int C;
     template <int VEC>
     __device__ __forceinline__ void operator()(int, int64_t r, int c, float (&acc)[1][VEC]) const {
@@ -667,12 +885,60 @@ struct BiasGradFn {
     }
 };
 
+// d alpha of a PReLU on a tensor with C <= 4 channels (the discriminator's activation of the IMAGE, ops.py:299): the column
+// skeleton would put 3 threads of a row-lane on a row (4-byte loads, 0.6 TB/s); here a thread owns whole pixels, 4 in flight.
+__global__ __launch_bounds__(EW_BLOCK) void prelu_dalpha_thin_kernel(float* part, const float* __restrict__ x, const float* __restrict__ dy,
+                                                                     float* __restrict__ dalpha, int64_t rows, int C) {
+    __shared__ float red[4][EW_BLOCK];
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const int64_t stride = (int64_t)gridDim.x * EW_BLOCK;
+    int64_t r = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x;
+    for (; r + 3 * stride < rows; r += 4 * stride) {
+        float xv[4][4], gv[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) {
+                    xv[u][c] = x[(r + u * stride) * C + c];
+                    gv[u][c] = dy[(r + u * stride) * C + c];
+                }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < C) acc[c] += xv[u][c] < 0.f ? gv[u][c] * xv[u][c] : 0.f;
+    }
+    for (; r < rows; r += stride)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < C) {
+                const float xs = x[r * C + c];
+                acc[c] += xs < 0.f ? dy[r * C + c] * xs : 0.f;
+            }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = acc[c];
+    __syncthreads();
+    for (int s = EW_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < C) {
+        if (part)
+            part[blockIdx.x * C + threadIdx.x] = red[threadIdx.x][0];
+        else
+            dalpha[threadIdx.x] += red[threadIdx.x][0];
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // max pool 2x2 / global sum pool
 // ------------------------------------------------------------------------------------------
-template <int VEC>
-__global__ __launch_bounds__(EW_BLOCK) void maxpool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                 int N, int H, int W, int C) {
+template <int VEC, class T>
+__global__ __launch_bounds__(EW_BLOCK) void maxpool2_fwd_t_kernel(const T* __restrict__ x, T* __restrict__ y, int N,
+                                                                   int H, int W, int C) {
     const int CV = C / VEC, Ho = H / 2, Wo = W / 2;
     const int64_t total = (int64_t)N * Ho * Wo * CV;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
@@ -682,7 +948,7 @@ __global__ __launch_bounds__(EW_BLOCK) void maxpool2_fwd_kernel(const float* __r
         t /= Wo;
         const int ho = (int)(t % Ho);
         const int n = (int)(t / Ho);
-        const float* p = x + (((int64_t)n * H + 2 * ho) * W + 2 * wo) * C + cv * VEC;
+        const T* p = x + (((int64_t)n * H + 2 * ho) * W + 2 * wo) * C + cv * VEC;
         float a[VEC], b[VEC], c_[VEC], d[VEC], o[VEC];
         loadv<VEC>(p, a);
         loadv<VEC>(p + C, b);
@@ -690,10 +956,47 @@ __global__ __launch_bounds__(EW_BLOCK) void maxpool2_fwd_kernel(const float* __r
         loadv<VEC>(p + (int64_t)W * C + C, d);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) o[j] = fmaxf(fmaxf(a[j], b[j]), fmaxf(c_[j], d[j]));
-        if constexpr (VEC == 4)
-            stg4(y + i * 4, make_float4(o[0], o[1], o[2], o[VEC - 1]));
-        else
-            y[i] = o[0];
+        storev<VEC>(y + i * VEC, o);
+    }
+}
+
+template <int VEC, class T>
+__global__ __launch_bounds__(EW_BLOCK) void maxpool2_bwd_t_kernel(const T* __restrict__ x, const T* __restrict__ dy,
+                                                                   T* __restrict__ dx, int N, int H, int W, int C) {
+    const int CV = C / VEC, Ho = H / 2, Wo = W / 2;
+    const int64_t total = (int64_t)N * Ho * Wo * CV;
+    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
+        const int cv = (int)(i % CV);
+        int64_t t = i / CV;
+        const int wo = (int)(t % Wo);
+        t /= Wo;
+        const int ho = (int)(t % Ho);
+        const int n = (int)(t / Ho);
+        const int64_t base = (((int64_t)n * H + 2 * ho) * W + 2 * wo) * C + cv * VEC;
+        const int64_t o1 = C, o2 = (int64_t)W * C, o3 = (int64_t)W * C + C;
+        float a[VEC], b[VEC], c_[VEC], d[VEC], g[VEC];
+        loadv<VEC>(x + base, a);
+        loadv<VEC>(x + base + o1, b);
+        loadv<VEC>(x + base + o2, c_);
+        loadv<VEC>(x + base + o3, d);
+        loadv<VEC>(dy + i * VEC, g);
+        float ra[VEC], rb[VEC], rc[VEC], rd[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const float m = fmaxf(fmaxf(a[j], b[j]), fmaxf(c_[j], d[j]));
+            const bool sa = a[j] == m;
+            const bool sb = !sa && b[j] == m;
+            const bool sc = !sa && !sb && c_[j] == m;
+            const bool sd = !sa && !sb && !sc;
+            ra[j] = sa ? g[j] : 0.f;
+            rb[j] = sb ? g[j] : 0.f;
+            rc[j] = sc ? g[j] : 0.f;
+            rd[j] = sd ? g[j] : 0.f;
+        }
+        storev<VEC>(dx + base, ra);
+        storev<VEC>(dx + base + o1, rb);
+        storev<VEC>(dx + base + o2, rc);
+        storev<VEC>(dx + base + o3, rd);
     }
 }
 
@@ -762,74 +1065,39 @@ __global__ __launch_bounds__(EW_BLOCK) void box2_up_kernel(const float* __restri
     }
 }
 
-template <int VEC>
-__global__ __launch_bounds__(EW_BLOCK) void maxpool2_bwd_kernel(const float* __restrict__ x,
-                                                                 const float* __restrict__ dy, float* __restrict__ dx,
-                                                                 int N, int H, int W, int C) {
-    const int CV = C / VEC, Ho = H / 2, Wo = W / 2;
-    const int64_t total = (int64_t)N * Ho * Wo * CV;
+// y[n][c] = sum_hw x[n][hw][c]: one thread per (n, 4 channels), the HW rows streamed with 4 loads in flight
+template <int VEC, class TX>
+__global__ __launch_bounds__(EW_BLOCK) void sum_pool_fwd_t_kernel(const TX* __restrict__ x, float* __restrict__ y, int N,
+                                                                   int HW, int C) {
+    const int CV = C / VEC;
+    const int64_t total = (int64_t)N * CV;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
         const int cv = (int)(i % CV);
-        int64_t t = i / CV;
-        const int wo = (int)(t % Wo);
-        t /= Wo;
-        const int ho = (int)(t % Ho);
-        const int n = (int)(t / Ho);
-        const int64_t base = (((int64_t)n * H + 2 * ho) * W + 2 * wo) * C + cv * VEC;
-        const int64_t o1 = C, o2 = (int64_t)W * C, o3 = (int64_t)W * C + C;
-        float a[VEC], b[VEC], c_[VEC], d[VEC], g[VEC];
-        loadv<VEC>(x + base, a);
-        loadv<VEC>(x + base + o1, b);
-        loadv<VEC>(x + base + o2, c_);
-        loadv<VEC>(x + base + o3, d);
-        loadv<VEC>(dy + i * VEC, g);
-        float ra[VEC], rb[VEC], rc[VEC], rd[VEC];
+        const int n = (int)(i / CV);
+        float s[VEC];
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const float m = fmaxf(fmaxf(a[j], b[j]), fmaxf(c_[j], d[j]));
-            // first maximum in window order (0,0),(0,1),(1,0),(1,1)
-            const bool sa = a[j] == m;
-            const bool sb = !sa && b[j] == m;
-            const bool sc = !sa && !sb && c_[j] == m;
-            const bool sd = !sa && !sb && !sc;
-            ra[j] = sa ? g[j] : 0.f;
-            rb[j] = sb ? g[j] : 0.f;
-            rc[j] = sc ? g[j] : 0.f;
-            rd[j] = sd ? g[j] : 0.f;
+        for (int j = 0; j < VEC; ++j) s[j] = 0.f;
+        for (int r = 0; r < HW; ++r) {
+            float v[VEC];
+            loadv<VEC>(x + ((int64_t)n * HW + r) * C + cv * VEC, v);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) s[j] += v[j];
         }
-        if constexpr (VEC == 4) {
-            stg4(dx + base, make_float4(ra[0], ra[1], ra[2], ra[VEC - 1]));
-            stg4(dx + base + o1, make_float4(rb[0], rb[1], rb[2], rb[VEC - 1]));
-            stg4(dx + base + o2, make_float4(rc[0], rc[1], rc[2], rc[VEC - 1]));
-            stg4(dx + base + o3, make_float4(rd[0], rd[1], rd[2], rd[VEC - 1]));
-        } else {
-            dx[base] = ra[0];
-            dx[base + o1] = rb[0];
-            dx[base + o2] = rc[0];
-            dx[base + o3] = rd[0];
-        }
+        storev<VEC>(y + (int64_t)n * C + cv * VEC, s);
     }
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void sum_pool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                 int N, int HW, int C) {
-    const int64_t total = (int64_t)N * C;
+template <int VEC, class TX>
+__global__ __launch_bounds__(EW_BLOCK) void sum_pool_bwd_t_kernel(const float* __restrict__ dy, TX* __restrict__ dx,
+                                                                   int N, int HW, int C) {
+    const int CV = C / VEC;
+    const int64_t total = (int64_t)N * HW * CV;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int c = (int)(i % C);
-        const int n = (int)(i / C);
-        float s = 0.f;
-        for (int r = 0; r < HW; ++r) s += x[((int64_t)n * HW + r) * C + c];
-        y[i] = s;
-    }
-}
-
-__global__ __launch_bounds__(EW_BLOCK) void sum_pool_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
-                                                                 int N, int HW, int C) {
-    const int64_t total = (int64_t)N * HW * C;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int c = (int)(i % C);
-        const int n = (int)(i / ((int64_t)HW * C));
-        dx[i] = dy[(int64_t)n * C + c];
+        const int cv = (int)(i % CV);
+        const int n = (int)(i / ((int64_t)HW * CV));
+        float v[VEC];
+        loadv<VEC>(dy + (int64_t)n * C + cv * VEC, v);
+        storev<VEC>(dx + i * VEC, v);
     }
 }
 
@@ -1021,17 +1289,42 @@ __global__ __launch_bounds__(EW_BLOCK) void scale_dev_kernel(const float* __rest
         y[i] = s * x[i];
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void dot_kernel(float* part, const float* __restrict__ a, const float* __restrict__ b,
-                                                        float* out, int64_t n) {
+// y = sa * a + sb * b (sa, sb: host scalars or device scalars when the pointers are non-null), n % 4 == 0
+template <class T>
+__global__ __launch_bounds__(EW_BLOCK) void lincomb_t_kernel(const T* __restrict__ a, const float* sa_dev, float sa,
+                                                              const T* __restrict__ b, float sb, T* __restrict__ y,
+                                                              int64_t n4) {
+    const float s = sa_dev ? *sa_dev : sa;
+    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += (int64_t)gridDim.x * EW_BLOCK) {
+        float av[4], bv[4], o[4];
+        loadv<4>(a + i * 4, av);
+        if (b) {
+            loadv<4>(b + i * 4, bv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = s * av[j] + sb * bv[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = s * av[j];
+        }
+        storev<4>(y + i * 4, o);
+    }
+}
+
+// sum of a[i] b[i] per block: groups of 4 elements, then the n % 4 elements of the tail one by one
+template <class T>
+__global__ __launch_bounds__(EW_BLOCK) void dot_t_kernel(float* part, const T* __restrict__ a, const T* __restrict__ b, float* out,
+                                                          int64_t n) {
     __shared__ float sh[4];
     float s = 0.f;
     const int64_t n4 = n / 4;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += (int64_t)gridDim.x * EW_BLOCK) {
-        float4 av = ldg4(a + i * 4), bv = ldg4(b + i * 4);
-        s += av.x * bv.x + av.y * bv.y + av.z * bv.z + av.w * bv.w;
+        float av[4], bv[4];
+        loadv<4>(a + i * 4, av);
+        loadv<4>(b + i * 4, bv);
+        s += av[0] * bv[0] + av[1] * bv[1] + av[2] * bv[2] + av[3] * bv[3];
     }
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EW_BLOCK)
-        s += a[i] * b[i];
+        s += (float)a[i] * (float)b[i];
     s = block_sum_256(s, sh);
     if (threadIdx.x == 0) {
         if (part)
@@ -1039,6 +1332,19 @@ __global__ __launch_bounds__(EW_BLOCK) void dot_kernel(float* part, const float*
         else
             *out += s;
     }
+}
+
+// out += <a, b>, any n (a, b 16-byte aligned): the per-block sums are added in a fixed order
+template <class T>
+static int launch_dot(const T* a, const T* b, float* out, int64_t n, hipStream_t s) {
+    int grid = ew_grid(n / 4 + 1);
+    if (grid > 512) grid = 512;
+    float* part = nullptr;
+    if (!block_partials(grid, 1, s, &part)) return BG_ERR_LAUNCH;
+    hipLaunchKernelGGL((dot_t_kernel<T>), dim3(grid), dim3(EW_BLOCK), 0, s, part, a, b, out, n);
+    finalize_block_partials(part, out, grid, 1, s);
+    BG_LAUNCH_CHECK();
+    return BG_OK;
 }
 
 __global__ __launch_bounds__(EW_BLOCK) void tanh_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -1053,59 +1359,9 @@ __global__ __launch_bounds__(EW_BLOCK) void tanh_bwd_kernel(const float* __restr
         dx[i] = dy[i] * (1.f - y[i] * y[i]);
 }
 
-
-// ==========================================================================================
-// Typed variants for the bf16-resident data path (BASELINE configs 3-5): the same arithmetic in fp32 registers,
-// activation tensors fp32 or bf16 in HBM (8-byte bf16x4 / 16-byte float4 accesses per thread).
-// ==========================================================================================
-template <int VEC>
-__device__ __forceinline__ void loadv(const __bf16* p, float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        const uint2 r = *reinterpret_cast<const uint2*>(p);
-        v[0] = __builtin_bit_cast(float, r.x << 16);
-        v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-        v[2] = __builtin_bit_cast(float, r.y << 16);
-        v[VEC - 1] = __builtin_bit_cast(float, r.y & 0xffff0000u);
-    } else if constexpr (VEC == 8) {
-        const uint4 r = *reinterpret_cast<const uint4*>(p);
-        v[0] = __builtin_bit_cast(float, r.x << 16); v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-        v[2] = __builtin_bit_cast(float, r.y << 16); v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
-        v[4] = __builtin_bit_cast(float, r.z << 16); v[5] = __builtin_bit_cast(float, r.z & 0xffff0000u);
-        v[6] = __builtin_bit_cast(float, r.w << 16); v[VEC - 1] = __builtin_bit_cast(float, r.w & 0xffff0000u);
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) v[j] = (float)p[j];
-    }
-}
-__device__ __forceinline__ uint32_t bf16_pack2(float a, float b) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    bf16x2_t v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;
-    return __builtin_bit_cast(uint32_t, v);
-}
-template <int VEC>
-__device__ __forceinline__ void storev(float* p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4)
-        stg4(p, make_float4(v[0], v[1], v[2], v[VEC - 1]));
-    else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) p[j] = v[j];
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void storev(__bf16* p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        uint2 r;
-        r.x = bf16_pack2(v[0], v[1]);
-        r.y = bf16_pack2(v[2], v[VEC - 1]);
-        *reinterpret_cast<uint2*>(p) = r;
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) p[j] = (__bf16)v[j];
-    }
-}
-
+// ------------------------------------------------------------------------------------------
+// channel padding / folding of the image layers, element-type casts
+// ------------------------------------------------------------------------------------------
 // Widen or narrow the middle dimension of an [outer][C][inner] view (Cs -> Cd entries), converting the element type.
 //   mode 0  zero fill / truncate:  dst[c] = c < Cs ? src[c] : 0
 //   mode 1  split (Cd >= 2 Cs):    dst[c] = hi = bf16(src[c]),  dst[Cs + c] = src[c] - hi,  rest 0
@@ -1191,487 +1447,6 @@ __global__ __launch_bounds__(EW_BLOCK) void cast_kernel(const TX* __restrict__ x
     }
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EW_BLOCK)
         y[i] = (TY)(float)x[i];
-}
-
-template <class TX>
-struct BnStatsFnT {
-    const TX* x;
-    int C;
-    template <int VEC>
-    __device__ __forceinline__ void operator()(int, int64_t r, int c, float (&acc)[2][VEC]) const {
-        float v[VEC];
-        loadv<VEC>(x + r * C + c, v);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            acc[0][j] += v[j];
-            acc[1][j] += v[j] * v[j];
-        }
-    }
-};
-
-template <int VEC, class TX, class TY>
-__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_fwd_t_kernel(const TX* __restrict__ x,
-                                                                       const float* __restrict__ mean,
-                                                                       const float* __restrict__ rstd,
-                                                                       const float* __restrict__ gamma,
-                                                                       const float* __restrict__ beta, int per_sample,
-                                                                       const float* __restrict__ alpha,
-                                                                       TY* __restrict__ y, int N, int HW, int C) {
-    const int CV = C / VEC;
-    const int64_t total = (int64_t)N * HW * CV;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int c = (int)(i % CV) * VEC;
-        const int n = (int)(i / ((int64_t)HW * CV));
-        const float* gp = gamma + (per_sample ? (int64_t)n * C : 0) + c;
-        const float* bp = beta + (per_sample ? (int64_t)n * C : 0) + c;
-        float xv[VEC], mu[VEC], rs[VEC], ga[VEC], be[VEC], al[VEC], out[VEC];
-        loadv<VEC>(x + i * VEC, xv);
-        loadv<VEC>(mean + c, mu);
-        loadv<VEC>(rstd + c, rs);
-        loadv<VEC>(gp, ga);
-        loadv<VEC>(bp, be);
-        if (alpha) loadv<VEC>(alpha + c, al);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const float inv = rs[j] * ga[j];
-            float v = xv[j] * inv + (be[j] - mu[j] * inv);
-            out[j] = alpha ? prelu_f(v, al[j]) : v;
-        }
-        storev<VEC>(y + i * VEC, out);
-    }
-}
-
-// ---- bf16 fast forms of batch-norm apply (+PReLU) and its input gradient --------------------------------------
-// The generic kernels above spend two 64-bit divisions and five to nine 16-byte coefficient loads per 8 bytes of
-// activation (measured r02: 2.9 - 3.3 TB/s of tensor traffic, ~10 % of a config-3 iteration).  Here a thread keeps ONE
-// group of 8 channels for its whole walk - the grid stride is a multiple of C / 8 - so the per-channel coefficients
-// sit in registers (reloaded only when a conditional batch norm moves to the next sample) and an item is one 16-byte
-// load, 8 FMAs + PReLU, one 16-byte store.
-__device__ __forceinline__ void bf16x8_load(const __bf16* p, float (&v)[8]) {
-    const uint4 r = *reinterpret_cast<const uint4*>(p);
-    v[0] = __builtin_bit_cast(float, r.x << 16); v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-    v[2] = __builtin_bit_cast(float, r.y << 16); v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
-    v[4] = __builtin_bit_cast(float, r.z << 16); v[5] = __builtin_bit_cast(float, r.z & 0xffff0000u);
-    v[6] = __builtin_bit_cast(float, r.w << 16); v[7] = __builtin_bit_cast(float, r.w & 0xffff0000u);
-}
-__device__ __forceinline__ void bf16x8_store(__bf16* p, const float (&v)[8]) {
-    uint4 r;
-    r.x = bf16_pack2(v[0], v[1]); r.y = bf16_pack2(v[2], v[3]); r.z = bf16_pack2(v[4], v[5]); r.w = bf16_pack2(v[6], v[7]);
-    *reinterpret_cast<uint4*>(p) = r;
-}
-__device__ __forceinline__ void f32x8_load(const float* p, float (&v)[8]) {
-    const float4 a = ldg4(p), b = ldg4(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-// rows = N * HW pixels of C = 8 CV channels; (gridDim.x * EW_BLOCK) % CV == 0
-__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_fwd_bf16x8_kernel(
-    const __bf16* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
-    const float* __restrict__ gamma, const float* __restrict__ beta, int per_sample, const float* __restrict__ alpha,
-    __bf16* __restrict__ y, int rows, int HW, int CV) {
-    const int gtid = blockIdx.x * EW_BLOCK + threadIdx.x;
-    const int cv = gtid % CV, c = cv * 8, C = CV * 8;
-    const int rstep = (gridDim.x * EW_BLOCK) / CV;
-    float mu[8], rs[8], al[8], inv[8], sh[8];
-    f32x8_load(mean + c, mu);
-    f32x8_load(rstd + c, rs);
-    if (alpha) f32x8_load(alpha + c, al);
-    int r_end = 0;                       // rows [.., r_end) share the coefficients in registers
-    for (int r = gtid / CV; r < rows; r += rstep) {
-        if (r >= r_end) {
-            const int n = per_sample ? r / HW : 0;
-            r_end = per_sample ? (n + 1) * HW : rows;
-            float ga[8], be[8];
-            f32x8_load(gamma + (int64_t)n * C * per_sample + c, ga);
-            f32x8_load(beta + (int64_t)n * C * per_sample + c, be);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                inv[j] = rs[j] * ga[j];
-                sh[j] = be[j] - mu[j] * inv[j];
-            }
-        }
-        float xv[8], out[8];
-        bf16x8_load(x + (int64_t)r * C + c, xv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v = xv[j] * inv[j] + sh[j];
-            out[j] = alpha ? prelu_f(v, al[j]) : v;
-        }
-        bf16x8_store(y + (int64_t)r * C + c, out);
-    }
-}
-
-__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_bwd_dx_bf16x8_kernel(
-    const __bf16* __restrict__ x, const __bf16* __restrict__ dy, const float* __restrict__ mean,
-    const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta, int per_sample,
-    const float* __restrict__ alpha, const float* __restrict__ cm, __bf16* dx, const __bf16* add, int rows, int HW,
-    int CV) {
-    // add (may alias dx): dx = add + gradient - the sum with the other branch of a forked tensor, fused (ops.py:253/263)
-    const int gtid = blockIdx.x * EW_BLOCK + threadIdx.x;
-    const int cv = gtid % CV, c = cv * 8, C = CV * 8;
-    const int rstep = (gridDim.x * EW_BLOCK) / CV;
-    float mu[8], rs[8], al[8], m1[8], m2[8], ga[8], be[8];
-    f32x8_load(mean + c, mu);
-    f32x8_load(rstd + c, rs);
-    f32x8_load(cm + c, m1);
-    f32x8_load(cm + C + c, m2);
-    if (alpha) f32x8_load(alpha + c, al);
-    int r_end = 0;
-    for (int r = gtid / CV; r < rows; r += rstep) {
-        if (r >= r_end) {
-            const int n = per_sample ? r / HW : 0;
-            r_end = per_sample ? (n + 1) * HW : rows;
-            f32x8_load(gamma + (int64_t)n * C * per_sample + c, ga);
-            f32x8_load(beta + (int64_t)n * C * per_sample + c, be);
-        }
-        float xv[8], dv[8], out[8];
-        bf16x8_load(x + (int64_t)r * C + c, xv);
-        bf16x8_load(dy + (int64_t)r * C + c, dv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float xh = (xv[j] - mu[j]) * rs[j];
-            const float pre = xh * ga[j] + be[j];
-            const float g = alpha ? dv[j] * prelu_d(pre, al[j]) : dv[j];
-            out[j] = rs[j] * (g * ga[j] - m1[j] - xh * m2[j]);
-        }
-        if (add) {
-            float av[8];
-            bf16x8_load(add + (int64_t)r * C + c, av);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) out[j] += av[j];
-        }
-        bf16x8_store(dx + (int64_t)r * C + c, out);
-    }
-}
-
-// stand-alone PReLU (ops.py:532) and its input gradient, same scheme
-template <bool BWD>
-__global__ __launch_bounds__(EW_BLOCK) void prelu_bf16x8_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ dy,
-                                                                 const float* __restrict__ alpha, __bf16* out,
-                                                                 const __bf16* add, int rows, int CV) {
-    const int gtid = blockIdx.x * EW_BLOCK + threadIdx.x;
-    const int c = (gtid % CV) * 8, C = CV * 8;
-    const int rstep = (gridDim.x * EW_BLOCK) / CV;
-    float al[8];
-    f32x8_load(alpha + c, al);
-    for (int r = gtid / CV; r < rows; r += rstep) {
-        float xv[8], dv[8], o[8];
-        bf16x8_load(x + (int64_t)r * C + c, xv);
-        if (BWD) bf16x8_load(dy + (int64_t)r * C + c, dv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = BWD ? dv[j] * prelu_d(xv[j], al[j]) : prelu_f(xv[j], al[j]);
-        if (BWD && add) {
-            float av[8];
-            bf16x8_load(add + (int64_t)r * C + c, av);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] += av[j];
-        }
-        bf16x8_store(out + (int64_t)r * C + c, o);
-    }
-}
-
-// y = sa a + sb b on bf16 tensors, 16 bytes per operand and item
-__global__ __launch_bounds__(EW_BLOCK) void lincomb_bf16x8_kernel(const __bf16* __restrict__ a, const float* sa_dev, float sa,
-                                                                   const __bf16* __restrict__ b, float sb,
-                                                                   __bf16* __restrict__ y, int64_t n8) {
-    const float s = sa_dev ? *sa_dev : sa;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n8; i += (int64_t)gridDim.x * EW_BLOCK) {
-        float av[8], bv[8], o[8];
-        bf16x8_load(a + i * 8, av);
-        if (b) {
-            bf16x8_load(b + i * 8, bv);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = s * av[j] + sb * bv[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = s * av[j];
-        }
-        bf16x8_store(y + i * 8, o);
-    }
-}
-
-// grid for the x8 kernels: enough blocks to fill the chip, a multiple of CV / gcd(CV, EW_BLOCK)
-static inline int bn_x8_grid(int64_t rows, int CV) {
-    int a = CV, b = EW_BLOCK;
-    while (b) { const int t = a % b; a = b; b = t; }
-    const int unit = CV / a;
-    int64_t want = (rows * CV + EW_BLOCK - 1) / EW_BLOCK;
-    if (want > 4096) want = 4096;
-    if (want < 1) want = 1;
-    return (int)((want + unit - 1) / unit * unit);
-}
-
-template <class TX, class TY>
-struct BnBwdReduceFnT {
-    const TX* x;
-    const TY* dy;
-    const float *mean, *rstd, *gamma, *beta, *alpha;
-    int per_sample, HW, C;
-    template <int VEC>
-    __device__ __forceinline__ void operator()(int n, int64_t r, int c, float (&acc)[3][VEC]) const {
-        const int64_t off = ((int64_t)n * HW + r) * C + c;
-        float xv[VEC], dv[VEC], mu[VEC], rs[VEC], ga[VEC], be[VEC], al[VEC];
-        loadv<VEC>(x + off, xv);
-        loadv<VEC>(dy + off, dv);
-        loadv<VEC>(mean + c, mu);
-        loadv<VEC>(rstd + c, rs);
-        loadv<VEC>(gamma + (per_sample ? (int64_t)n * C : 0) + c, ga);
-        loadv<VEC>(beta + (per_sample ? (int64_t)n * C : 0) + c, be);
-        if (alpha) loadv<VEC>(alpha + c, al);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const float xh = (xv[j] - mu[j]) * rs[j];
-            const float pre = xh * ga[j] + be[j];
-            const float g = alpha ? dv[j] * prelu_d(pre, al[j]) : dv[j];
-            acc[0][j] += g;
-            acc[1][j] += g * xh;
-            acc[2][j] += alpha ? dv[j] * fminf(pre, 0.f) : 0.f;
-        }
-    }
-};
-
-template <int VEC, class TX, class TY>
-__global__ __launch_bounds__(EW_BLOCK) void bn_apply_act_bwd_dx_t_kernel(
-    const TX* __restrict__ x, const TY* __restrict__ dy, const float* __restrict__ mean,
-    const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta, int per_sample,
-    const float* __restrict__ alpha, const float* __restrict__ cm, TX* dx, const TX* add, int N, int HW, int C) {
-    const int CV = C / VEC;
-    const int64_t total = (int64_t)N * HW * CV;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int c = (int)(i % CV) * VEC;
-        const int n = (int)(i / ((int64_t)HW * CV));
-        float xv[VEC], dv[VEC], mu[VEC], rs[VEC], ga[VEC], be[VEC], al[VEC], m1[VEC], m2[VEC], out[VEC];
-        loadv<VEC>(x + i * VEC, xv);
-        loadv<VEC>(dy + i * VEC, dv);
-        loadv<VEC>(mean + c, mu);
-        loadv<VEC>(rstd + c, rs);
-        loadv<VEC>(gamma + (per_sample ? (int64_t)n * C : 0) + c, ga);
-        loadv<VEC>(beta + (per_sample ? (int64_t)n * C : 0) + c, be);
-        loadv<VEC>(cm + c, m1);
-        loadv<VEC>(cm + C + c, m2);
-        if (alpha) loadv<VEC>(alpha + c, al);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const float xh = (xv[j] - mu[j]) * rs[j];
-            const float pre = xh * ga[j] + be[j];
-            const float g = alpha ? dv[j] * prelu_d(pre, al[j]) : dv[j];
-            out[j] = rs[j] * (g * ga[j] - m1[j] - xh * m2[j]);
-        }
-        if (add) {
-            float av[VEC];
-            loadv<VEC>(add + i * VEC, av);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) out[j] += av[j];
-        }
-        storev<VEC>(dx + i * VEC, out);
-    }
-}
-
-template <int VEC, class TX, class TY>
-__global__ __launch_bounds__(EW_BLOCK) void prelu_fwd_t_kernel(const TX* __restrict__ x, const float* __restrict__ alpha,
-                                                                TY* __restrict__ y, int64_t total_v, int C) {
-    const int CV = C / VEC;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total_v; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int c = (int)(i % CV) * VEC;
-        float xv[VEC], al[VEC], out[VEC];
-        loadv<VEC>(x + i * VEC, xv);
-        loadv<VEC>(alpha + c, al);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) out[j] = prelu_f(xv[j], al[j]);
-        storev<VEC>(y + i * VEC, out);
-    }
-}
-
-template <int VEC, class TX, class TY>
-__global__ __launch_bounds__(EW_BLOCK) void prelu_bwd_dx_t_kernel(const TX* __restrict__ x, const TY* __restrict__ dy,
-                                                                   const float* __restrict__ alpha, TX* dx, const TX* add,
-                                                                   int64_t total_v, int C) {
-    const int CV = C / VEC;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total_v; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int c = (int)(i % CV) * VEC;
-        float xv[VEC], dv[VEC], al[VEC], out[VEC];
-        loadv<VEC>(x + i * VEC, xv);
-        loadv<VEC>(dy + i * VEC, dv);
-        loadv<VEC>(alpha + c, al);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) out[j] = dv[j] * prelu_d(xv[j], al[j]);
-        if (add) {
-            float av[VEC];
-            loadv<VEC>(add + i * VEC, av);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) out[j] += av[j];
-        }
-        storev<VEC>(dx + i * VEC, out);
-    }
-}
-
-template <class TX, class TY>
-struct PreluDalphaFnT {
-    const TX* x;
-    const TY* dy;
-    int C;
-    template <int VEC>
-    __device__ __forceinline__ void operator()(int, int64_t r, int c, float (&acc)[1][VEC]) const {
-        float xv[VEC], dv[VEC];
-        loadv<VEC>(x + r * C + c, xv);
-        loadv<VEC>(dy + r * C + c, dv);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[0][j] += dv[j] * fminf(xv[j], 0.f);
-    }
-};
-
-template <class T>
-struct BiasGradFnT {
-    const T* dy;
-    int C;
-    template <int VEC>
-    __device__ __forceinline__ void operator()(int, int64_t r, int c, float (&acc)[1][VEC]) const {
-        float dv[VEC];
-        loadv<VEC>(dy + r * C + c, dv);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[0][j] += dv[j];
-    }
-};
-
-template <int VEC, class T>
-__global__ __launch_bounds__(EW_BLOCK) void maxpool2_fwd_t_kernel(const T* __restrict__ x, T* __restrict__ y, int N,
-                                                                   int H, int W, int C) {
-    const int CV = C / VEC, Ho = H / 2, Wo = W / 2;
-    const int64_t total = (int64_t)N * Ho * Wo * CV;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int cv = (int)(i % CV);
-        int64_t t = i / CV;
-        const int wo = (int)(t % Wo);
-        t /= Wo;
-        const int ho = (int)(t % Ho);
-        const int n = (int)(t / Ho);
-        const T* p = x + (((int64_t)n * H + 2 * ho) * W + 2 * wo) * C + cv * VEC;
-        float a[VEC], b[VEC], c_[VEC], d[VEC], o[VEC];
-        loadv<VEC>(p, a);
-        loadv<VEC>(p + C, b);
-        loadv<VEC>(p + (int64_t)W * C, c_);
-        loadv<VEC>(p + (int64_t)W * C + C, d);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) o[j] = fmaxf(fmaxf(a[j], b[j]), fmaxf(c_[j], d[j]));
-        storev<VEC>(y + i * VEC, o);
-    }
-}
-
-template <int VEC, class T>
-__global__ __launch_bounds__(EW_BLOCK) void maxpool2_bwd_t_kernel(const T* __restrict__ x, const T* __restrict__ dy,
-                                                                   T* __restrict__ dx, int N, int H, int W, int C) {
-    const int CV = C / VEC, Ho = H / 2, Wo = W / 2;
-    const int64_t total = (int64_t)N * Ho * Wo * CV;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int cv = (int)(i % CV);
-        int64_t t = i / CV;
-        const int wo = (int)(t % Wo);
-        t /= Wo;
-        const int ho = (int)(t % Ho);
-        const int n = (int)(t / Ho);
-        const int64_t base = (((int64_t)n * H + 2 * ho) * W + 2 * wo) * C + cv * VEC;
-        const int64_t o1 = C, o2 = (int64_t)W * C, o3 = (int64_t)W * C + C;
-        float a[VEC], b[VEC], c_[VEC], d[VEC], g[VEC];
-        loadv<VEC>(x + base, a);
-        loadv<VEC>(x + base + o1, b);
-        loadv<VEC>(x + base + o2, c_);
-        loadv<VEC>(x + base + o3, d);
-        loadv<VEC>(dy + i * VEC, g);
-        float ra[VEC], rb[VEC], rc[VEC], rd[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const float m = fmaxf(fmaxf(a[j], b[j]), fmaxf(c_[j], d[j]));
-            const bool sa = a[j] == m;
-            const bool sb = !sa && b[j] == m;
-            const bool sc = !sa && !sb && c_[j] == m;
-            const bool sd = !sa && !sb && !sc;
-            ra[j] = sa ? g[j] : 0.f;
-            rb[j] = sb ? g[j] : 0.f;
-            rc[j] = sc ? g[j] : 0.f;
-            rd[j] = sd ? g[j] : 0.f;
-        }
-        storev<VEC>(dx + base, ra);
-        storev<VEC>(dx + base + o1, rb);
-        storev<VEC>(dx + base + o2, rc);
-        storev<VEC>(dx + base + o3, rd);
-    }
-}
-
-// y[n][c] = sum_hw x[n][hw][c]: one thread per (n, 4 channels), the HW rows streamed with 4 loads in flight
-template <int VEC, class TX>
-__global__ __launch_bounds__(EW_BLOCK) void sum_pool_fwd_t_kernel(const TX* __restrict__ x, float* __restrict__ y, int N,
-                                                                   int HW, int C) {
-    const int CV = C / VEC;
-    const int64_t total = (int64_t)N * CV;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int cv = (int)(i % CV);
-        const int n = (int)(i / CV);
-        float s[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) s[j] = 0.f;
-        for (int r = 0; r < HW; ++r) {
-            float v[VEC];
-            loadv<VEC>(x + ((int64_t)n * HW + r) * C + cv * VEC, v);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) s[j] += v[j];
-        }
-        storev<VEC>(y + (int64_t)n * C + cv * VEC, s);
-    }
-}
-
-template <int VEC, class TX>
-__global__ __launch_bounds__(EW_BLOCK) void sum_pool_bwd_t_kernel(const float* __restrict__ dy, TX* __restrict__ dx,
-                                                                   int N, int HW, int C) {
-    const int CV = C / VEC;
-    const int64_t total = (int64_t)N * HW * CV;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * EW_BLOCK) {
-        const int cv = (int)(i % CV);
-        const int n = (int)(i / ((int64_t)HW * CV));
-        float v[VEC];
-        loadv<VEC>(dy + (int64_t)n * C + cv * VEC, v);
-        storev<VEC>(dx + i * VEC, v);
-    }
-}
-
-// y = sa * a + sb * b (sa, sb: host scalars or device scalars when the pointers are non-null), n % 4 == 0
-template <class T>
-__global__ __launch_bounds__(EW_BLOCK) void lincomb_t_kernel(const T* __restrict__ a, const float* sa_dev, float sa,
-                                                              const T* __restrict__ b, float sb, T* __restrict__ y,
-                                                              int64_t n4) {
-    const float s = sa_dev ? *sa_dev : sa;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += (int64_t)gridDim.x * EW_BLOCK) {
-        float av[4], bv[4], o[4];
-        loadv<4>(a + i * 4, av);
-        if (b) {
-            loadv<4>(b + i * 4, bv);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = s * av[j] + sb * bv[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = s * av[j];
-        }
-        storev<4>(y + i * 4, o);
-    }
-}
-
-template <class T>
-__global__ __launch_bounds__(EW_BLOCK) void dot_t_kernel(float* part, const T* __restrict__ a, const T* __restrict__ b, float* out,
-                                                          int64_t n4) {
-    __shared__ float sh[4];
-    float s = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += (int64_t)gridDim.x * EW_BLOCK) {
-        float av[4], bv[4];
-        loadv<4>(a + i * 4, av);
-        loadv<4>(b + i * 4, bv);
-        s += av[0] * bv[0] + av[1] * bv[1] + av[2] * bv[2] + av[3] * bv[3];
-    }
-    s = block_sum_256(s, sh);
-    if (threadIdx.x == 0) {
-        if (part)
-            part[blockIdx.x] = s;
-        else
-            *out += s;
-    }
 }
 
 // w / sigma for one [taps][R][Cc] weight plus its two bf16 packed copies (BgSnItem::pack_p / pack_t): 64 x 64 tiles
@@ -2236,14 +2011,6 @@ using namespace bg;
 
 extern "C" {
 
-int bg_bn_stats(const float* x, double* sums, int64_t rows, int C, void* stream) {
-    BG_REQUIRE(x && sums && rows > 0 && C > 0, "bg_bn_stats: bad argument");
-    BnStatsFn fn{x, C};
-    launch_colreduce<2>(fn, sums, (int64_t)C, rows, 1, C, as_stream(stream));
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
 int bg_bn_finalize(const double* sums, double count, float eps, float momentum, int unbiased_moving_var, float* mean,
                    float* rstd, float* moving_mean, float* moving_var, int C, void* stream) {
     BG_REQUIRE(sums && mean && rstd && C > 0 && count > 0, "bg_bn_finalize: bad argument");
@@ -2334,187 +2101,11 @@ int bg_renorm_affine_bwd(const float* dgamma_eff, const float* dbeta_eff, const 
     return BG_OK;
 }
 
-int bg_bn_apply_act_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
-                        int per_sample, const float* alpha, float* y, int N, int HW, int C, void* stream) {
-    BG_REQUIRE(x && mean && rstd && gamma && beta && y && N > 0 && HW > 0 && C > 0, "bg_bn_apply_act_fwd: bad argument");
-    const int64_t total = (int64_t)N * HW * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL((bn_apply_act_fwd_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0, as_stream(stream),
-                           x, mean, rstd, gamma, beta, per_sample, alpha, y, N, HW, C);
-    else
-        hipLaunchKernelGGL((bn_apply_act_fwd_kernel<1>), dim3(ew_grid(total)), dim3(EW_BLOCK), 0, as_stream(stream), x,
-                           mean, rstd, gamma, beta, per_sample, alpha, y, N, HW, C);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-int bg_bn_apply_act_bwd_reduce(const float* x, const float* dy, const float* mean, const float* rstd,
-                               const float* gamma, const float* beta, int per_sample, const float* alpha, float* part,
-                               int N, int HW, int C, void* stream) {
-    BG_REQUIRE(x && dy && mean && rstd && gamma && beta && part && N > 0 && HW > 0 && C > 0,
-               "bg_bn_apply_act_bwd_reduce: bad argument");
-    if (zero_async(part, sizeof(float) * 3 * (size_t)N * C, as_stream(stream)) != hipSuccess) {
-        set_error("bg_bn_apply_act_bwd_reduce: memset failed");
-        return BG_ERR_LAUNCH;
-    }
-    BnBwdReduceFn fn{x, dy, mean, rstd, gamma, beta, alpha, per_sample, HW, C};
-    launch_colreduce<3>(fn, part, (int64_t)N * C, HW, N, C, as_stream(stream));
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
 int bg_bn_bwd_finalize(const float* part, const float* gamma, int per_sample, double count, float* dgamma, float* dbeta,
                        float* dalpha, float* cm, int N, int C, void* stream) {
     BG_REQUIRE(part && gamma && dgamma && dbeta && cm && N > 0 && C > 0 && count > 0, "bg_bn_bwd_finalize: bad argument");
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, as_stream(stream), part, gamma,
                        per_sample, count, dgamma, dbeta, dalpha, cm, N, C);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-int bg_bn_apply_act_bwd_dx(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
-                           const float* beta, int per_sample, const float* alpha, const float* cm, float* dx, int N,
-                           int HW, int C, void* stream) {
-    BG_REQUIRE(x && dy && mean && rstd && gamma && beta && cm && dx && N > 0 && HW > 0 && C > 0,
-               "bg_bn_apply_act_bwd_dx: bad argument");
-    const int64_t total = (int64_t)N * HW * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL((bn_apply_act_bwd_dx_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0,
-                           as_stream(stream), x, dy, mean, rstd, gamma, beta, per_sample, alpha, cm, dx, N, HW, C);
-    else
-        hipLaunchKernelGGL((bn_apply_act_bwd_dx_kernel<1>), dim3(ew_grid(total)), dim3(EW_BLOCK), 0, as_stream(stream),
-                           x, dy, mean, rstd, gamma, beta, per_sample, alpha, cm, dx, N, HW, C);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-int bg_prelu_fwd(const float* x, const float* alpha, float* y, int64_t rows, int C, void* stream) {
-    BG_REQUIRE(x && alpha && y && rows > 0 && C > 0, "bg_prelu_fwd: bad argument");
-    const int64_t total = rows * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL((prelu_fwd_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0, as_stream(stream), x,
-                           alpha, y, total / 4, C);
-    else
-        hipLaunchKernelGGL((prelu_fwd_kernel<1>), dim3(ew_grid(total)), dim3(EW_BLOCK), 0, as_stream(stream), x, alpha,
-                           y, total, C);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-// d alpha of a PReLU on a tensor with C <= 4 channels (the discriminator's activation of the IMAGE, ops.py:299): the column
-// skeleton would put 3 threads of a row-lane on a row (4-byte loads, 0.6 TB/s); here a thread owns whole pixels, 4 in flight.
-__global__ __launch_bounds__(EW_BLOCK) void prelu_dalpha_thin_kernel(float* part, const float* __restrict__ x, const float* __restrict__ dy,
-                                                                     float* __restrict__ dalpha, int64_t rows, int C) {
-    __shared__ float red[4][EW_BLOCK];
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    const int64_t stride = (int64_t)gridDim.x * EW_BLOCK;
-    int64_t r = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x;
-    for (; r + 3 * stride < rows; r += 4 * stride) {
-        float xv[4][4], gv[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (c < C) {
-                    xv[u][c] = x[(r + u * stride) * C + c];
-                    gv[u][c] = dy[(r + u * stride) * C + c];
-                }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (c < C) acc[c] += xv[u][c] < 0.f ? gv[u][c] * xv[u][c] : 0.f;
-    }
-    for (; r < rows; r += stride)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (c < C) {
-                const float xs = x[r * C + c];
-                acc[c] += xs < 0.f ? dy[r * C + c] * xs : 0.f;
-            }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = acc[c];
-    __syncthreads();
-    for (int s = EW_BLOCK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
-        __syncthreads();
-    }
-    if ((int)threadIdx.x < C) {
-        if (part)
-            part[blockIdx.x * C + threadIdx.x] = red[threadIdx.x][0];
-        else
-            dalpha[threadIdx.x] += red[threadIdx.x][0];
-    }
-}
-
-int bg_prelu_bwd(const float* x, const float* dy, const float* alpha, float* dx, float* dalpha, int64_t rows, int C,
-                 void* stream) {
-    BG_REQUIRE(x && dy && alpha && rows > 0 && C > 0, "bg_prelu_bwd: bad argument");
-    const int64_t total = rows * C;
-    if (dx) {
-        if (C % 4 == 0)
-            hipLaunchKernelGGL((prelu_bwd_dx_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0, as_stream(stream),
-                               x, dy, alpha, dx, total / 4, C);
-        else
-            hipLaunchKernelGGL((prelu_bwd_dx_kernel<1>), dim3(ew_grid(total)), dim3(EW_BLOCK), 0, as_stream(stream), x,
-                               dy, alpha, dx, total, C);
-        BG_LAUNCH_CHECK();
-    }
-    if (dalpha) {
-        if (C <= 4 && rows >= (int64_t(1) << 16)) {
-            int grid = 256;
-            float* part = nullptr;
-            if (!block_partials(grid, C, as_stream(stream), &part)) return BG_ERR_LAUNCH;
-            hipLaunchKernelGGL(prelu_dalpha_thin_kernel, dim3(grid), dim3(EW_BLOCK), 0, as_stream(stream), part, x, dy,
-                               dalpha, rows, C);
-            finalize_block_partials(part, dalpha, grid, C, as_stream(stream));
-            BG_LAUNCH_CHECK();
-            return BG_OK;
-        }
-        PreluDalphaFn fn{x, dy, C};
-        launch_colreduce<1>(fn, dalpha, (int64_t)C, rows, 1, C, as_stream(stream));
-        BG_LAUNCH_CHECK();
-    }
-    return BG_OK;
-}
-
-int bg_bias_grad(const float* dy, float* db, int64_t rows, int C, void* stream) {
-    BG_REQUIRE(dy && db && rows > 0 && C > 0, "bg_bias_grad: bad argument");
-    if (zero_async(db, sizeof(float) * (size_t)C, as_stream(stream)) != hipSuccess) {
-        set_error("bg_bias_grad: memset failed");
-        return BG_ERR_LAUNCH;
-    }
-    BiasGradFn fn{dy, C};
-    launch_colreduce<1>(fn, db, (int64_t)C, rows, 1, C, as_stream(stream));
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-int bg_maxpool2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream) {
-    BG_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0, "bg_maxpool2_fwd: bad argument");
-    const int64_t total = (int64_t)N * (H / 2) * (W / 2) * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL((maxpool2_fwd_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0, as_stream(stream), x,
-                           y, N, H, W, C);
-    else
-        hipLaunchKernelGGL((maxpool2_fwd_kernel<1>), dim3(ew_grid(total)), dim3(EW_BLOCK), 0, as_stream(stream), x, y,
-                           N, H, W, C);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-int bg_maxpool2_bwd(const float* x, const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
-    BG_REQUIRE(x && dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0,
-               "bg_maxpool2_bwd: bad argument");
-    const int64_t total = (int64_t)N * (H / 2) * (W / 2) * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL((maxpool2_bwd_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0, as_stream(stream), x,
-                           dy, dx, N, H, W, C);
-    else
-        hipLaunchKernelGGL((maxpool2_bwd_kernel<1>), dim3(ew_grid(total)), dim3(EW_BLOCK), 0, as_stream(stream), x, dy,
-                           dx, N, H, W, C);
     BG_LAUNCH_CHECK();
     return BG_OK;
 }
@@ -2605,22 +2196,6 @@ int bg_prelu_tangent_dalpha(const float* x, const float* xdot, const float* dy, 
     return BG_OK;
 }
 
-int bg_sum_pool_fwd(const float* x, float* y, int N, int HW, int C, void* stream) {
-    BG_REQUIRE(x && y && N > 0 && HW > 0 && C > 0, "bg_sum_pool_fwd: bad argument");
-    hipLaunchKernelGGL(sum_pool_fwd_kernel, dim3(ew_grid((int64_t)N * C)), dim3(EW_BLOCK), 0, as_stream(stream), x, y,
-                       N, HW, C);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-int bg_sum_pool_bwd(const float* dy, float* dx, int N, int HW, int C, void* stream) {
-    BG_REQUIRE(dy && dx && N > 0 && HW > 0 && C > 0, "bg_sum_pool_bwd: bad argument");
-    hipLaunchKernelGGL(sum_pool_bwd_kernel, dim3(ew_grid((int64_t)N * HW * C)), dim3(EW_BLOCK), 0, as_stream(stream),
-                       dy, dx, N, HW, C);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
 int bg_axpby(const float* x, float a, float* y, float b, int64_t n, void* stream) {
     BG_REQUIRE(x && y && n > 0, "bg_axpby: bad argument");
     BG_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "bg_axpby: pointers must be 16-byte aligned");
@@ -2644,19 +2219,6 @@ int bg_scale_add(const float* o, const float* gamma_dev, const float* x, float* 
                "bg_scale_add: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(scale_add_kernel, dim3(ew_grid(n / 4 + 1)), dim3(EW_BLOCK), 0, as_stream(stream), o, gamma_dev,
                        x, y, n);
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-int bg_dot(const float* a, const float* b, float* out_accum, int64_t n, void* stream) {
-    BG_REQUIRE(a && b && out_accum && n > 0, "bg_dot: bad argument");
-    BG_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0, "bg_dot: pointers must be 16-byte aligned");
-    int grid = ew_grid(n / 4 + 1);
-    if (grid > 512) grid = 512;
-    float* part = nullptr;
-    if (!block_partials(grid, 1, as_stream(stream), &part)) return BG_ERR_LAUNCH;
-    hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(EW_BLOCK), 0, as_stream(stream), part, a, b, out_accum, n);
-    finalize_block_partials(part, out_accum, grid, 1, as_stream(stream));
     BG_LAUNCH_CHECK();
     return BG_OK;
 }
@@ -2748,13 +2310,8 @@ int bg_spectral_norm_bwd(const float* g_wnorm, const float* w_norm, const float*
         return BG_ERR_LAUNCH;
     }
     const int64_t n = (int64_t)rows * cols;
-    int grid = ew_grid(n / 4 + 1);
-    if (grid > 512) grid = 512;
-    float* part = nullptr;
-    if (!block_partials(grid, 1, s, &part)) return BG_ERR_LAUNCH;
-    hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(EW_BLOCK), 0, s, part, g_wnorm, w_norm, scr + 3, n);
-    finalize_block_partials(part, scr + 3, grid, 1, s);
-    BG_LAUNCH_CHECK();
+    const int rc = launch_dot(g_wnorm, w_norm, scr + 3, n, s);
+    if (rc != BG_OK) return rc;
     hipLaunchKernelGGL(sn_bwd_kernel, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, g_wnorm, u_hat, v_hat, sigma, scr + 3, dw,
                        rows, cols);
     BG_LAUNCH_CHECK();
@@ -3049,7 +2606,15 @@ int bg_prelu_bwd_t(const void* x, int x_dtype, const void* dy, int y_dtype, cons
                                               (const TX*)dx_add, total, C));
         BG_LAUNCH_CHECK();
     }
-    if (dalpha) {
+    if (dalpha && x_dtype == BG_F32 && y_dtype == BG_F32 && C <= 4 && rows >= (int64_t(1) << 16)) {
+        const int grid = 256;
+        float* part = nullptr;
+        if (!block_partials(grid, C, as_stream(stream), &part)) return BG_ERR_LAUNCH;
+        hipLaunchKernelGGL(prelu_dalpha_thin_kernel, dim3(grid), dim3(EW_BLOCK), 0, as_stream(stream), part,
+                           (const float*)x, (const float*)dy, dalpha, rows, C);
+        finalize_block_partials(part, dalpha, grid, C, as_stream(stream));
+        BG_LAUNCH_CHECK();
+    } else if (dalpha) {
         BG_DISPATCH_XY(x_dtype, y_dtype, PreluDalphaFnT<TX, TY> fn{(const TX*)x, (const TY*)dy, C};
                        launch_colreduce<1, sizeof(TX) == 2 && sizeof(TY) == 2>(fn, dalpha, 0, rows, 1, C,
                                                                                as_stream(stream)));
@@ -3140,15 +2705,71 @@ int bg_lincomb_t(const void* a, const float* sa_dev, float sa, const void* b, fl
 
 int bg_dot_t(const void* a, const void* b, int dtype, float* out_accum, int64_t n, void* stream) {
     BG_REQUIRE(a && b && out_accum && n > 0 && n % 4 == 0 && BG_DT_OK(dtype), "bg_dot_t: bad argument (n %% 4 == 0)");
-    int blocks = ew_grid(n / 4);
-    if (blocks > 512) blocks = 512;
-    float* part = nullptr;
-    if (!block_partials(blocks, 1, as_stream(stream), &part)) return BG_ERR_LAUNCH;
-    BG_DISPATCH_T(dtype, hipLaunchKernelGGL((dot_t_kernel<T>), dim3(blocks), dim3(EW_BLOCK), 0, as_stream(stream), part,
-                                            (const T*)a, (const T*)b, out_accum, n / 4));
-    finalize_block_partials(part, out_accum, blocks, 1, as_stream(stream));
-    BG_LAUNCH_CHECK();
-    return BG_OK;
+    int rc = BG_OK;
+    BG_DISPATCH_T(dtype, rc = launch_dot((const T*)a, (const T*)b, out_accum, n, as_stream(stream)));
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// fp32 entry points of the same family: each is its "_t" entry with BG_F32 and no dx_add, so a rejected call
+// names the "_t" entry in bg_last_error.  bg_dot alone differs from its twin: it takes any n.
+// ------------------------------------------------------------------------------------------
+int bg_bn_stats(const float* x, double* sums, int64_t rows, int C, void* stream) {
+    return bg_bn_stats_t(x, BG_F32, sums, rows, C, stream);
+}
+
+int bg_bn_apply_act_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        int per_sample, const float* alpha, float* y, int N, int HW, int C, void* stream) {
+    return bg_bn_apply_act_fwd_t(x, BG_F32, mean, rstd, gamma, beta, per_sample, alpha, y, BG_F32, N, HW, C, stream);
+}
+
+int bg_bn_apply_act_bwd_reduce(const float* x, const float* dy, const float* mean, const float* rstd,
+                               const float* gamma, const float* beta, int per_sample, const float* alpha, float* part,
+                               int N, int HW, int C, void* stream) {
+    return bg_bn_apply_act_bwd_reduce_t(x, BG_F32, dy, BG_F32, mean, rstd, gamma, beta, per_sample, alpha, part, N, HW, C,
+                                        stream);
+}
+
+int bg_bn_apply_act_bwd_dx(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, int per_sample, const float* alpha, const float* cm, float* dx, int N,
+                           int HW, int C, void* stream) {
+    return bg_bn_apply_act_bwd_dx_t(x, BG_F32, dy, BG_F32, mean, rstd, gamma, beta, per_sample, alpha, cm, dx, NULL, N, HW,
+                                    C, stream);
+}
+
+int bg_prelu_fwd(const float* x, const float* alpha, float* y, int64_t rows, int C, void* stream) {
+    return bg_prelu_fwd_t(x, BG_F32, alpha, y, BG_F32, rows, C, stream);
+}
+
+int bg_prelu_bwd(const float* x, const float* dy, const float* alpha, float* dx, float* dalpha, int64_t rows, int C,
+                 void* stream) {
+    return bg_prelu_bwd_t(x, BG_F32, dy, BG_F32, alpha, dx, dalpha, NULL, rows, C, stream);
+}
+
+int bg_bias_grad(const float* dy, float* db, int64_t rows, int C, void* stream) {
+    return bg_bias_grad_t(dy, BG_F32, db, rows, C, stream);
+}
+
+int bg_maxpool2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream) {
+    return bg_maxpool2_fwd_t(x, y, BG_F32, N, H, W, C, stream);
+}
+
+int bg_maxpool2_bwd(const float* x, const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
+    return bg_maxpool2_bwd_t(x, dy, dx, BG_F32, N, H, W, C, stream);
+}
+
+int bg_sum_pool_fwd(const float* x, float* y, int N, int HW, int C, void* stream) {
+    return bg_sum_pool_fwd_t(x, BG_F32, y, N, HW, C, stream);
+}
+
+int bg_sum_pool_bwd(const float* dy, float* dx, int N, int HW, int C, void* stream) {
+    return bg_sum_pool_bwd_t(dy, dx, BG_F32, N, HW, C, stream);
+}
+
+int bg_dot(const float* a, const float* b, float* out_accum, int64_t n, void* stream) {
+    BG_REQUIRE(a && b && out_accum && n > 0, "bg_dot: bad argument");
+    BG_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0, "bg_dot: pointers must be 16-byte aligned");
+    return launch_dot(a, b, out_accum, n, as_stream(stream));
 }
 
 }  // extern "C"

@@ -253,6 +253,12 @@ def _fork_target(fk, like):
     return torch.empty_like(like), False
 
 
+def _fused_fork(fk, x, dy):
+    """``fk`` where batch-norm / PReLU backward fuses the fork sum into its dx (``dx_add``): not on the all-fp32 path,
+    whose branches each write their own tensor - there the fused sum would add in another order."""
+    return None if x.dtype == torch.float32 and dy.dtype == torch.float32 else fk
+
+
 def _fork_done(fk, dx):
     if fk is not None and dx is not None:
         fk.buf = dx
@@ -405,10 +411,7 @@ def zeros(n, dtype, device):
 
 
 def _bias_grad(dy2d, out):
-    if dy2d.dtype == torch.float32:
-        check(lib().bg_bias_grad(f32(dy2d), f32(out), dy2d.shape[0], dy2d.shape[1], stream()))
-    else:
-        check(lib().bg_bias_grad_t(act(dy2d), dt(dy2d), f32(out), dy2d.shape[0], dy2d.shape[1], stream()))
+    check(lib().bg_bias_grad_t(act(dy2d), dt(dy2d), f32(out), dy2d.shape[0], dy2d.shape[1], stream()))
 
 
 # ------------------------------------------------------------------------------------------
@@ -1517,7 +1520,6 @@ class BnActFn(Function):
         pre_sums = getattr(x, "bg_bn_sums", None)      # left by the producing kernel's epilogue (Deconv2dFn stats_box)
         x = _c(x)
         ydt = out_dtype or x.dtype
-        typed = x.dtype != torch.float32 or ydt != torch.float32
         N, H, W_, C = x.shape
         HW = H * W_
         per_sample = int(gamma.dim() == 2)
@@ -1531,10 +1533,7 @@ class BnActFn(Function):
                 sums = pre_sums
             else:
                 sums = zeros(2 * C, torch.float64, dev)
-                if typed:
-                    check(L.bg_bn_stats_t(act(x), dt(x), hip.ptr(sums), N * HW, C, stream()))
-                else:
-                    check(L.bg_bn_stats(f32(x), hip.ptr(sums), N * HW, C, stream()))
+                check(L.bg_bn_stats_t(act(x), dt(x), hip.ptr(sums), N * HW, C, stream()))
             if reduce_fn is not None:
                 reduce_fn(sums)
             if renorm is not None:          # corrections first: they read the running statistics before any update
@@ -1559,13 +1558,8 @@ class BnActFn(Function):
                                          gamma_c.numel() // C, C, stream()))
             gamma_c, beta_c = g_eff, b_eff
             ctx.renorm_rd = (r_, d_)
-        if typed:
-            check(L.bg_bn_apply_act_fwd_t(act(x), dt(x), f32(mean), f32(rstd), f32(gamma_c), f32(beta_c), per_sample,
-                                          f32(alpha), act(y), dt(y), N, HW, C, stream()))
-        else:
-            check(L.bg_bn_apply_act_fwd(f32(x), f32(mean), f32(rstd), f32(gamma_c), f32(beta_c), per_sample,
-                                        f32(alpha), f32(y), N, HW, C, stream()))
-        ctx.typed = typed
+        check(L.bg_bn_apply_act_fwd_t(act(x), dt(x), f32(mean), f32(rstd), f32(gamma_c), f32(beta_c), per_sample,
+                                      f32(alpha), act(y), dt(y), N, HW, C, stream()))
         if KinkProbe.sites is not None and alpha is not None:
             KinkProbe.sites.append((getattr(alpha, "bg_name", None), "bn", x.detach().float().clone(), mean.clone(),
                                     rstd.clone(), gamma_c.detach().clone(), beta_c.detach().clone(), per_sample))
@@ -1589,12 +1583,8 @@ class BnActFn(Function):
         dev = x.device
         ps = ctx.per_sample
         part = torch.empty((3, N, C), dtype=torch.float32, device=dev)
-        if ctx.typed:
-            check(L.bg_bn_apply_act_bwd_reduce_t(act(x), dt(x), act(dy), dt(dy), f32(mean), f32(rstd), f32(ctx.gamma_c),
-                                                 f32(ctx.beta_c), ps, f32(alpha), f32(part), N, HW, C, stream()))
-        else:
-            check(L.bg_bn_apply_act_bwd_reduce(f32(x), f32(dy), f32(mean), f32(rstd), f32(ctx.gamma_c), f32(ctx.beta_c),
-                                               ps, f32(alpha), f32(part), N, HW, C, stream()))
+        check(L.bg_bn_apply_act_bwd_reduce_t(act(x), dt(x), act(dy), dt(dy), f32(mean), f32(rstd), f32(ctx.gamma_c),
+                                             f32(ctx.beta_c), ps, f32(alpha), f32(part), N, HW, C, stream()))
         gshape = (N, C) if ps else (C,)
         dgamma = torch.empty(gshape, dtype=torch.float32, device=dev)
         dbeta = torch.empty(gshape, dtype=torch.float32, device=dev)
@@ -1614,16 +1604,12 @@ class BnActFn(Function):
             ctx.reduce_fn(cm)
         dx = None
         if ctx.needs_input_grad[0]:
-            if ctx.typed:
-                dx, add = _fork_target(ctx.fork, x)
-                check(L.bg_bn_apply_act_bwd_dx_t(act(x), dt(x), act(dy), dt(dy), f32(mean), f32(rstd), f32(ctx.gamma_c),
-                                                 f32(ctx.beta_c), ps, f32(alpha), f32(cm), act(dx), act(dx) if add else None,
-                                                 N, HW, C, stream()))
-                _fork_done(ctx.fork, dx)
-            else:
-                dx = torch.empty_like(x)
-                check(L.bg_bn_apply_act_bwd_dx(f32(x), f32(dy), f32(mean), f32(rstd), f32(ctx.gamma_c), f32(ctx.beta_c),
-                                               ps, f32(alpha), f32(cm), f32(dx), N, HW, C, stream()))
+            fork = _fused_fork(ctx.fork, x, dy)
+            dx, add = _fork_target(fork, x)
+            check(L.bg_bn_apply_act_bwd_dx_t(act(x), dt(x), act(dy), dt(dy), f32(mean), f32(rstd), f32(ctx.gamma_c),
+                                             f32(ctx.beta_c), ps, f32(alpha), f32(cm), act(dx), act(dx) if add else None,
+                                             N, HW, C, stream()))
+            _fork_done(fork, dx)
 
         def deliver(t, needed, g):
             if not needed:
@@ -1650,10 +1636,7 @@ class PReluFn(Function):
         if KinkProbe.sites is not None:
             KinkProbe.sites.append((getattr(alpha, "bg_name", None), "act", x.detach().float().clone()))
         y = torch.empty_like(x)
-        if x.dtype == torch.float32:
-            check(lib().bg_prelu_fwd(f32(x), f32(alpha), f32(y), x.numel() // C, C, stream()))
-        else:
-            check(lib().bg_prelu_fwd_t(act(x), dt(x), f32(alpha), act(y), dt(y), x.numel() // C, C, stream()))
+        check(lib().bg_prelu_fwd_t(act(x), dt(x), f32(alpha), act(y), dt(y), x.numel() // C, C, stream()))
         ctx.x, ctx.alpha = x, alpha
         return y
 
@@ -1665,23 +1648,16 @@ class PReluFn(Function):
         rows = x.numel() // C
         L = lib()
         dx = None
-        f32s = x.dtype == torch.float32 and dy.dtype == torch.float32
         if ctx.needs_input_grad[0]:
-            if f32s:
-                dx = torch.empty_like(x)
-                check(L.bg_prelu_bwd(f32(x), f32(dy), f32(alpha), f32(dx), None, rows, C, stream()))
-            else:
-                dx, add = _fork_target(ctx.fork, x)
-                check(L.bg_prelu_bwd_t(act(x), dt(x), act(dy), dt(dy), f32(alpha), act(dx), None, act(dx) if add else None,
-                                       rows, C, stream()))
-                _fork_done(ctx.fork, dx)
+            fork = _fused_fork(ctx.fork, x, dy)
+            dx, add = _fork_target(fork, x)
+            check(L.bg_prelu_bwd_t(act(x), dt(x), act(dy), dt(dy), f32(alpha), act(dx), None, act(dx) if add else None,
+                                   rows, C, stream()))
+            _fork_done(fork, dx)
 
         def prod(out):
             out.zero_()
-            if f32s:
-                check(L.bg_prelu_bwd(f32(x), f32(dy), f32(alpha), None, f32(out), rows, C, stream()))
-            else:
-                check(L.bg_prelu_bwd_t(act(x), dt(x), act(dy), dt(dy), f32(alpha), None, f32(out), None, rows, C, stream()))
+            check(L.bg_prelu_bwd_t(act(x), dt(x), act(dy), dt(dy), f32(alpha), None, f32(out), None, rows, C, stream()))
         da = param_grad(alpha, ctx.needs_input_grad[1], prod)
         ctx.x = None
         return dx, da
@@ -1696,10 +1672,7 @@ class MaxPool2Fn(Function):
         x = _c(x)
         N, H, W_, C = x.shape
         y = torch.empty((N, H // 2, W_ // 2, C), dtype=x.dtype, device=x.device)
-        if x.dtype == torch.float32:
-            check(lib().bg_maxpool2_fwd(f32(x), f32(y), N, H, W_, C, stream()))
-        else:
-            check(lib().bg_maxpool2_fwd_t(act(x), act(y), dt(x), N, H, W_, C, stream()))
+        check(lib().bg_maxpool2_fwd_t(act(x), act(y), dt(x), N, H, W_, C, stream()))
         ctx.x = x
         return y
 
@@ -1709,10 +1682,7 @@ class MaxPool2Fn(Function):
         x = ctx.x
         N, H, W_, C = x.shape
         dx = torch.empty_like(x)
-        if x.dtype == torch.float32:
-            check(lib().bg_maxpool2_bwd(f32(x), f32(dy), f32(dx), N, H, W_, C, stream()))
-        else:
-            check(lib().bg_maxpool2_bwd_t(act(x), act(cast(dy, x.dtype)), act(dx), dt(x), N, H, W_, C, stream()))
+        check(lib().bg_maxpool2_bwd_t(act(x), act(cast(dy, x.dtype)), act(dx), dt(x), N, H, W_, C, stream()))
         ctx.x = None
         return dx
 
@@ -1814,10 +1784,7 @@ class BnGluFn(Function):
         rstd = torch.empty(C2, dtype=torch.float32, device=dev)
         count = float(rows * world)
         sums = zeros(2 * C2, torch.float64, dev)
-        if x.dtype == torch.float32:
-            check(L.bg_bn_stats(f32(x), hip.ptr(sums), rows, C2, stream()))
-        else:
-            check(L.bg_bn_stats_t(act(x), dt(x), hip.ptr(sums), rows, C2, stream()))
+        check(L.bg_bn_stats_t(act(x), dt(x), hip.ptr(sums), rows, C2, stream()))
         if reduce_fn is not None:
             reduce_fn(sums)
         check(L.bg_bn_finalize(hip.ptr(sums), count, eps, momentum, int(unbiased_mv), f32(mean), f32(rstd),
@@ -1943,10 +1910,7 @@ class SumPoolFn(Function):
         x = _c(x)
         N, H, W_, C = x.shape
         y = torch.empty((N, C), dtype=torch.float32, device=x.device)
-        if x.dtype == torch.float32:
-            check(lib().bg_sum_pool_fwd(f32(x), f32(y), N, H * W_, C, stream()))
-        else:
-            check(lib().bg_sum_pool_fwd_t(act(x), dt(x), f32(y), N, H * W_, C, stream()))
+        check(lib().bg_sum_pool_fwd_t(act(x), dt(x), f32(y), N, H * W_, C, stream()))
         ctx.shape = x.shape
         ctx.xdt = x.dtype
         return y
@@ -1956,10 +1920,7 @@ class SumPoolFn(Function):
         dy = _c(dy)
         N, H, W_, C = ctx.shape
         dx = torch.empty(ctx.shape, dtype=ctx.xdt, device=dy.device)
-        if ctx.xdt == torch.float32:
-            check(lib().bg_sum_pool_bwd(f32(dy), f32(dx), N, H * W_, C, stream()))
-        else:
-            check(lib().bg_sum_pool_bwd_t(f32(dy), act(dx), dt(dx), N, H * W_, C, stream()))
+        check(lib().bg_sum_pool_bwd_t(f32(dy), act(dx), dt(dx), N, H * W_, C, stream()))
         return dx
 
 
@@ -2196,7 +2157,7 @@ class ScaleAddFn(Function):
 
         def prod(out):
             out.zero_()
-            if dy.dtype == torch.float32:
+            if dy.numel() % 4:          # (fp32 only: bg_dot takes any n, bg_dot_t whole groups of 4)
                 check(L.bg_dot(f32(dy), f32(o), f32(out), dy.numel(), stream()))
             else:
                 check(L.bg_dot_t(act(dy), act(o), dt(dy), f32(out), dy.numel(), stream()))
@@ -2283,7 +2244,8 @@ class PReluTangentFn(Function):
         xdot, x = _c(xdot), _c(x)
         C = x.shape[-1]
         y = torch.empty_like(x)
-        check(lib().bg_prelu_bwd(f32(x), f32(xdot), f32(alpha), f32(y), None, x.numel() // C, C, stream()))
+        check(lib().bg_prelu_bwd_t(act(x), dt(x), act(xdot), dt(xdot), f32(alpha), act(y), None, None, x.numel() // C, C,
+                                   stream()))
         ctx.xdot, ctx.x, ctx.alpha = xdot, x, alpha
         return y
 
@@ -2297,7 +2259,7 @@ class PReluTangentFn(Function):
         dxdot = None
         if ctx.needs_input_grad[0]:
             dxdot = torch.empty_like(x)
-            check(L.bg_prelu_bwd(f32(x), f32(dy), f32(alpha), f32(dxdot), None, rows, C, stream()))
+            check(L.bg_prelu_bwd_t(act(x), dt(x), act(dy), dt(dy), f32(alpha), act(dxdot), None, None, rows, C, stream()))
 
         def prod(out):
             check(L.bg_prelu_tangent_dalpha(f32(x), f32(xdot), f32(dy), f32(out), rows, C, stream()))
@@ -2324,7 +2286,7 @@ class MaxPool2TangentFn(Function):
         x = ctx.x
         N, H, W_, C = x.shape
         d = torch.empty_like(x)
-        check(lib().bg_maxpool2_bwd(f32(x), f32(dy), f32(d), N, H, W_, C, stream()))
+        check(lib().bg_maxpool2_bwd_t(f32(x), f32(dy), f32(d), hip.F32, N, H, W_, C, stream()))
         ctx.x = None
         return d, None
 

@@ -1017,7 +1017,7 @@ class BigGAN(GANBase):
         xhat = torch.empty_like(real)
         if self.gradient_penalty_type == 'dragan':
             sums = torch.zeros(2, dtype=torch.float64, device=self.device)
-            Fn.check(L.bg_bn_stats(Fn.f32(real), Fn.hip.ptr(sums), real.numel(), 1, Fn.stream()))
+            Fn.check(L.bg_bn_stats_t(Fn.f32(real), Fn.hip.F32, Fn.hip.ptr(sums), real.numel(), 1, Fn.stream()))
             if self._reduce_fn() is not None:          # the moments of the GLOBAL real batch (BigGAN.py:720)
                 self._reduce_fn()(sums)
             Fn.check(L.bg_gp_interpolate(Fn.f32(real), Fn.f32(draws["eps"].contiguous()), Fn.f32(draws["alpha"]),

@@ -408,6 +408,8 @@ int bg_gram16(const void* a, int rows, int cols, int ld, float* out, void* ws, s
  *   apply: y = act((x - mean) * rstd * gamma + beta), gamma/beta per sample [N,C] (per_sample=1,
  *   condition_batch_norm) or per channel [C] (tf.layers.batch_normalization);
  *   act = PReLU with per-channel alpha when alpha != NULL (ops.py:535-537), identity otherwise.
+ *   The entries that take activation tensors (here and below: PReLU, pooling, bg_bias_grad) forward to their "_t"
+ *   forms with BG_F32 - see "bf16-resident data path".
  * ------------------------------------------------------------------------------------------ */
 int bg_bn_stats(const float* x, double* sums, int64_t rows, int C, void* stream);
 int bg_bn_finalize(const double* sums, double count, float eps, float momentum, int unbiased_moving_var,
@@ -522,8 +524,12 @@ int bg_alpha_mask_tangent(const float* x, const float* xdot, float* ydot, int64_
  * accesses) - except column reductions (statistics, backward reduce, dalpha, bias gradient) over 16 Mi elements or
  * more, which read 16 bytes at C % 8 == 0 and need 16-byte alignment; any other C (the image layers' 3 and 6) goes one
  * element per thread.  fp32 tensors: 16-byte aligned when C % 4 == 0.  bg_lincomb_t / bg_dot_t: n % 4 == 0, bf16
- * tensors 8-byte aligned.  Same formulas and reference call sites as the fp32 entry points of the same name;
- * tests/test_gpu_elementwise16.py holds every one of these forms to a float64 reference.
+ * tensors 8-byte aligned.  tests/test_gpu_elementwise16.py holds every one of these forms to a float64 reference.
+ * These ARE the implementation of the fp32 entry points of the same name (bg_bn_stats, bg_bn_apply_act_fwd /
+ * _bwd_reduce / _bwd_dx, bg_prelu_fwd / _bwd, bg_bias_grad, bg_maxpool2_fwd / _bwd, bg_sum_pool_fwd / _bwd): each of
+ * those calls its "_t" entry with BG_F32 and dx_add = NULL, so a call it rejects names the "_t" entry in
+ * bg_last_error.  bg_dot runs bg_dot_t's kernel too but keeps its own check: it takes any n.  An fp32 / fp32
+ * bg_prelu_bwd(_t) with C <= 4 and rows >= 65536 (the PReLU of the image) sums dalpha with whole pixels per thread.
  * ------------------------------------------------------------------------------------------ */
 int bg_cast(const void* x, int x_dtype, void* y, int y_dtype, int64_t n, void* stream);
 /* tf.nn.depth_to_space (ops.py:27) and its inverse / adjoint, NHWC, block size r (csrc/subpixel.hip):

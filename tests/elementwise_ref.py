@@ -19,7 +19,8 @@ Test helper, not product code.  Three parts:
   case must stay <= AMBIGUITY_CAP (continuous data: ~ E_pre / sigma ~ 1e-6).  Exact zeros planted for the alpha / 2
   rule go through the stand-alone PReLU, whose argument is the stored value: never ambiguous.
 * CASES - the table both test modules walk: the (N, HW, C) of the batch-norm, PReLU, residual-add, max-pool and
-  bias-gradient sites of BASELINE config 3 at batch 256, and small edge shapes for every dispatch fallback.
+  bias-gradient sites of BASELINE config 3 at batch 256, and small edge shapes for every dispatch fallback (the thin
+  slope-gradient path of fp32 tensors with C <= 4 and bg_dot's n % 4 != 0 among them).
 """
 import torch
 
@@ -208,6 +209,9 @@ def select(got, r):
 # ------------------------------------------------------------------------------------------
 # the case table
 # ------------------------------------------------------------------------------------------
+# ops whose fp32-only entry point ("bg_X" next to "bg_X_t") the GPU test also calls on the fp32 / fp32 rows without dx_add
+FP32_ENTRY = ("bn_stats", "bn_fwd", "bn_bwd_reduce", "bn_bwd_dx", "prelu_fwd", "prelu_bwd", "bias_grad", "maxpool_fwd",
+              "maxpool_bwd", "sum_pool_fwd", "sum_pool_bwd", "dot")
 OPS = ("bn_stats", "bn_fwd", "bn_bwd_reduce", "bn_bwd_dx", "prelu_fwd", "prelu_bwd", "bias_grad", "maxpool_fwd",
        "maxpool_bwd", "sum_pool_fwd", "sum_pool_bwd", "lincomb", "dot", "cast")
 TWO_DTYPES = ("bn_fwd", "bn_bwd_reduce", "bn_bwd_dx", "prelu_fwd", "prelu_bwd")
@@ -381,6 +385,16 @@ def _edge():
         out.append(case("prelu_fwd", "4x256x%d zeros" % C, why, **kw))
         out.append(case("prelu_bwd", "4x256x%d zeros" % C, why, **kw))
         out.append(case("prelu_bwd", "4x256x%d zeros add-alias" % C, why, add="alias", **kw))
+    # the thin slope-gradient path of an fp32 / fp32 bg_prelu_bwd(_t): C <= 4 and >= 65536 rows (the PReLU of the image) -
+    # 256 blocks x 256 threads that own whole pixels, 4 in flight, instead of the column reduction
+    for rows, C, both, why in ((65535, 3, False, "one row short of the thin path: the column reduction"),
+                               (65536, 1, False, "first thin shape, one grid stride: the tail loop only"),
+                               (65536, 3, False, "first thin shape, one grid stride: the tail loop only"),
+                               (65536, 4, False, "first thin shape, one grid stride: the tail loop only"),
+                               (4 * 65536 + 1000, 3, False, "thin path: the unrolled loop, then the tail"),
+                               (65536, 3, True, "thin path: the dx and the dalpha launch of one call")):
+        out.append(case("prelu_bwd", "thin %dx%d f/f %s" % (rows, C, "dx + dalpha" if both else "dalpha only"), why,
+                        N=1, HW=rows, C=C, xdt=F32, ydt=F32, add="none" if both else "null-dx", small=True))
     # bg_lincomb_t / bg_dot_t / bg_cast: n % 8 == 4, the device scalar (host sa poisoned), b == NULL, fp32, a second
     # grid-stride step of the x8 form (n > 2048 blocks x 256 threads x 8)
     for dt in (BF16, F32):
@@ -391,6 +405,9 @@ def _edge():
                     out.append(case("lincomb", nm, "n %% 8 == %d, sa_dev %d, b %d" % (n % 8, dev, b), n=n, xdt=dt, ydt=dt,
                                     sa_dev=dev, b=b, small=True))
             out.append(case("dot", "n%d %s" % (n, "fb"[dt]), "n %% 8 == %d" % (n % 8), n=n, xdt=dt, ydt=dt, small=True))
+    for n in (6, 4 * 65536 + 3):        # fp32 through bg_dot alone: bg_dot_t refuses n % 4 != 0
+        out.append(case("dot", "n%d f bg_dot" % n, "n %% 4 == %d: the scalar tail (and 2 blocks' worth of groups)" % (n % 4),
+                        n=n, xdt=F32, ydt=F32, small=True))
     out.append(case("lincomb", "n5242884 dev1", "second grid-stride step of the x8 form... n % 8 == 4: 4-element form",
                     n=5 * (1 << 20) + 4, sa_dev=True, small=True))
     out.append(case("lincomb", "n5242880 dev1", "second grid-stride step of the x8 form", n=5 * (1 << 20), sa_dev=True,

@@ -5,7 +5,10 @@ shapes of BASELINE config 3 at batch 256, and small shapes for each dispatch fal
 ``hip.lib()`` on guarded buffers (launch_replay.Buf): outputs prefilled with NaN (or their initial value where the call
 accumulates or aliases), two runs that must agree bit for bit, guard bands before and after every buffer, inputs left
 unchanged, and the per-element gate of launch_replay against the float64 reference with a bound counted from the
-formula's fp32 roundings.  One GateStats table per entry point records how much of each bound is used."""
+formula's fp32 roundings.  One GateStats table per entry point records how much of each bound is used.
+
+The fp32-only entry points of the family ("bg_X" next to "bg_X_t") forward to the "_t" ones: every fp32 / fp32 row without
+dx_add then also calls the fp32 entry on the same buffers, and its outputs must equal the gated ones bit for bit."""
 import ctypes
 import time
 
@@ -92,14 +95,20 @@ class Runner:
         g = b.get
         if op == "bn_stats":
             o = self.outb((2 * C,), torch.float64, y0=i["sums0"])
+            self.call32 = lambda: L.bg_bn_stats(P(b["x"]), o.ptr(), N * HW, C, st())
             return (lambda: L.bg_bn_stats_t(P(b["x"]), c["xdt"], o.ptr(), N * HW, C, st())), {"sums": o}
         if op == "bn_fwd":
             o = self.outb((N, HW, C), ydt, al)
+            self.call32 = lambda: L.bg_bn_apply_act_fwd(P(b["x"]), P(b["mean"]), P(b["rstd"]), P(b["gamma"]), P(b["beta"]),
+                                                        c["per_sample"], P(g("alpha")), o.ptr(), N, HW, C, st())
             return (lambda: L.bg_bn_apply_act_fwd_t(P(b["x"]), c["xdt"], P(b["mean"]), P(b["rstd"]), P(b["gamma"]),
                                                     P(b["beta"]), c["per_sample"], P(g("alpha")), o.ptr(), c["ydt"], N,
                                                     HW, C, st())), {"y": o}
         if op == "bn_bwd_reduce":
             o = self.outb((3, N, C), torch.float32)
+            self.call32 = lambda: L.bg_bn_apply_act_bwd_reduce(P(b["x"]), P(b["dy"]), P(b["mean"]), P(b["rstd"]),
+                                                               P(b["gamma"]), P(b["beta"]), c["per_sample"], P(g("alpha")),
+                                                               o.ptr(), N, HW, C, st())
             return (lambda: L.bg_bn_apply_act_bwd_reduce_t(P(b["x"]), c["xdt"], P(b["dy"]), c["ydt"], P(b["mean"]),
                                                            P(b["rstd"]), P(b["gamma"]), P(b["beta"]), c["per_sample"],
                                                            P(g("alpha")), o.ptr(), N, HW, C, st())), {"part": o}
@@ -112,33 +121,43 @@ class Runner:
                 o = self.outb((N, HW, C), xdt, al, y0=i["add"] if alias else None)
             addp = (lambda: o.ptr()) if alias else (lambda: P(g("add")))
             if op == "bn_bwd_dx":
+                self.call32 = lambda: L.bg_bn_apply_act_bwd_dx(P(b["x"]), P(b["dy"]), P(b["mean"]), P(b["rstd"]),
+                                                               P(b["gamma"]), P(b["beta"]), c["per_sample"], P(g("alpha")),
+                                                               P(b["cm"]), o.ptr(), N, HW, C, st())
                 return (lambda: L.bg_bn_apply_act_bwd_dx_t(P(b["x"]), c["xdt"], P(b["dy"]), c["ydt"], P(b["mean"]),
                                                            P(b["rstd"]), P(b["gamma"]), P(b["beta"]), c["per_sample"],
                                                            P(g("alpha")), P(b["cm"]), o.ptr(), addp(), N, HW, C,
                                                            st())), {"dx": o}
             da = self.outb((C,), torch.float32, y0=i["dalpha0"]) if c["dalpha"] else None
             outs = {k: v for k, v in (("dx", o), ("dalpha", da)) if v is not None}
+            self.call32 = lambda: L.bg_prelu_bwd(P(b["x"]), P(b["dy"]), P(b["alpha"]), P(o), P(da), N * HW, C, st())
             return (lambda: L.bg_prelu_bwd_t(P(b["x"]), c["xdt"], P(b["dy"]), c["ydt"], P(b["alpha"]), P(o), P(da),
                                              addp() if o is not None else None, N * HW, C, st())), outs
         if op == "prelu_fwd":
             o = self.outb((N, HW, C), ydt, al)
+            self.call32 = lambda: L.bg_prelu_fwd(P(b["x"]), P(b["alpha"]), o.ptr(), N * HW, C, st())
             return (lambda: L.bg_prelu_fwd_t(P(b["x"]), c["xdt"], P(b["alpha"]), o.ptr(), c["ydt"], N * HW, C,
                                              st())), {"y": o}
         if op == "bias_grad":
             o = self.outb((C,), torch.float32)
+            self.call32 = lambda: L.bg_bias_grad(P(b["x"]), o.ptr(), N * HW, C, st())
             return (lambda: L.bg_bias_grad_t(P(b["x"]), c["xdt"], o.ptr(), N * HW, C, st())), {"db": o}
         if op == "maxpool_fwd":
             o = self.outb((N, c["H"] // 2, c["W"] // 2, C), xdt, al)
+            self.call32 = lambda: L.bg_maxpool2_fwd(P(b["x"]), o.ptr(), N, c["H"], c["W"], C, st())
             return (lambda: L.bg_maxpool2_fwd_t(P(b["x"]), o.ptr(), c["xdt"], N, c["H"], c["W"], C, st())), {"y": o}
         if op == "maxpool_bwd":
             o = self.outb((N, c["H"], c["W"], C), xdt, al)
+            self.call32 = lambda: L.bg_maxpool2_bwd(P(b["x"]), P(b["dy"]), o.ptr(), N, c["H"], c["W"], C, st())
             return (lambda: L.bg_maxpool2_bwd_t(P(b["x"]), P(b["dy"]), o.ptr(), c["xdt"], N, c["H"], c["W"], C,
                                                 st())), {"dx": o}
         if op == "sum_pool_fwd":
             o = self.outb((N, C), torch.float32)
+            self.call32 = lambda: L.bg_sum_pool_fwd(P(b["x"]), o.ptr(), N, HW, C, st())
             return (lambda: L.bg_sum_pool_fwd_t(P(b["x"]), c["xdt"], o.ptr(), N, HW, C, st())), {"y": o}
         if op == "sum_pool_bwd":
             o = self.outb((N, HW, C), xdt, al)
+            self.call32 = lambda: L.bg_sum_pool_bwd(P(b["dy"]), o.ptr(), N, HW, C, st())
             return (lambda: L.bg_sum_pool_bwd_t(P(b["dy"]), o.ptr(), c["xdt"], N, HW, C, st())), {"dx": o}
         if op == "lincomb":
             o = self.outb((c["n"],), xdt, al)
@@ -150,6 +169,9 @@ class Runner:
                                            st())), {"y": o}
         if op == "dot":
             o = self.outb((1,), torch.float32, y0=i["out0"])
+            self.call32 = lambda: L.bg_dot(P(b["a"]), P(b["b"]), o.ptr(), c["n"], st())
+            if c["n"] % 4:                  # bg_dot_t refuses these (test_bad_arguments_are_rejected): bg_dot is gated
+                return self.call32, {"out": o}
             return (lambda: L.bg_dot_t(P(b["a"]), P(b["b"]), c["xdt"], o.ptr(), c["n"], st())), {"out": o}
         if op == "cast":
             o = self.outb((c["n"],), ydt)
@@ -163,7 +185,10 @@ class Runner:
         self.ins, self.outs = [], []
         gen = torch.Generator(device=self.dev).manual_seed(seed)
         i = E.make_inputs(c, self.dev, gen)
+        self.call32 = None
         call, out = self.launcher(c, i)
+        if not (c["op"] in E.FP32_ENTRY and c["xdt"] == c["ydt"] == E.F32 and c["add"] in ("none", "null-dx")):
+            self.call32 = None
         self.stats.launch(self.key)
         first = None
         for rep in range(2):
@@ -190,6 +215,21 @@ class Runner:
         if namb > E.AMBIGUITY_CAP * nout:
             self.failures.append("%s: %d of %d elements are sign-ambiguous (cap %g)" % (E.describe(c), namb, nout,
                                                                                         E.AMBIGUITY_CAP))
+        if self.call32 is not None and self.call32 is not call:
+            want = [o.view.clone() for o in out.values()]
+            for o in self.outs:
+                o.prefill()
+            torch.cuda.synchronize()
+            rc = self.call32()
+            torch.cuda.synchronize()
+            if rc != 0:
+                self.failures.append("%s: fp32 entry: return code %d (%s)" % (E.describe(c), rc,
+                                                                              self.L.bg_last_error().decode()))
+                return namb
+            for (k, o), w in zip(out.items(), want):
+                self.exact("fp32 entry " + k, o.view, w)
+            if not all(bf.guards_ok() for bf in self.ins + self.outs):
+                self.failures.append("%s: fp32 entry wrote outside a buffer (guard band)" % E.describe(c))
         return namb
 
 
