@@ -576,24 +576,39 @@ __global__ __launch_bounds__(256) void nn16_slab_reduce_kernel(const float* __re
 //   16 x 16 patch of output pixels of one image and a slice of BN output channels; per 64-channel chunk it loads the
 //   (16 + NT - 1)^2 source pixels ONCE into LDS (128-byte pixel rows, 16-byte chunks XOR-swizzled by (pixel & 6): found by
 //   brute force to be conflict-free for a 16-lane fragment starting at ANY pixel, i.e. for every tap shift), and the
-//   NT^2 taps read their operands from that tile at shifted pixel indices while only the weight tile of each
-//   (chunk, tap) streams in through a 3-stage ring.  L2 -> LDS bytes per MAC: 0.0098 against 0.031.
+//   NT^2 taps read their operands from that ONE halo buffer at shifted pixel indices while only the weight tile of each
+//   (chunk, tap) step streams in through a ring of two slots: the tile of step s + 1 is issued behind the barrier of
+//   step s, and every step opens with vmcnt(0) + barrier.  L2 -> LDS bytes per MAC: 0.0098 against 0.031.
 //   8 waves = 4 (pixel rows) x 2 (channels), wave tile 64 pixels x 16 NF channels, v_mfma_f32_16x16x32_bf16.
+//   LDS (halo | 2 weight slots) is sized in 1 KB wave-instructions, not in 8 KB rounds of the whole block: the waves whose
+//   index lies beyond a tile's last round skip that DMA instruction (wave-uniform branch) instead of fetching the zero
+//   page into padding - 41 instead of 48 instructions per halo tile at NT = 3 (37 / 40 at NT = 2), 4 NF instead of 8 or
+//   16 per weight tile (12 / 16 at NF = 3, 4 / 8 at NF = 1).  Every destination stays 1 KB aligned; 45 - 73 KB per block,
+//   two blocks per CU.
+//   Measured and rejected (profiles/halo_ring_ab.txt): a THREE-slot ring in this layout (41 + 3 x 12 = 77 KB at NF = 3:
+//   it fits beside a second block), weight tile s + 2 issued behind the barrier of step s, counted vmcnt per wave in
+//   front of each barrier so that the newest tile stays in flight across it and across the halo reload.  Bit-identical;
+//   per layer within +- 1 % of the two-slot instantiation of the same kernel on every halo shape of config 3 (2.5 %
+//   SLOWER on 96 -> 96 at 128^2 and 384 -> 192 at 32^2 k4s2): the second co-resident block already covers a block's weight
+//   latency, a deeper ring per block adds nothing.
 // ------------------------------------------------------------------------------------------
 constexpr int NH_T = 16;                                   // patch edge
+constexpr int NH_LDS_MAX = 81920;                          // two blocks per CU
 template <int NT> struct NHGeom {
     static constexpr int HW = NH_T + NT - 1;               // halo edge
     static constexpr int NPIX = HW * HW;
-    static constexpr int A_INSTR = (NPIX * 8 + 511) / 512; // LDS-DMA instructions per thread and chunk
-    static constexpr int A_BYTES = A_INSTR * 8192;
+    static constexpr int A_ROUNDS = (NPIX * 8 + 63) / 64;  // LDS-DMA wave-instructions (1 KB = 8 pixel rows) per chunk
+    static constexpr int A_INSTR = (A_ROUNDS + 7) / 8;     // ... per wave at most (wave w issues rounds w, w + 8, ...)
+    static constexpr int A_BYTES = A_ROUNDS * 1024;
 };
-constexpr int nh_w_instr(int NF) { return (32 * NF * 8 + 511) / 512; }
-// Two blocks per CU (80 KB of LDS each): ONE halo buffer and a 2-tile weight ring.  A block alone on its CU (two halo
+constexpr int nh_w_rounds(int NF) { return 32 * NF * 8 / 64; }          // wave-instructions per weight tile [32 NF][64]
+constexpr int nh_w_instr(int NF) { return (nh_w_rounds(NF) + 7) / 8; }
+// Two blocks per CU: ONE halo buffer and a 2-tile weight ring.  A block alone on its CU (two halo
 // buffers, 3- or 4-tile ring, 147 - 160 KB) was measured 10 - 20 % slower than nn16_kernel: nothing runs while it computes
 // its per-lane halo addresses, waits for its first 77 KB or stores its epilogue (~7 of 21 us per block at C = 96).
 constexpr int NH_WS = 2;
 template <int NT, int NF> constexpr int nn16h_lds_bytes() {
-    const int ring = NHGeom<NT>::A_BYTES + NH_WS * nh_w_instr(NF) * 8192;
+    const int ring = NHGeom<NT>::A_BYTES + NH_WS * nh_w_rounds(NF) * 1024;
     const int epi = 128 * (32 * NF + 4) * 4;               // the epilogue goes through LDS in two halves of 128 pixels
     return ring > epi ? ring : epi;
 }
@@ -732,11 +747,17 @@ __device__ __forceinline__ void nn16h_epilogue(const NN16Params& p, const NHTile
 template <int NT, int NF, int MODE, int THIN = 0>
 __global__ __launch_bounds__(512, 4) void nn16h_kernel(const NN16Params p) {       // 4 waves per SIMD: <= 128 VGPRs
     using G = NHGeom<NT>;
-    constexpr int WW = G::HW, NPIX = G::NPIX, A_INSTR = G::A_INSTR, A_BYTES = G::A_BYTES;
-    constexpr int BN = 32 * NF, W_INSTR = nh_w_instr(NF), W_BYTES = W_INSTR * 8192, NTAPS = NT * NT;
+    constexpr int WW = G::HW, NPIX = G::NPIX, A_ROUNDS = G::A_ROUNDS, A_INSTR = G::A_INSTR, A_BYTES = G::A_BYTES;
+    constexpr int BN = 32 * NF, W_ROUNDS = nh_w_rounds(NF), W_INSTR = nh_w_instr(NF), W_BYTES = W_ROUNDS * 1024;
+    constexpr int NTAPS = NT * NT;
+    static_assert(NH_WS == 2, "the step loop below alternates between two slots");
+    static_assert(nn16h_lds_bytes<NT, NF>() <= NH_LDS_MAX, "two blocks per CU");
+    static_assert(128 * (BN + 4) * 4 <= nn16h_lds_bytes<NT, NF>(), "the epilogue's staging tile overlays the ring");
+    static_assert(A_BYTES % 1024 == 0 && W_BYTES % 1024 == 0, "every LDS-DMA destination is 1 KB aligned");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // halo tile | W ring (NH_WS tiles)
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wu = __builtin_amdgcn_readfirstlane(w);   // (scalar: the branches on it below are wave-uniform by construction)
     const int wm = w >> 1, wn = w & 1;
     const Gather& g = p.g;
 
@@ -798,12 +819,14 @@ __global__ __launch_bounds__(512, 4) void nn16h_kernel(const NN16Params p) {    
     const uint32_t ldsw = lds0 + A_BYTES;
 
     // ---- per-lane sources of the halo tile (fixed for the whole block) ----
+    // byte offset of this lane's 8 channels inside a 64-channel chunk: pixel 8 (8 i + w) + (lane >> 3), chunk (lane & 7)
+    // swizzled by (pixel & 6) - the same for every instruction i (one register, not A_INSTR)
+    const int acb = 16 * ((lane & 7) ^ ((lane >> 3) & 6));
     const unsigned char* asrc[A_INSTR];
-    int acb[A_INSTR];                                   // byte offset of this lane's 8 channels inside a 64-channel chunk
 #pragma unroll
     for (int i = 0; i < A_INSTR; ++i) {
         const int pp = (i * 8 + w) * 64 + lane;
-        const int q = pp >> 3, c = (pp & 7) ^ (q & 6);
+        const int q = pp >> 3;
         const int hy = q / WW, hx = q - hy * WW;
         int sy = y0 + hy + base_h, sx = x0 + hx + base_w;
         bool ok = q < NPIX;
@@ -814,53 +837,56 @@ __global__ __launch_bounds__(512, 4) void nn16h_kernel(const NN16Params p) {    
             sx = sx >= g.Ws ? 2 * (g.Ws - 1) - sx : sx;
         }
         ok = ok && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
-        acb[i] = 16 * c;
         asrc[i] = ok ? abase + 2 * ((int64_t)((b * g.Hs + sy) * g.Ws + sx) * g.ld) : zero;
     }
+    // (weight row n = 8 (8 i + w) + (lane >> 3): its swizzle (n >> 1) & 7 = 4 (w & 1) + (lane >> 4) does not depend on i)
+    const int wcb = 16 * ((lane & 7) ^ (4 * (w & 1) + (lane >> 4)));
     const unsigned char* wsrc[W_INSTR];
-    int wcb[W_INSTR];
     bool wok[W_INSTR];
     int wrow[W_INSTR];
 #pragma unroll
     for (int i = 0; i < W_INSTR; ++i) {
         const int pp = (i * 8 + w) * 64 + lane;
-        const int n = pp >> 3, c = (pp & 7) ^ ((n >> 1) & 7);
+        const int n = pp >> 3;
         wok[i] = n < BN && n0 + n < p.N;
-        wcb[i] = 16 * c;
         wrow[i] = n;
         wsrc[i] = bbase + 2 * ((int64_t)(THIN == 1 ? (n & 7) : n0 + n) * p.C);      // THIN 1: column = (py, px, channel)
     }
     const uint32_t dma_a = __builtin_amdgcn_readfirstlane(lds0 + w * 1024);
     const uint32_t dma_w = __builtin_amdgcn_readfirstlane(ldsw + w * 1024);
 
+    // Round r = 8 i + (wave index) of a tile is one instruction of one wave (1 KB); the waves beyond the tile's last round
+    // skip instruction i as a whole (EXEC stays full in the issued ones: surplus lanes of the last halo round fetch the
+    // zero page into the padding behind pixel NPIX - 1).
     auto issue_a = [&](int chunk) {                     // the (NT + 15)^2 source pixels of 64 channels
         const uint32_t dst = dma_a;
         const int cb = chunk * 128;
+        const bool cv = (cb + acb) < 2 * p.C;
 #pragma unroll
         for (int i = 0; i < A_INSTR; ++i) {
-            const bool cv = (cb + acb[i]) < 2 * p.C;
-            glds16_asm(cv ? asrc[i] + (cb + acb[i]) : zero, dst + i * 8192);
+            if (8 * (i + 1) > A_ROUNDS && 8 * i + wu >= A_ROUNDS) continue;
+            glds16_asm(cv ? asrc[i] + (cb + acb) : zero, dst + i * 8192);
         }
     };
-    auto issue_w = [&](int step) {                      // weight tile [BN][64 channels] of (chunk, tap)
-        const int chunk = step / ntaps, tap = step - chunk * ntaps;
-        const int ty_ = tap / nkw;
-        const int hy = NT - nkh + ty_, hx = NT - nkw + (tap - ty_ * nkw);
+    // weight tile [BN][64 channels] of chunk `chunk` and tap (ty_, tx_) of the nkh x nkw taps this block walks
+    auto issue_w = [&](int chunk, int ty_, int tx_, int slot) {
+        const int hy = NT - nkh + ty_, hx = NT - nkw + tx_;
         const int kh = MODE == GATHER_CONV ? hy : kh0 + kstep * (NT - 1 - hy);
         const int kw = MODE == GATHER_CONV ? hx : kw0 + kstep * (NT - 1 - hx);
         const int64_t toff = 2 * ((int64_t)(kh * g.k + kw) * p.tap_stride);
-        const uint32_t dst = dma_w + (step % NH_WS) * W_BYTES;
+        const uint32_t dst = dma_w + slot * W_BYTES;
         const int cb = chunk * 128;
 #pragma unroll
         for (int i = 0; i < W_INSTR; ++i) {
-            bool cv = wok[i] && (cb + wcb[i]) < 2 * p.C;
+            if (8 * (i + 1) > W_ROUNDS && 8 * i + wu >= W_ROUNDS) continue;
+            bool cv = wok[i] && (cb + wcb) < 2 * p.C;
             int64_t to = toff;
             if (THIN == 1) {                            // window position (hy, hx), output parity (py, px) -> tap
                 const int kty = ((wrow[i] >> 4) & 1) + 1 - 2 * hy, ktx = ((wrow[i] >> 3) & 1) + 1 - 2 * hx;
                 cv = cv && kty >= 0 && ktx >= 0;
                 to = 2 * ((int64_t)(kty * 3 + ktx) * p.tap_stride);
             }
-            glds16_asm(cv ? wsrc[i] + to + (cb + wcb[i]) : zero, dst + i * 8192);
+            glds16_asm(cv ? wsrc[i] + to + (cb + wcb) : zero, dst + i * 8192);
         }
     };
 
@@ -886,34 +912,50 @@ __global__ __launch_bounds__(512, 4) void nn16h_kernel(const NN16Params p) {    
 
     const int nchunks = (p.C + 63) >> 6;
     const int T = nchunks * ntaps;
-    issue_a(0);
-    issue_w(0);
-
-    for (int step = 0; step < T; ++step) {
-        const int chunk = step / ntaps, tap = step - chunk * ntaps;
-        // W(step) (and at a chunk's first tap its halo tile, issued in front of it) has landed: nothing else is in flight
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (step + 1 < T) {
-            if (tap == ntaps - 1) {
-                // the next step starts a chunk: its halo tile goes into the ONE buffer this step still reads - so this
-                // step computes first (below) and issues after a barrier of its own
-            } else {
-                issue_w(step + 1);
+    // Cursors over the (chunk, tap) steps - the step that computes and the next weight tile to issue, one step in front -
+    // instead of a division by the (run-time) tap counts per step.
+    // DMA order per wave: W(0), halo(0) | W(s + 1) behind the barrier of step s | and at a chunk's last tap, whose
+    // successor needs the ONE halo buffer this step still reads: compute, barrier, halo(next chunk), W(s + 1).
+    int c_chunk = 0, c_ty = 0, c_tx = 0;
+    int w_chunk = 0, w_ty = 0, w_tx = 0, w_step = 0;
+    auto issue_next_w = [&](int slot) {
+        if (w_step < T) {
+            issue_w(w_chunk, w_ty, w_tx, slot);
+            ++w_step;
+            if (++w_tx == nkw) {
+                w_tx = 0;
+                if (++w_ty == nkh) {
+                    w_ty = 0;
+                    ++w_chunk;
+                }
             }
         }
+    };
+    issue_next_w(0);
+    issue_a(0);
 
-        const int ty_ = tap / nkw;
-        const int hy = NT - nkh + ty_, hx = NT - nkw + (tap - ty_ * nkw);
-        const uint32_t abuf = 0;
-        const uint32_t wslot = (uint32_t)(step % NH_WS) * W_BYTES;
+    // one (chunk, tap) step on ring slot SLOT (a compile-time constant: the operand addresses are base + immediate)
+    auto hstep = [&](int step, auto slot_c) {
+        constexpr int SLOT = decltype(slot_c)::value;
+        constexpr int NEXT = SLOT ^ 1;                  // the slot step - 1 read
+        // W(step) (and at a chunk's first tap its halo tile, issued in front of it) has landed - this wave's part; the
+        // barrier extends that to every wave: nothing else is in flight
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        // the next step starts a chunk: its halo tile goes into the ONE buffer this step still reads - so this step
+        // computes first and issues after a barrier of its own
+        const bool reload = c_ty == nkh - 1 && c_tx == nkw - 1 && step + 1 < T;
+        if (!reload) issue_next_w(NEXT);
+
+        const int hy = NT - nkh + c_ty, hx = NT - nkw + c_tx;
+        constexpr uint32_t wslot = (uint32_t)SLOT * W_BYTES;
         const int tq = hy * WW + hx;
-        const int ksteps = (p.C - chunk * 64) >= 64 ? 2 : 1;           // 32-channel MFMA steps in this chunk
+        const int ksteps = (p.C - c_chunk * 64) >= 64 ? 2 : 1;         // 32-channel MFMA steps in this chunk
         uint32_t aaddr[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int q = qb[i] + tq;
-            aaddr[i] = abuf + q * 128 + 16 * (kb ^ (q & 6));
+            aaddr[i] = q * 128 + 16 * (kb ^ (q & 6));
         }
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
@@ -924,7 +966,7 @@ __global__ __launch_bounds__(512, 4) void nn16h_kernel(const NN16Params p) {    
                     a[i] = *reinterpret_cast<const bf16x8_t*>(smem + (aaddr[i] ^ (s2 ? 64u : 0u)));
 #pragma unroll
                 for (int j = 0; j < NF; ++j)
-                    bw[j] = *reinterpret_cast<const bf16x8_t*>(smem + ((boff[j] + wslot) ^ (s2 ? 64u : 0u)));
+                    bw[j] = *reinterpret_cast<const bf16x8_t*>(smem + ((boff[j] ^ (s2 ? 64u : 0u)) + wslot));
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -932,12 +974,23 @@ __global__ __launch_bounds__(512, 4) void nn16h_kernel(const NN16Params p) {    
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[j], a[i], acc[i][j], 0, 0, 0);
             }
         }
-        if (tap == ntaps - 1 && step + 1 < T) {
+        if (reload) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // every wave has read the halo tile of this chunk
             __builtin_amdgcn_s_barrier();
-            issue_a(chunk + 1);
-            issue_w(step + 1);
+            issue_a(c_chunk + 1);
+            issue_next_w(NEXT);
         }
+        if (++c_tx == nkw) {
+            c_tx = 0;
+            if (++c_ty == nkh) {
+                c_ty = 0;
+                ++c_chunk;
+            }
+        }
+    };
+    for (int step = 0; step < T; step += NH_WS) {
+        hstep(step, std::integral_constant<int, 0>());
+        if (step + 1 < T) hstep(step + 1, std::integral_constant<int, 1>());
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -955,9 +1008,9 @@ __global__ __launch_bounds__(512, 4) void nn16h_kernel(const NN16Params p) {    
 // Bit-identical results, config 3 at batch 256: 101.6 -> 106.9 ms per iteration; transposed conv 192 -> 96 at 128^2:
 // 3.1 -> 4.4 ms.  A block computes a 32-channel chunk of a 2 x 2 window in ~0.6 us and a halo tile takes ~2 us to arrive: one
 // chunk of look-ahead hides less than the single 64-channel buffer of the first form loses, and the 64-byte rows halve the
-// coalescing of the DMA's global reads.  Hiding the latency needs ~3 tiles in flight per block, which two blocks per CU
-// cannot hold in 160 KB.  (The 64-byte-row swizzle that is conflict-free for ds_read_b128's lane groups, should it be
-// needed again: chunk c of row r at c ^ ((r >> 1) & 2).)
+// coalescing of the DMA's global reads.  (Three WEIGHT tiles in flight per block beside the one 64-channel halo buffer do
+// fit two blocks per CU and were measured as well - no gain, see the kernel's header.)  (The 64-byte-row swizzle that is
+// conflict-free for ds_read_b128's lane groups, should it be needed again: chunk c of row r at c ^ ((r >> 1) & 2).)
 // ------------------------------------------------------------------------------------------
 // TN kernel (weight gradients): K = pixels, both operands pixel-major in LDS, transposed operand reads
 // ------------------------------------------------------------------------------------------
@@ -1577,12 +1630,13 @@ static int nn16h_taps(const NN16Params& p, int mode, int zdim) {
     return 0;
 }
 
-template <int NT, int NF, int MODE>
+template <int NT, int NF, int MODE, int THIN = 0>
 static int launch_nn16h_inst(const NN16Params& p, int blocks, hipStream_t s) {
     constexpr int lds = nn16h_lds_bytes<NT, NF>();
-    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16h_kernel<NT, NF, MODE>), lds)) return BG_ERR_LAUNCH;
-    prof_kernel("nn16h_kernel<%d, %d, %d>", NT, NF, MODE);
-    hipLaunchKernelGGL((nn16h_kernel<NT, NF, MODE>), dim3(blocks), dim3(512), lds, s, p);
+    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16h_kernel<NT, NF, MODE, THIN>), lds)) return BG_ERR_LAUNCH;
+    if (THIN) prof_kernel("nn16h_kernel<%d, %d, %d, d2s>", NT, NF, MODE);
+    else prof_kernel("nn16h_kernel<%d, %d, %d>", NT, NF, MODE);
+    hipLaunchKernelGGL((nn16h_kernel<NT, NF, MODE, THIN>), dim3(blocks), dim3(512), lds, s, p);
     return BG_OK;
 }
 
@@ -1614,10 +1668,7 @@ int launch_nn16h_d2s(const NN16Params& plain, hipStream_t s) {
     p.splitk = 1; p.mfast = 0; p.ring = 0;
     const int64_t blocks = (int64_t)g.Nb * (g.Hq / NH_T) * (g.Wq / NH_T);
     BG_REQUIRE(blocks > 0 && blocks < (int64_t(1) << 31), "nn16h: grid out of range");
-    constexpr int lds = nn16h_lds_bytes<2, 1>();
-    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16h_kernel<2, 1, GATHER_CONV, 1>), lds)) return BG_ERR_LAUNCH;
-    prof_kernel("nn16h_kernel<2, 1, 0, d2s>");
-    hipLaunchKernelGGL((nn16h_kernel<2, 1, GATHER_CONV, 1>), dim3((int)blocks), dim3(512), lds, s, p);
+    if (const int rc = launch_nn16h_inst<2, 1, GATHER_CONV, 1>(p, (int)blocks, s)) return rc;
     BG_LAUNCH_CHECK();
     return BG_OK;
 }
@@ -1644,7 +1695,11 @@ static int launch_nn16h(NN16Params& p, int mode, int ntaps, hipStream_t s) {
     int nf = 4, best = 1 << 30;
     // (c = 1, a 32-column tile, r03: the generator's 96 -> 3 (8) image layer - a quarter of the padded MFMA work of the
     //  64-column tile and the input read once instead of once per tap by the tap kernel)
-    for (int c = 4; c >= 1; --c) {                      // least padded output channels; ties: the wider tile
+    // Least padded output channels; ties: the wider tile.  N = 384 / 768 pad alike at 128 and 96 columns; measured on
+    // config 3 at batch 256 (profiles/halo_ring_ab.txt; NF = 4 against NF = 3, forward / input gradient, ms):
+    // 16^2 768 -> 384 k4s2 0.53 against 0.59, 32^2 384 -> 384 k3 0.55 / 0.55 against 0.61 / 0.60, 16^2 768 -> 768 k3 0.53 / 0.53
+    // against 0.58 / 0.56 - the narrower tile loads the halo 4/3 times as often.
+    for (int c = 4; c >= 1; --c) {
         const int padded = (p.N + 32 * c - 1) / (32 * c) * (32 * c);
         if (padded < best) { best = padded; nf = c; }
     }
