@@ -71,8 +71,11 @@ __device__ __forceinline__ void lds_zero(float* p, int n) {
 // ------------------------------------------------------------------------------------------
 // forward: grid (N/128, B), 4 waves x 32 queries, key tiles of 32
 // ------------------------------------------------------------------------------------------
+// __launch_bounds__(256, 2) on the three tile kernels: a 256-register budget, so that the MFMA accumulators, which the
+// softmax / dS arithmetic reads and rewrites every key tile, live in VGPRs and not in AGPRs behind v_accvgpr copies
+// (attention16.hip has the story); no instantiation spills (tools/attn_regs.py).
 template <int DQ, int DVT>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                        const float* __restrict__ v, float* __restrict__ o,
                                                        float* __restrict__ lse, int N, int Nk, int d, int dv) {
     constexpr int DV = DVT * 32;
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
 //   S^T = K Q^T ; P^T = exp(S^T - lse) ; dP^T = V dO^T ; dS^T = P^T (dP^T - delta) ; dQ^T += K^T dS^T
 // ------------------------------------------------------------------------------------------
 template <int DQ, int DVT>
-__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float* __restrict__ q, const float* __restrict__ k,
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                           const float* __restrict__ v,
                                                           const float* __restrict__ dout,
                                                           const float* __restrict__ lse,
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float* __restric
 //   S = Q K^T ; P = exp(S - lse_row) ; dV^T += dO^T P ; dP = dO V^T ; dS = P (dP - delta_row) ; dK^T += Q^T dS
 // ------------------------------------------------------------------------------------------
 template <int DQ, int DVT>
-__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ v,
                                                            const float* __restrict__ dout,
                                                            const float* __restrict__ lse,

@@ -146,13 +146,24 @@ struct A16Geom {
     int64_t sq, sk, sv, so;              // batch strides (elements)
 };
 
+// Second argument of __launch_bounds__ (blocks of 256 threads per CU = waves per SIMD) per instantiation.  With no
+// bound the compiler budgets 512 registers per lane and picks the AGPR form of every MFMA; the softmax / dS arithmetic
+// needs the accumulators in VGPRs, so each key tile then copies the score tile out (v_accvgpr_read) and the converted
+// operands back (v_accvgpr_write): 40 % of the loop's VALU instructions.  Bound 2 = a 256-register budget = the VGPR form
+// and no copies.  The instantiations with dv > 128 (32 DVT accumulator registers and two prefetched tiles) do not fit 256
+// registers: they would spill, and keep the 512-register budget.  tools/attn_regs.py prints the table this is read from
+// (profiles/attn_vgpr_ab.txt): no instantiation has scratch.
+constexpr int a16_fwd_blocks(int dqt, int dvt) { return dvt <= 4 ? 2 : 1; }
+constexpr int a16_dq_blocks(int dqt, int dvt) { return 2; }
+constexpr int a16_dkv_blocks(int dqt, int dvt) { return dvt <= 4 ? 2 : 1; }
+
 // ------------------------------------------------------------------------------------------
 // forward: grid (N / 128, B); a wave owns 32 queries, key tiles of 32
 // ------------------------------------------------------------------------------------------
 template <int DQT, int DVT>          // d <= 16 DQT, dv <= 32 DVT
-__global__ __launch_bounds__(256) void attn16_fwd_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
-                                                         const __bf16* __restrict__ v, __bf16* __restrict__ o,
-                                                         float* __restrict__ lse, const A16Geom gm) {
+__global__ __launch_bounds__(256, a16_fwd_blocks(DQT, DVT))
+void attn16_fwd_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
+                       __bf16* __restrict__ o, float* __restrict__ lse, const A16Geom gm) {
     constexpr int VIMG = (DVT + 3) / 4;
     __shared__ __attribute__((aligned(16))) unsigned char Ks[2][A16_IMG];
     __shared__ __attribute__((aligned(16))) unsigned char Vs[2][VIMG * A16_IMG];
@@ -269,34 +280,51 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(const __bf16* __restric
     if (half == 0) lse[(int64_t)b * gm.N + q0 + col] = m_run + __logf(l_run);
 }
 
-// delta[row] = sum_c dO[row,c] * O[row,c]   (one wave per row)
+// delta[b, n] = sum_c dO[b,n,c] * O[b,n,c]: grid (N / (256 >> LG), B).  A group of 2^LG lanes owns a row, a lane 4
+// consecutive channels of it (one 8-byte load per tensor: row strides are only multiples of 4 elements); the host picks
+// the smallest group that covers dv.  The sum keeps the order of the kernel this one replaced (one wave per row, channel
+// c on lane c & 63, wave_sum), so delta - and every gradient behind it - has the same bits: channels 64 apart are added
+// in ascending order, then the channels c and c ^ 32, ^ 16, ^ 8, ^ 4 (lanes 8, 4, 2, 1 apart here, per channel of the
+// lane), then c ^ 2 and c ^ 1 inside the lane.  The products of two bf16 are exact in fp32, so only that order matters.
 __global__ __launch_bounds__(256) void attn16_delta_kernel(const __bf16* __restrict__ o, const __bf16* __restrict__ dout,
-                                                           float* __restrict__ delta, int B, int N, int dv, int64_t ldo,
+                                                           float* __restrict__ delta, int N, int dv, int lg, int64_t ldo,
                                                            int64_t so, int64_t ldg, int64_t sg) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (int64_t)B * N) return;
-    const int b = (int)(row / N), n = (int)(row - (int64_t)b * N);
-    const __bf16* op = o + b * so + n * ldo;
-    const __bf16* gp = dout + b * sg + n * ldg;
-    float s = 0.f;
-    for (int c = lane; c < dv; c += 64) s += (float)op[c] * (float)gp[c];
-    s = wave_sum(s);
-    if (lane == 0) delta[row] = s;
+    const int b = blockIdx.y;
+    const int n = (int)((blockIdx.x * 256u + threadIdx.x) >> lg);
+    const int G = 1 << lg;
+    const int j = threadIdx.x & (G - 1);
+    float p[4] = {0.f, 0.f, 0.f, 0.f};
+    if (n < N && 4 * j < dv) {
+        const uint2 x = *reinterpret_cast<const uint2*>(o + b * so + n * ldo + 4 * j);
+        const uint2 y = *reinterpret_cast<const uint2*>(dout + b * sg + n * ldg + 4 * j);
+        // (+ 0: a product of -0 becomes +0, as in a sum that starts from 0)
+        p[0] = fmaf(__uint_as_float(x.x << 16), __uint_as_float(y.x << 16), 0.f);
+        p[1] = fmaf(__uint_as_float(x.x & 0xffff0000u), __uint_as_float(y.x & 0xffff0000u), 0.f);
+        p[2] = fmaf(__uint_as_float(x.y << 16), __uint_as_float(y.y << 16), 0.f);
+        p[3] = fmaf(__uint_as_float(x.y & 0xffff0000u), __uint_as_float(y.y & 0xffff0000u), 0.f);
+    }
+    float v[4] = {p[0], p[1], p[2], p[3]};
+    for (int up = 16; up < G; up += 16)          // channels c + 64, c + 128, c + 192 (lanes 16, 32, 48 up), in that order
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] += __shfl_down(p[i], up, 64);
+    for (int off = G < 16 ? G >> 1 : 8; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] += __shfl_xor(v[i], off, 64);
+    if (n < N && j == 0) delta[(int64_t)b * N + n] = (v[0] + v[2]) + (v[1] + v[3]);
 }
 
 // ------------------------------------------------------------------------------------------
 // backward, dQ: grid (N / 128, B); a wave owns 32 queries and walks the keys
 //   S^T = K Q^T ; P^T = exp(S^T - lse) ; dP^T = V dO^T ; dS^T = P^T (dP^T - delta) ; dQ^T += K^T dS^T
+// (lse and delta are subtracted per score, here and in the dk / dv kernel.  As initial accumulators of the two chains
+// they save VALU work but sum in another fp32 order, and here cost 32 registers and a wave per SIMD - DESIGN 5.1.)
 // ------------------------------------------------------------------------------------------
 template <int DQT, int DVT>
-__global__ __launch_bounds__(256) void attn16_bwd_dq_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
-                                                            const __bf16* __restrict__ v,
-                                                            const __bf16* __restrict__ dout,
-                                                            const float* __restrict__ lse,
-                                                            const float* __restrict__ delta, __bf16* __restrict__ dq,
-                                                            const A16Geom gm, int64_t ldg, int64_t sg, int64_t lddq,
-                                                            int64_t sdq) {
+__global__ __launch_bounds__(256, a16_dq_blocks(DQT, DVT))
+void attn16_bwd_dq_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
+                          const __bf16* __restrict__ dout, const float* __restrict__ lse,
+                          const float* __restrict__ delta, __bf16* __restrict__ dq, const A16Geom gm, int64_t ldg,
+                          int64_t sg, int64_t lddq, int64_t sdq) {
     constexpr int VIMG = (DVT + 3) / 4;
     constexpr int MT = (DQT + 1) / 2;           // 32-row tiles of dQ^T
     __shared__ __attribute__((aligned(16))) unsigned char Ks[2][A16_IMG];
@@ -379,14 +407,12 @@ __global__ __launch_bounds__(256) void attn16_bwd_dq_kernel(const __bf16* __rest
 //   S = Q K^T ; P = exp(S - lse_row) ; dV^T += dO^T P ; dP = dO V^T ; dS = P (dP - delta_row) ; dK^T += Q^T dS
 // ------------------------------------------------------------------------------------------
 template <int DQT, int DVT>
-__global__ __launch_bounds__(256) void attn16_bwd_dkv_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
-                                                             const __bf16* __restrict__ v,
-                                                             const __bf16* __restrict__ dout,
-                                                             const float* __restrict__ lse,
-                                                             const float* __restrict__ delta, __bf16* __restrict__ dk,
-                                                             __bf16* __restrict__ dvo, const A16Geom gm, int64_t ldg,
-                                                             int64_t sg, int64_t lddk, int64_t sdk, int64_t lddv,
-                                                             int64_t sdv) {
+__global__ __launch_bounds__(256, a16_dkv_blocks(DQT, DVT))
+void attn16_bwd_dkv_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
+                           const __bf16* __restrict__ dout, const float* __restrict__ lse,
+                           const float* __restrict__ delta, __bf16* __restrict__ dk, __bf16* __restrict__ dvo,
+                           const A16Geom gm, int64_t ldg, int64_t sg, int64_t lddk, int64_t sdk, int64_t lddv,
+                           int64_t sdv) {
     constexpr int GIMG = (DVT + 3) / 4;
     constexpr int MT = (DQT + 1) / 2;
     __shared__ __attribute__((aligned(16))) unsigned char Qs[2][A16_IMG];
@@ -614,10 +640,12 @@ int bg_attention16_bwd(const BgAttn16Desc* g, const void* q, const void* k, cons
     hipStream_t s = as_stream(stream);
     const A16Geom gm = a16_geom(g);
     const int B = g->B;
-    const int64_t rows = (int64_t)B * gm.N;
     if (dk) {       // delta_ws is (re)computed by the call that produces dk / dv and reused by a later dq-only call
-        hipLaunchKernelGGL(attn16_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const __bf16*)o,
-                           (const __bf16*)dout, delta_ws, B, gm.N, gm.dv, gm.ldo, gm.so, g->ldg, g->sg);
+        int lg = 0;                 // lanes per row: the smallest power of two with 4 * 2^lg >= dv (dv <= 256: at most 64)
+        while ((4 << lg) < gm.dv) ++lg;
+        const int rpb = 256 >> lg;  // rows per block
+        hipLaunchKernelGGL(attn16_delta_kernel, dim3((unsigned)((gm.N + rpb - 1) / rpb), B), dim3(256), 0, s,
+                           (const __bf16*)o, (const __bf16*)dout, delta_ws, gm.N, gm.dv, lg, gm.ldo, gm.so, g->ldg, g->sg);
         BG_LAUNCH_CHECK();
     }
     // algorithmic backward work = dV, dP, dQ, dK = 2 x forward over BOTH calls of one backward (the dk / dv call and the
