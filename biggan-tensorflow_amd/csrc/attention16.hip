@@ -562,11 +562,13 @@ static void a16_launch_bwd(hipStream_t s, const __bf16* q, const __bf16* k, cons
                            delta, dk, dvo, gm, ldg, sg, lddk, sdk, lddv, sdv);
 }
 
-// (d, dv) -> (DQT, DVT) instances: every BASELINE topology's pair plus a generic ladder
+// (d, dv) -> (DQT, DVT) instances: every BASELINE topology's pair plus a generic ladder.  Every rung covers the whole
+// dv range a16_shape_ok accepts: d <= 16 with dv > 128 runs on the <2, 8> instance (its unused second 16-column group of
+// q / k is read as zeros).
 #define A16_DISPATCH(FN, ...)                                                       \
     do {                                                                            \
         const int dqt = (gm.d + 15) / 16, dvt = (gm.dv + 31) / 32;                  \
-        if (dqt <= 1) {                                                             \
+        if (dqt <= 1 && dvt <= 4) {                                                 \
             if (dvt <= 1) FN<1, 1>(__VA_ARGS__);                                    \
             else if (dvt <= 2) FN<1, 2>(__VA_ARGS__);                               \
             else FN<1, 4>(__VA_ARGS__);                                             \

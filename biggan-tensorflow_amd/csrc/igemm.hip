@@ -1048,13 +1048,29 @@ static bool reflect_hi_only(const BgConvDesc* d) {
     return d->pad_mode == BG_PAD_REFLECT && d->pad_lo == 0 && conv_pad_hi(d) > 0;
 }
 
-// fp32-tensor launch of the input gradient on the padded grid of a reflect_hi_only geometry (stride 1)
+// A row / column of a small reflect-padded map can mirror padded positions on BOTH sides (row o with 1 <= o <= pad_lo and
+// H - 1 - pad_hi <= o <= H - 2, i.e. H <= pad_lo + pad_hi + 1: a 3 x 3 window on a 3 x 3 map, a 5 x 5 one on maps up to
+// 5 x 5).  The fp32 MIRROR kernels gather one mirrored source per axis, so these geometries take the padded grid too.
+static bool conv_dgrad_double_mirror(const BgConvDesc* d) {
+    if (d->pad_mode != BG_PAD_REFLECT || d->pad_lo == 0) return false;
+    auto axis = [&](int n, int no) {
+        const int hi = (no - 1) * d->stride + d->k - 1 - d->pad_lo - (n - 1);       // high padding the windows read
+        if (hi <= 0) return false;
+        const int first_hi = n - 1 - hi > 1 ? n - 1 - hi : 1, last_lo = d->pad_lo < n - 2 ? d->pad_lo : n - 2;
+        return first_hi <= last_lo;
+    };
+    return axis(d->H, d->Ho) || axis(d->W, d->Wo);
+}
+static bool conv_dgrad_fold32(const BgConvDesc* d) { return reflect_hi_only(d) || conv_dgrad_double_mirror(d); }
+
+// fp32-tensor launch of the input gradient on the padded grid of a conv_dgrad_fold32 geometry (stride phases as on the
+// map: the extent is a multiple of the stride)
 static void conv_dgrad_padded_params(const BgConvDesc* d, NNParams& p) {
     conv_dgrad_params(d, p);
     Gather& g = p.g;
     g.Ho = padded_extent(d->Ho, d->k, d->stride);
     g.Wo = padded_extent(d->Wo, d->k, d->stride);
-    g.Hq = g.Ho; g.Wq = g.Wo; g.pad = 0; g.reflect = 0;
+    g.Hq = g.Ho / d->stride; g.Wq = g.Wo / d->stride; g.pad = 0; g.reflect = 0;
     p.M = d->N * g.Hq * g.Wq;
 }
 
@@ -1169,14 +1185,14 @@ size_t bg_conv2d_dgrad_workspace_bytes(const BgConvDesc* d) {
         if (padded) b = align256(b) + align256((size_t)out_elems * (d->x_dtype == BG_F32 ? 4 : 2));
         return b;
     }
-    if (reflect_hi_only(d) && d->stride == 1) {
+    UnevenPhases uneven(d);
+    if (conv_dgrad_fold32(d)) {
         NNParams p;
         conv_dgrad_padded_params(d, p);
-        const int64_t out_elems = (int64_t)p.M * d->Cin;
-        return align256(nn_workspace_bytes(p.M, d->Cin, 1, tconv_min_iters(d, d->Cout), out_elems)) +
+        const int64_t out_elems = (int64_t)d->N * p.g.Ho * p.g.Wo * d->Cin;
+        return align256(nn_workspace_bytes(p.M, d->Cin, z, tconv_min_iters(d, d->Cout), out_elems)) +
                align256((size_t)out_elems * sizeof(float));
     }
-    UnevenPhases uneven(d);
     return nn_workspace_bytes((int64_t)d->N * (d->H / d->stride) * (d->W / d->stride), d->Cin, z,
                               tconv_min_iters(d, d->Cout), (int64_t)d->N * d->H * d->W * d->Cin);
 }
@@ -1224,25 +1240,25 @@ int bg_conv2d_dgrad(const BgConvDesc* d, const void* dy, const void* w, const fl
                                    as_stream(stream));
     }
     BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32 && !d->w_packed, "bg_conv2d_dgrad: unsupported dtype mix");
-    if (reflect_hi_only(d)) {
-        BG_REQUIRE(d->stride == 1 && d->Cin % 8 == 0,
-                   "bg_conv2d_dgrad: reflect padding on the high side only needs stride 1 and Cin %% 8 == 0 (Cin=%d)", d->Cin);
+    UnevenPhases uneven(d);
+    if (conv_dgrad_fold32(d)) {
+        // gradient on the reflect-padded grid (plain transposed gather, stride phases), then the fold
         NNParams p;
         conv_dgrad_padded_params(d, p);
-        const int64_t out_elems = (int64_t)p.M * d->Cin;
+        const int64_t out_elems = (int64_t)d->N * p.g.Ho * p.g.Wo * d->Cin;
         const size_t pbytes = align256((size_t)out_elems * sizeof(float));
         BG_REQUIRE(ws && ws_bytes >= pbytes, "bg_conv2d_dgrad: workspace too small for the padded gradient");
         p.A = (const float*)dy; p.B = (const float*)w; p.alpha = alpha_dev; p.out = (float*)ws; p.accumulate = 0;
         const bool vec = (d->Cout % 4 == 0) && aligned16(dy) && aligned16(w);
         char* slabs = reinterpret_cast<char*>(ws) + pbytes;
         ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-        rc = launch_nn(p, GATHER_TCONV, true, false, vec, 1, tconv_min_iters(d, d->Cout), out_elems, true,
-                       ws_bytes > pbytes ? slabs : nullptr, ws_bytes - pbytes, as_stream(stream),
+        rc = launch_nn(p, GATHER_TCONV, true, false, vec, d->stride * d->stride, tconv_min_iters(d, d->Cout), out_elems,
+                       true, ws_bytes > pbytes ? slabs : nullptr, ws_bytes - pbytes, as_stream(stream),
                        d->compute == BG_COMPUTE_BF16);
         if (rc) return rc;
-        return launch_reflect_fold(ws, dx, 1, d->N, d->H, d->W, d->Cin, p.g.Ho, p.g.Wo, 0, accumulate, as_stream(stream));
+        return launch_reflect_fold(ws, dx, 1, d->N, d->H, d->W, d->Cin, p.g.Ho, p.g.Wo, d->pad_lo, accumulate,
+                                   as_stream(stream));
     }
-    UnevenPhases uneven(d);
     NNParams p;
     conv_dgrad_params(d, p);
     p.A = (const float*)dy; p.B = (const float*)w; p.alpha = alpha_dev; p.out = (float*)dx; p.accumulate = accumulate;

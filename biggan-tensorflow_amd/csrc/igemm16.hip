@@ -1427,9 +1427,47 @@ __global__ __launch_bounds__(256) void reflect_fold_kernel(const void* __restric
     }
 }
 
+// the same fold, one fp32 element per thread: channel counts that are no multiple of 8 (fp32 tensors only)
+__global__ __launch_bounds__(256) void reflect_fold_scalar_kernel(const float* __restrict__ dxp, float* __restrict__ dx,
+                                                                  int N, int H, int W, int C, int Hp, int Wp, int pad,
+                                                                  int accumulate) {
+    const int64_t total = (int64_t)N * H * W * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        int64_t t = i / C;
+        const int w = (int)(t % W);
+        t /= W;
+        const int h = (int)(t % H);
+        const int n = (int)(t / H);
+        int hs[3], ws[3], nh = 0, nw = 0;
+        hs[nh++] = h + pad;
+        if (h >= 1 && pad - h >= 0) hs[nh++] = pad - h;
+        if (h <= H - 2 && 2 * (H - 1) - h + pad < Hp) hs[nh++] = 2 * (H - 1) - h + pad;
+        ws[nw++] = w + pad;
+        if (w >= 1 && pad - w >= 0) ws[nw++] = pad - w;
+        if (w <= W - 2 && 2 * (W - 1) - w + pad < Wp) ws[nw++] = 2 * (W - 1) - w + pad;
+        float acc = 0.f;
+        for (int a = 0; a < nh; ++a)
+            for (int b = 0; b < nw; ++b) {
+                if (hs[a] >= Hp || ws[b] >= Wp) continue;
+                acc += dxp[(((int64_t)n * Hp + hs[a]) * Wp + ws[b]) * C + c];
+            }
+        dx[i] = accumulate ? dx[i] + acc : acc;
+    }
+}
+
 int launch_reflect_fold(const void* dxp, void* dx, int f32, int N, int H, int W, int C, int Hp, int Wp, int pad_lo,
                         int accumulate, hipStream_t s) {
-    BG_REQUIRE(C % 8 == 0, "reflect fold: C %% 8 != 0");
+    if (C % 8 != 0) {
+        BG_REQUIRE(f32, "reflect fold: bf16 tensors need C %% 8 == 0");
+        const int64_t n = (int64_t)N * H * W * C;
+        int64_t nb = (n + 255) / 256;
+        if (nb > 4096) nb = 4096;
+        hipLaunchKernelGGL(reflect_fold_scalar_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const float*)dxp, (float*)dx, N,
+                           H, W, C, Hp, Wp, pad_lo, accumulate);
+        BG_LAUNCH_CHECK();
+        return BG_OK;
+    }
     const int64_t total = (int64_t)N * H * W * (C / 8);
     int64_t blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;

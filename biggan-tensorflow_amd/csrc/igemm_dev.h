@@ -55,12 +55,15 @@ __device__ __forceinline__ int tconv_src_from_num(int hn, int stride, int n) {
 
 // mirrored source of a TCONV gather with reflect padding (gradient of tf.pad(REFLECT) folded in):
 // the padded positions that alias output pixel o are  pad - o  (1 <= o <= pad)  and
-// 2*(n_out-1) + pad - o  (n_out-1-pad <= o <= n_out-2).
-__device__ __forceinline__ int tconv_mirror_src(int o, int kk, int stride, int pad, int n_out, int n_src) {
+// 2*(n_out-1) + pad - o  (n_out-1-pad_hi <= o <= n_out-2), pad = the low padding.  The high range is taken with the
+// widest high padding a k-tap window can have, k - 1 - pad: a position beyond the actual padded extent has no source
+// (tconv_src_from_num rejects it).  ONE mirror per pixel: the host sends a geometry in which a pixel lies in both ranges
+// (n_out <= pad + pad_hi + 1, conv_dgrad_double_mirror) to the padded-grid form instead.
+__device__ __forceinline__ int tconv_mirror_src(int o, int kk, int k, int stride, int pad, int n_out, int n_src) {
     int hn;
     if (o >= 1 && o <= pad)
         hn = pad - o - kk;
-    else if (o >= n_out - 1 - pad && o <= n_out - 2)
+    else if (o >= n_out - k + pad && o <= n_out - 2)
         hn = 2 * (n_out - 1) + pad - o - kk;
     else
         return -1;
@@ -86,8 +89,8 @@ __device__ __forceinline__ void tap_sources(const Gather& g, const RowPos& r, in
         h0 = tconv_src_from_num(r.ho + g.pad - kh, g.stride, g.Hs);
         w0 = tconv_src_from_num(r.wo + g.pad - kw, g.stride, g.Ws);
         if (MIRROR) {
-            h1 = tconv_mirror_src(r.ho, kh, g.stride, g.pad, g.Ho, g.Hs);
-            w1 = tconv_mirror_src(r.wo, kw, g.stride, g.pad, g.Wo, g.Ws);
+            h1 = tconv_mirror_src(r.ho, kh, g.k, g.stride, g.pad, g.Ho, g.Hs);
+            w1 = tconv_mirror_src(r.wo, kw, g.k, g.stride, g.pad, g.Wo, g.Ws);
         }
     }
     const int64_t base = (int64_t)r.b * g.Hs;

@@ -118,30 +118,32 @@ __global__ __launch_bounds__(256) void rgb_conv_dgrad_kernel(const float* __rest
         const int64_t b = t / g.H;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int kh = 0; kh < g.k; ++kh) {
-            // output rows ho whose tap kh reads input row hi: direct and (reflect) mirrored
-            int hos[2];
+            // output rows ho whose tap kh reads input row hi: direct and (reflect) through the padded rows that mirror
+            // hi, -hi below the map (hi >= 1) and 2 (H - 1) - hi above it (hi <= H - 2).  A row of a small map can have
+            // both; a mirror that lies outside the padding gives an ho outside [0, H) and is skipped below
+            int hos[3];
             hos[0] = hi + g.pad - kh;
-            hos[1] = -1;
+            hos[1] = hos[2] = -1;
             if (g.reflect) {
-                if (hi >= 1 && hi <= g.pad) hos[1] = g.pad - hi - kh;
-                else if (hi >= g.H - 1 - g.pad && hi <= g.H - 2) hos[1] = 2 * (g.H - 1) + g.pad - hi - kh;
+                if (hi >= 1) hos[1] = g.pad - hi - kh;
+                if (hi <= g.H - 2) hos[2] = 2 * (g.H - 1) + g.pad - hi - kh;
             }
-            for (int a = 0; a < 2; ++a) {
+            for (int a = 0; a < 3; ++a) {
                 const int ho = hos[a];
                 if (ho < 0 || ho >= g.H) continue;
                 for (int kw = 0; kw < g.k; ++kw) {
-                    int wos[2];
+                    int wos[3];
                     wos[0] = wi + g.pad - kw;
-                    wos[1] = -1;
+                    wos[1] = wos[2] = -1;
                     if (g.reflect) {
-                        if (wi >= 1 && wi <= g.pad) wos[1] = g.pad - wi - kw;
-                        else if (wi >= g.W - 1 - g.pad && wi <= g.W - 2) wos[1] = 2 * (g.W - 1) + g.pad - wi - kw;
+                        if (wi >= 1) wos[1] = g.pad - wi - kw;
+                        if (wi <= g.W - 2) wos[2] = 2 * (g.W - 1) + g.pad - wi - kw;
                     }
                     const float* wt = wl + (kh * g.k + kw) * g.Cin * 4 + c;       // [tap][co][Cin]
                     const float4 w0 = *reinterpret_cast<const float4*>(wt);            // co 0, channels c..c+3
                     const float4 w1 = *reinterpret_cast<const float4*>(wt + g.Cin);
                     const float4 w2 = *reinterpret_cast<const float4*>(wt + 2 * g.Cin);
-                    for (int e = 0; e < 2; ++e) {
+                    for (int e = 0; e < 3; ++e) {
                         const int wo = wos[e];
                         if (wo < 0 || wo >= g.W) continue;
                         const float* d = dy + ((b * g.H + ho) * g.W + wo) * g.Cout;
@@ -263,9 +265,16 @@ __global__ __launch_bounds__(256) void rgb_wgrad_reduce_kernel(const float* __re
 
 using namespace bg;
 
+// k = 1 or 3 only: the tap counts the weight-gradient kernel is instantiated for (a layer takes all three passes here or
+// none, functional.Conv2dFn decides once in forward); reflect padding within tf.pad's rule (pad_lo, pad_hi <= H - 1, W - 1)
 static bool rgb_supported(const BgConvDesc* d) {
-    return d && d->Cout <= 3 && d->stride == 1 && d->k * d->k <= RGB_MAXTAPS && d->Cin % 4 == 0 &&
-           d->Ho == d->H && d->Wo == d->W && (size_t)d->k * d->k * d->Cin * 4 * sizeof(float) <= 60 * 1024;
+    if (!(d && d->Cout >= 1 && d->Cout <= 3 && d->stride == 1 && (d->k == 1 || d->k == 3) && d->Cin > 0 && d->Cin % 4 == 0 &&
+          d->N > 0 && d->H > 0 && d->W > 0 && d->Ho == d->H && d->Wo == d->W && d->pad_lo >= 0 && d->pad_lo < d->k &&
+          (size_t)d->k * d->k * d->Cin * 4 * sizeof(float) <= 60 * 1024))
+        return false;
+    if (d->pad_mode == BG_PAD_ZERO) return true;
+    const int lim = (d->H < d->W ? d->H : d->W) - 1;
+    return d->pad_mode == BG_PAD_REFLECT && d->pad_lo <= lim && d->k - 1 - d->pad_lo <= lim;
 }
 
 static RgbGeom rgb_geom(const BgConvDesc* d) {

@@ -417,8 +417,10 @@ def _bias_grad(dy2d, out):
 # ------------------------------------------------------------------------------------------
 # conv / transposed conv
 # ------------------------------------------------------------------------------------------
-def _resident_ok(x, cin, cout):
-    return x.dtype == BF16 and cin % 8 == 0 and cout % 8 == 0
+def _resident_ok(x, cin, cout, k=1):
+    """The bf16-resident kernels (csrc/igemm16.hip) take channel counts that are multiples of 8 and kernels of at most
+    4 x 4 taps (include/biggan_hip.h); every other layer runs on the fp32-tensor kernels."""
+    return x.dtype == BF16 and cin % 8 == 0 and cout % 8 == 0 and k <= 4
 
 
 def pad_channels(x, C, dtype, axis=-1, mode=hip.PAD_ZERO_FILL):
@@ -465,9 +467,9 @@ class Conv2dFn(Function):
         k, _, cin2, Cout = w.shape
         assert cin2 == Cin, (x.shape, w.shape)
         L = lib()
-        ctx.resident = _resident_ok(x, Cin, Cout)
+        ctx.resident = _resident_ok(x, Cin, Cout, k)
         ctx.in_dtype = x.dtype
-        ctx.pad8 = None if ctx.resident else _thin_plan(x, Cin, Cout)
+        ctx.pad8 = None if ctx.resident or k > 4 else _thin_plan(x, Cin, Cout)
         ctx.acc = accumulate_into is not None
         if ctx.acc:          # residual sum fused into the epilogue: accumulate_into += conv(x)   (ops.py:313)
             assert ctx.pad8 is None and tuple(accumulate_into.shape) == (N, Ho, Wo, Cout), "accumulate_into: shape"
@@ -712,7 +714,7 @@ class Deconv2dFn(Function):
         N, H, W_, Cin = x.shape
         k, _, Cout, cin2 = w.shape
         assert cin2 == Cin, (x.shape, w.shape)
-        ctx.resident = _resident_ok(x, Cin, Cout)
+        ctx.resident = _resident_ok(x, Cin, Cout, k)
         ctx.in_dtype = x.dtype
         if x.dtype == BF16 and not ctx.resident:
             x = cast(x, torch.float32)

@@ -260,9 +260,9 @@ def conv(x, channels, opt, kernel=4, stride=2, pad=0, dilation=1, use_bias=True,
             return _add(y if _out_dtype is not None else _resident_out(y), acc)
         if acc is not None:
             # the fused form needs an accumulator of the result's own type and shape that this call may overwrite
-            want = (_out_dtype or (torch.bfloat16 if Fn._resident_ok(x, Cin, channels) else torch.float32))
+            want = (_out_dtype or (torch.bfloat16 if Fn._resident_ok(x, Cin, channels, kernel) else torch.float32))
             if (acc.dtype != want or not acc.is_contiguous() or Fn._thin_plan(x, Cin, channels) is not None
-                    or (x.dtype == torch.bfloat16 and not Fn._resident_ok(x, Cin, channels))):
+                    or (x.dtype == torch.bfloat16 and not Fn._resident_ok(x, Cin, channels, kernel))):
                 y = Fn.Conv2dFn.apply(x, wk, bias, stride, pad_lo, Ho, Wo, pad_mode, _out_dtype)
                 return _add(y if _out_dtype is not None else _resident_out(y), acc)
         y = Fn.Conv2dFn.apply(x, wk, bias, stride, pad_lo, Ho, Wo, pad_mode, _out_dtype, acc)

@@ -97,8 +97,18 @@ typedef struct BgConvDesc {
  *     forward of deconv: [k*k][Cout][Cin]      input gradient of deconv: [k*k][Cin][Cout]
  * i.e. for each op one of the two copies bg_spectral_norm_batch_fwd writes next to w / sigma (BgSnItem::pack_p =
  * the variable's own order, pack_t = the two inner axes swapped).  Channel counts must be multiples of 8.  The
+ * forward and the input gradient take kernels of at most 4 x 4 taps (k <= 4): with a larger k bg_conv2d_fwd /
+ * bg_conv2d_dgrad / bg_deconv2d_fwd / bg_deconv2d_dgrad return BG_ERR_ARG and a message, and callers run the layer
+ * on the fp32-tensor kernels (functional._resident_ok).  The
  * other tensor of the call may be bf16 or fp32 (its dtype field); weight gradients are always fp32.  With
- * BG_PAD_REFLECT the input gradient is computed on the padded grid and folded back (scratch from ws). */
+ * BG_PAD_REFLECT the input gradient is computed on the padded grid and folded back (scratch from ws), or, for
+ * 3 x 3 windows with one row of padding on maps of at least 4 x 4, by mirrored-tap launches on the map itself.
+ *
+ * Geometry every conv entry point accepts (check_conv): 1 <= k <= 7, stride 1 or 2, 0 <= pad_lo < k, pad_lo < H,
+ * the last window starting inside the input, and for BG_PAD_REFLECT tf.pad's rule pad_lo, pad_hi <= H - 1, W - 1
+ * (pad_hi = (Ho - 1) stride + k - 1 - pad_lo - (H - 1)); the input gradient also needs H, W multiples of the
+ * stride.  Within that, every map size (down to 2 x 2, non-square), both splits of an odd total padding and maps
+ * on which one row mirrors both borders (H <= pad_lo + pad_hi + 1) are computed. */
 
 /* Every MFMA GEMM entry point takes caller-provided scratch (ws, ws_bytes) sized by the matching
  * *_workspace_bytes(): it holds split-K partial slabs for layers whose output is too small to fill
@@ -159,7 +169,12 @@ int bg_deconv2d_wgrad(const BgConvDesc*, const void* x, const void* dy, float* d
 
 /* Direct (vector-ALU, HBM-bound) path for k x k stride-1 convolutions with <= 3 output channels:
  * the generator's RGB head G_logit (BigGAN.py:570 -> ops.py:49-113).  Same arithmetic as
- * bg_conv2d_*; bg_rgbconv_supported tells whether a geometry qualifies. */
+ * bg_conv2d_*; bg_rgbconv_supported tells whether a geometry qualifies.
+ * bg_rgbconv_supported(d) == 1 means that ALL THREE passes (fwd, dgrad, wgrad) compute d, so a caller decides once per
+ * layer: fp32 tensors, 1 <= Cout <= 3, Cin % 4 == 0, stride 1, Ho x Wo = H x W, k = 1 or 3, any 0 <= pad_lo < k
+ * (pad_hi = k - 1 - pad_lo, the two may differ), k * k * Cin * 16 bytes <= 60 KB of LDS, and for BG_PAD_REFLECT
+ * pad_lo, pad_hi <= min(H, W) - 1.  That includes maps on which a row mirrors both borders (H <= pad_lo + pad_hi + 1:
+ * the input gradient takes both mirrors).  Every other geometry runs on bg_conv2d_*. */
 int bg_rgbconv_supported(const BgConvDesc*);
 int bg_rgbconv_fwd  (const BgConvDesc*, const float* x, const float* w, const float* bias, float* y,
                      int accumulate, void* stream);
@@ -307,6 +322,9 @@ int bg_attention2_bwd(const float* q, const float* k, const float* v, const floa
  * Probabilities are rounded to bf16 before the P V product (fp32 accumulation); deterministic, no atomics.
  * bwd: dq may be NULL, or dk and dv_out may both be NULL (the two gradient kernels are independent); delta_ws is
  * (re)computed by a call that produces dk / dv and reused as it stands by a dq-only call.
+ * bg_attention16_supported(N, Nk, d, dv) == 1 means that fwd and both bwd calls compute EVERY column of every output
+ * for that shape: each (d, dv) with d % 4 == 0, d <= 64, dv % 4 == 0, dv <= 256 in any combination (d <= 16 with
+ * dv > 128 included), N and Nk any multiples of 128, equal or not.
  * ------------------------------------------------------------------------------------------ */
 typedef struct BgAttn16Desc {
     int32_t B, N, Nk, d, dv;

@@ -11,10 +11,14 @@ Test helper, not product code.  Three parts:
   point times its absolute-value term); an fp32 output must satisfy ``|got - ref| <= E + 2^-24 |ref|``, a bf16 output
   ``RNE(ref - E) <= got <= RNE(ref + E)``;
 * ``Recorder`` / ``replay`` - a proxy over ``functional.lib`` / ``hip.lib`` keeps the descriptor and flags of every
-  conv / deconv / attention16 / gram16 / gemm call of an iteration (deduplicated), and ``replay`` runs each unique
+  conv / deconv / rgbconv / attention16 / attention2 / gram16 / gemm call of an iteration (deduplicated), and ``replay``
+  runs each unique
   call again through the same entry point on fresh bf16-exact buffers: NaN-prefilled (or random, when accumulating)
   outputs behind and before which sit guard bands, two runs that must agree bit for bit, and the ``bg_prof`` set of
   (tag, kernel symbol) pairs, which must equal the recorded iteration's.
+
+``tests/geometry_sweep.py`` builds lists of ``Call`` objects for the geometries the entry points accept but no benchmark
+model builds; they go through the same ``replay_all``.
 """
 import collections
 import ctypes
@@ -215,9 +219,11 @@ def gate(got, ref, E):
 # ------------------------------------------------------------------------------------------
 CONV = ("bg_conv2d_fwd", "bg_conv2d_dgrad", "bg_conv2d_wgrad", "bg_deconv2d_fwd", "bg_deconv2d_fwd_stats",
         "bg_deconv2d_dgrad", "bg_deconv2d_wgrad")
-RECORDED = CONV + ("bg_attention16_fwd", "bg_attention16_bwd", "bg_gram16", "bg_gemm")
-# profiled families the replay does not cover (the fp32 fused attention of bg_attention2_*)
-UNREPLAYED_TAGS = ("attention2_",)
+RGBCONV = ("bg_rgbconv_fwd", "bg_rgbconv_dgrad", "bg_rgbconv_wgrad")          # (these emit no bg_prof record)
+RECORDED = CONV + RGBCONV + ("bg_attention16_fwd", "bg_attention16_bwd", "bg_attention2_fwd", "bg_attention2_bwd",
+                             "bg_gram16", "bg_gemm")
+# profiled families the replay does not cover (none: every GEMM-family tag is replayed)
+UNREPLAYED_TAGS = ()
 
 
 def _addr(p):
@@ -263,6 +269,21 @@ def _describe(name, a):
     if name in ("bg_conv2d_wgrad", "bg_deconv2d_wgrad"):
         d, x, dy, dw, ws, nb = a[:6]
         return _struct(d), dict(ws=int(nb) if _addr(ws) else 0), al(x, dy, dw)
+    if name == "bg_rgbconv_fwd":
+        d, x, w, bias, y, acc = a[:6]
+        return _struct(d), dict(bias=bool(_addr(bias)), acc=int(acc)), al(x, w, y)
+    if name == "bg_rgbconv_dgrad":
+        d, dy, w, dx, acc = a[:5]
+        return _struct(d), dict(acc=int(acc)), al(dy, w, dx)
+    if name == "bg_rgbconv_wgrad":
+        d, x, dy, dw, ws, nb = a[:6]
+        return _struct(d), dict(ws=int(nb) if _addr(ws) else 0), al(x, dy, dw)
+    if name == "bg_attention2_fwd":
+        q, k, v, o, lse = a[:5]
+        return tuple(int(t) for t in a[5:10]), {}, al(q, k, v, o)
+    if name == "bg_attention2_bwd":
+        q, k, v, o, do, lse, dq, dk, dv, delta = a[:10]
+        return tuple(int(t) for t in a[10:15]), {}, al(q, k, v, o, do, dq, dk, dv)
     if name == "bg_attention16_fwd":
         D, q, k, v, o, lse = a[:6]
         return _struct(D), {}, al(q, k, v, o)
@@ -412,6 +433,20 @@ def mirror_mask(d, device):
     return (mh[:, None] | mw[None, :]).double()[..., None]
 
 
+def dgrad_ring_form(d):
+    """Whether the bf16-resident input gradient of reflect-padded conv `d` takes the ring form (plain launch + mirrored-tap
+    launches) and not the padded grid + fold: the rule of dgrad_ring_ok (csrc/igemm.hip), BG_DGRAD_RING included."""
+    e = os.environ.get("BG_DGRAD_RING")
+    if e is not None and e.strip() == "0":
+        return False
+    forced = e is not None and e.strip() == "1"
+    need = 32 if d.H >= 32 else (96 if d.H >= 16 else 160)
+    if not forced and d.N < need:
+        return False
+    return (d.pad_mode == PAD_REFLECT and d.pad_lo == 1 and d.k == 3 and d.stride in (1, 2) and d.H >= 4 and d.W >= 4 and
+            d.H % d.stride == 0 and d.W % d.stride == 0 and d.Ho == d.H // d.stride and d.Wo == d.W // d.stride)
+
+
 def bf16_exact(shape, gen, device, scale=1.0, dtype=torch.float32):
     t = (torch.randn(shape, generator=gen, device=device) * scale).to(torch.bfloat16)
     return t.to(dtype)
@@ -447,6 +482,7 @@ class Replayer:
         self.subset_over = subset_over
         self.stats = stats if stats is not None else GateStats()
         self.failures = []
+        self.entry = "?"
 
     def stream(self):
         from biggan_tensorflow_amd import hip
@@ -489,7 +525,7 @@ class Replayer:
                 finally:
                     got = prof_take(L)
                 self.prof |= got
-                kern = " + ".join(sorted({k for _, k in got})) or "?"
+                kern = " + ".join(sorted({k for _, k in got})) or self.entry      # (rgbconv: no bg_prof record)
                 self.stats.launch(kern)
                 first = [o.raw.clone() for o in outs if o.dtype != torch.uint8]
             else:
@@ -525,6 +561,7 @@ class Replayer:
 
     # -- entry points
     def replay(self, c):
+        self.entry = c.name
         fn = getattr(self, "_" + c.name[3:])
         return fn(c)
 
@@ -566,14 +603,16 @@ class Replayer:
         bias = bf16_exact((d.Cout,), self.gen, self.dev) if f.get("bias") else None
         alpha = torch.full((1,), 0.5, device=self.dev) if f.get("alpha") else None
         y = self.out((d.N, d.Ho, d.Wo, d.Cout), _dt(d.y_dtype), c.align[2], acc=bool(f["acc"]))
-        ws = self.ws(f["ws"])
+        ws = self.ws(f.get("ws", 0))
         stats = "stats_ws" in f
         sums = Buf(2 * d.Cout, torch.float64, self.dev) if stats else None
         sws = self.ws(f.get("stats_ws", 0))
         P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())     # noqa: E731
 
         def run():
-            if stats:
+            if c.name == "bg_rgbconv_fwd":
+                rc = L.bg_rgbconv_fwd(d, x.ptr(), wb.ptr(), P(bias), y.ptr(), f["acc"], self.stream())
+            elif stats:
                 rc = L.bg_deconv2d_fwd_stats(d, x.ptr(), wb.ptr(), P(bias), P(alpha), y.ptr(), f["acc"], sums.ptr(),
                                              sws.ptr() if sws else None, f["stats_ws"], ws.ptr() if ws else None,
                                              f["ws"], self.stream())
@@ -627,6 +666,17 @@ class Replayer:
     def _deconv2d_fwd_stats(self, c):
         return self._conv_or_deconv_fwd(c, True)
 
+    # bg_rgbconv_*: the same three functions as bg_conv2d_* (fp32 tensors, stride 1, <= 3 output channels) on direct
+    # vector-ALU kernels - fp32 FMA chains over the same terms, so the same references and the same bound(A, K)
+    def _rgbconv_fwd(self, c):
+        return self._conv_or_deconv_fwd(c, False)
+
+    def _rgbconv_dgrad(self, c):
+        return self._dgrad(c, False)
+
+    def _rgbconv_wgrad(self, c):
+        return self._wgrad(c, False)
+
     def _dgrad(self, c, deconv):
         L = self.L
         d = self._conv_common(c)
@@ -635,10 +685,12 @@ class Replayer:
         w, wb = self._weights(c, d, deconv, False)
         alpha = torch.full((1,), 0.5, device=self.dev) if f.get("alpha") else None
         dx = self.out((d.N, d.H, d.W, d.Cin), _dt(d.x_dtype), c.align[2], acc=bool(f["acc"]))
-        ws = self.ws(f["ws"])
+        ws = self.ws(f.get("ws", 0))
         ent = L.bg_deconv2d_dgrad if deconv else L.bg_conv2d_dgrad
 
         def run():
+            if c.name == "bg_rgbconv_dgrad":
+                return self.check(L.bg_rgbconv_dgrad(d, dy.ptr(), wb.ptr(), dx.ptr(), f["acc"], self.stream()), c.name)
             ap = None if alpha is None else ctypes.c_void_p(alpha.data_ptr())
             self.check(ent(d, dy.ptr(), wb.ptr(), ap, dx.ptr(), f["acc"], ws.ptr() if ws else None, f["ws"],
                            self.stream()), c.name)
@@ -662,8 +714,13 @@ class Replayer:
             # the bf16 input gradient of a reflect-padded conv is rounded once more where the mirrored taps land: the
             # padded-grid form stores the grid in bf16 before folding it, the ring form adds the mirrored taps to the
             # plain launch's bf16 output.  One bf16 unit of the partial sum on those pixels (rows / columns whose padded
-            # source appears twice); every other pixel keeps the single-rounding bracket
-            extra = U16 * A * mirror_mask(d, self.dev)
+            # source appears twice); every other pixel keeps the single-rounding bracket.  The padded-grid form that
+            # ACCUMULATES rounds twice on every pixel: reflect_fold_kernel (csrc/igemm16.hip) reads the bf16 grid, adds the
+            # old dx in fp32 and rounds the sum to bf16 - so there the unit of the grid's rounding applies everywhere
+            mask = mirror_mask(d, self.dev)
+            if dx.y0 is not None and not dgrad_ring_form(d) and (d.pad_lo > 0 or bool(mask.any())):
+                mask = torch.ones_like(mask)
+            extra = U16 * A * mask
         if dx.y0 is not None:
             y0 = dx.y0.view(dx.view.shape).index_select(0, idx).double()
             ref, A = ref + y0, A + y0.abs()
@@ -685,6 +742,8 @@ class Replayer:
         dw = self.out(shape, torch.float32, c.align[2])
         ws = self.ws(f["ws"])
         ent = L.bg_deconv2d_wgrad if deconv else L.bg_conv2d_wgrad
+        if c.name == "bg_rgbconv_wgrad":
+            ent = L.bg_rgbconv_wgrad
 
         def run():
             self.check(ent(d, x.ptr(), dy.ptr(), dw.ptr(), ws.ptr() if ws else None, f["ws"], self.stream()), c.name)
@@ -762,20 +821,31 @@ class Replayer:
         self.record(kern, "bg_gemm", Cb.view, ref, bound(Aabs, d.K))
 
     # -- attention
-    def _attn_bufs(self, D, c):
+    def _attn_desc(self, c):
+        """-> (D, element type, unit roundoff of P / dS / the outputs).  bg_attention16_*: the recorded BgAttn16Desc, bf16;
+        bg_attention2_*: (B, N, Nk, d, dv) as the same fields with the strides of contiguous fp32 tensors."""
+        if c.name.startswith("bg_attention16"):
+            from biggan_tensorflow_amd import hip
+            return hip.BgAttn16Desc(*c.desc), torch.bfloat16, U16
+        B, N, Nk, d, dv = c.desc
+        D = collections.namedtuple("Attn2Desc", "B N Nk d dv ldq sq ldk sk ldv sv ldo so ldg sg lddq sdq lddk sdk lddv sdv")(
+            B, N, Nk, d, dv, d, N * d, d, Nk * d, dv, Nk * dv, dv, N * dv, dv, N * dv, d, N * d, d, Nk * d, dv, Nk * dv)
+        return D, torch.float32, U32
+
+    def _attn_bufs(self, D, c, dtype=torch.bfloat16):
         """q, k, v, o as column slices of [B, rows, ld] buffers with the recorded strides."""
-        def sl(rows, width, ld, s, align, dtype=torch.bfloat16):
+        def sl(rows, width, ld, s, align):
             n = (D.B - 1) * s + (rows - 1) * ld + width
             return Buf(n, dtype, self.dev, align, size=(D.B, rows, width), stride=(s, ld, 1))
         return sl
 
-    def _attn_inputs(self, D, c):
-        sl = self._attn_bufs(D, c)
+    def _attn_inputs(self, D, c, dtype=torch.bfloat16):
+        sl = self._attn_bufs(D, c, dtype)
         q = sl(D.N, D.d, D.ldq, D.sq, c.align[0])
         k = sl(D.Nk, D.d, D.ldk, D.sk, c.align[1])
         v = sl(D.Nk, D.dv, D.ldv, D.sv, c.align[2])
         for b, scale in ((q, 0.5), (k, 0.5), (v, 1.0)):
-            b.y0 = bf16_exact(b.size, self.gen, self.dev, scale, torch.bfloat16)
+            b.y0 = bf16_exact(b.size, self.gen, self.dev, scale, dtype)
             b.prefill()
         return sl, q, k, v
 
@@ -789,40 +859,52 @@ class Replayer:
         rel = 2.0 * eS.amax(2) + 4.0 * U32 * (S.abs().amax(2) + lse.abs() + 2.0)
         return qd, kd, vd, S, lse, P, rel
 
-    def _attention16_fwd(self, c):
-        from biggan_tensorflow_amd import hip
-        D = hip.BgAttn16Desc(*c.desc)
-        sl, q, k, v = self._attn_inputs(D, c)
+    def _attn_fwd(self, c):
+        """bg_attention16_fwd and bg_attention2_fwd.  The bound's rounding points: the fp32 accumulation of P v over Nk keys
+        (online-softmax rescaling included), P's own rounding U before the product (bf16 in attention16.hip; in
+        attention.hip P stays fp32, so U = U32 stands for the rounding of exp's result), the output's division by the row
+        sum, and `rel` (the S error through exp, the exponent's argument).  attention.hip has no rounding point beyond
+        these: its S, P v and dP are fp32 MFMA chains, exp / log are the same v_exp_f32 / v_log_f32 forms."""
+        D, dtype, U = self._attn_desc(c)
+        sl, q, k, v = self._attn_inputs(D, c, dtype)
         o = sl(D.N, D.dv, D.ldo, D.so, c.align[3])
         lse = Buf(D.B * D.N, torch.float32, self.dev)
 
         def run():
-            self.check(self.L.bg_attention16_fwd(D, q.ptr(), k.ptr(), v.ptr(), o.ptr(), lse.ptr(), self.stream()),
-                       "bg_attention16_fwd")
+            if dtype == torch.bfloat16:
+                rc = self.L.bg_attention16_fwd(D, q.ptr(), k.ptr(), v.ptr(), o.ptr(), lse.ptr(), self.stream())
+            else:
+                rc = self.L.bg_attention2_fwd(q.ptr(), k.ptr(), v.ptr(), o.ptr(), lse.ptr(), D.B, D.N, D.Nk, D.d, D.dv,
+                                              self.stream())
+            self.check(rc, c.name)
         kern, err = self._twice(run, [o, lse])
         if err:
-            return self.fail(kern, "bg_attention16_fwd " + err)
+            return self.fail(kern, c.name + " " + err)
         if bool(torch.isnan(o.view.float()).any()) or bool(torch.isnan(lse.view).any()):
-            return self.fail(kern, "bg_attention16_fwd left outputs unwritten")
+            return self.fail(kern, c.name + " left outputs unwritten")
         sel = torch.tensor(self._sel(D.B), device=self.dev)
         for part in torch.split(sel, max(1, (1 << 28) // (D.N * D.Nk))):
             qd, kd, vd, S, _, P, rel = self._attn16_fwd_ref(q, k, v, part)
             ref, lref = attn_fwd(qd, kd, vd)
             Pv = P @ vd.abs()
-            E = bound(Pv, D.Nk, (U16 + rel)[..., None] * Pv)
-            self.record(kern, "bg_attention16_fwd o", o.view.index_select(0, part), ref, E)
+            E = bound(Pv, D.Nk, (U + rel)[..., None] * Pv)
+            self.record(kern, c.name + " o", o.view.index_select(0, part), ref, E)
             lg = lse.view.view(D.B, D.N).index_select(0, part)
-            self.record(kern, "bg_attention16_fwd lse", lg, lref, rel + 8.0 * U32 * (lref.abs() + 1.0))
+            self.record(kern, c.name + " lse", lg, lref, rel + 8.0 * U32 * (lref.abs() + 1.0))
 
-    def _attention16_bwd(self, c):
-        from biggan_tensorflow_amd import hip
-        D = hip.BgAttn16Desc(*c.desc)
-        f = c.flags
-        sl, q, k, v = self._attn_inputs(D, c)
+    _attention16_fwd = _attention2_fwd = _attn_fwd
+
+    def _attn_bwd(self, c):
+        """bg_attention16_bwd (dq and / or dk + dv, per the recorded flags) and bg_attention2_bwd (always all three, delta
+        computed by the call).  U = the rounding of P and of dS before their products: bf16 in attention16.hip, fp32 in
+        attention.hip (U32: exp's result, the dS product)."""
+        D, dtype, U = self._attn_desc(c)
+        f = c.flags if dtype == torch.bfloat16 else dict(dq=True, dk=True, dv=True)
+        sl, q, k, v = self._attn_inputs(D, c, dtype)
         o = sl(D.N, D.dv, D.ldo, D.so, c.align[3])
         do = sl(D.N, D.dv, D.ldg, D.sg, c.align[4])
-        o.y0 = bf16_exact(o.size, self.gen, self.dev, 0.5, torch.bfloat16)
-        do.y0 = bf16_exact(do.size, self.gen, self.dev, 1.0, torch.bfloat16)
+        o.y0 = bf16_exact(o.size, self.gen, self.dev, 0.5, dtype)
+        do.y0 = bf16_exact(do.size, self.gen, self.dev, 1.0, dtype)
         o.prefill()
         do.prefill()
         # lse from float64 (the forward's output, as fp32); delta = rowsum(dO o) for a dq-only call that reuses it
@@ -852,16 +934,20 @@ class Replayer:
             outs.append(dv)
 
         def run():
-            self.check(self.L.bg_attention16_bwd(D, q.ptr(), k.ptr(), v.ptr(), o.ptr(), do.ptr(), lse.ptr(),
-                                                 dq.ptr() if dq else None, dk.ptr() if dk else None,
-                                                 dv.ptr() if dv else None, delta.ptr(), self.stream()),
-                       "bg_attention16_bwd")
+            if dtype == torch.bfloat16:
+                rc = self.L.bg_attention16_bwd(D, q.ptr(), k.ptr(), v.ptr(), o.ptr(), do.ptr(), lse.ptr(),
+                                               dq.ptr() if dq else None, dk.ptr() if dk else None,
+                                               dv.ptr() if dv else None, delta.ptr(), self.stream())
+            else:
+                rc = self.L.bg_attention2_bwd(q.ptr(), k.ptr(), v.ptr(), o.ptr(), do.ptr(), lse.ptr(), dq.ptr(), dk.ptr(),
+                                              dv.ptr(), delta.ptr(), D.B, D.N, D.Nk, D.d, D.dv, self.stream())
+            self.check(rc, c.name)
         kern, err = self._twice(run, outs + [delta])
         if err:
-            return self.fail(kern, "bg_attention16_bwd " + err)
+            return self.fail(kern, c.name + " " + err)
         for b in outs:
             if bool(torch.isnan(b.view.float()).any()):
-                return self.fail(kern, "bg_attention16_bwd left outputs unwritten")
+                return self.fail(kern, c.name + " left outputs unwritten")
         sel = torch.tensor(self._sel(D.B), device=self.dev)
         for part in torch.split(sel, max(1, (1 << 27) // (D.N * D.Nk))):
             qd, kd, vd, S, _, _, rel = self._attn16_fwd_ref(q, k, v, part)
@@ -872,20 +958,22 @@ class Replayer:
             rdq, rdk, rdv = attn_bwd(qd, kd, vd, dod, P, dlt)
             # |.| term of dS: P (|dO| |v|^T + sum |dO| |o|); relative coefficient: bf16 dS, bf16 P, S error, dP sums
             T = P * (dod.abs() @ vd.abs().transpose(1, 2) + (dod.abs() * od.abs()).sum(2)[..., None])
-            relb = (2.0 * U16 + rel + (8.0 * math.sqrt(D.dv) + 2.0) * U32)[..., None]
+            relb = (2.0 * U + rel + (8.0 * math.sqrt(D.dv) + 2.0) * U32)[..., None]
             if dq is not None:
                 A = T @ kd.abs()
-                self.record(kern, "bg_attention16_bwd dq", dq.view.index_select(0, part), rdq,
+                self.record(kern, c.name + " dq", dq.view.index_select(0, part), rdq,
                             bound(A, D.Nk, (relb * T) @ kd.abs()))
             if dk is not None:
                 A = T.transpose(1, 2) @ qd.abs()
-                self.record(kern, "bg_attention16_bwd dk", dk.view.index_select(0, part), rdk,
+                self.record(kern, c.name + " dk", dk.view.index_select(0, part), rdk,
                             bound(A, D.N, (relb * T).transpose(1, 2) @ qd.abs()))
             if dv is not None:
                 A = P.transpose(1, 2) @ dod.abs()
-                relp = (U16 + rel)[..., None]
-                self.record(kern, "bg_attention16_bwd dv", dv.view.index_select(0, part), rdv,
+                relp = (U + rel)[..., None]
+                self.record(kern, c.name + " dv", dv.view.index_select(0, part), rdv,
                             bound(A, D.N, (relp * P).transpose(1, 2) @ dod.abs()))
+
+    _attention16_bwd = _attention2_bwd = _attn_bwd
 
 
 def replay_all(calls, L, subset_over=16, stats=None):

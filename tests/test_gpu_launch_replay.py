@@ -1,9 +1,12 @@
 """Every GEMM-family launch of one D op and one G op of the benchmark's workloads, replayed against float64.
 
-tests/launch_replay.py records the unique conv / deconv / attention16 / gram16 / gemm calls of the iteration and replays
-each through the same entry point on bf16-exact operands; the gate bounds every output element by its fp32
-accumulation error (or brackets it between the bf16 roundings of ref -/+ that bound).  The replay's (tag, kernel symbol)
-set must equal the iteration's, so the check covers exactly the production dispatch."""
+tests/launch_replay.py records the unique conv / deconv / rgbconv / attention16 / attention2 / gram16 / gemm calls of the
+iteration and replays each through the same entry point on bf16-exact operands; the gate bounds every output element by
+its fp32 accumulation error (or brackets it between the bf16 roundings of ref -/+ that bound).  The replay's (tag, kernel
+symbol) set must equal the iteration's, so the check covers exactly the production dispatch.  The generator's RGB head
+(bg_rgbconv_*, rows keyed by the entry name: those launches have no profile record) and the fp32 fused attention
+(bg_attention2_*, float64 reference over launch_replay.image_subset) are part of the c2@64-fp32 replay; measured on an
+MI355X: 6.9 s of replay for c3@256, 2.0 s for c2@64-fp32, 19 s for the two cases with their model builds."""
 import time
 
 import pytest

@@ -225,3 +225,176 @@ def test_gate_rejects_a_write_past_the_output():
     s.flat[4] = 2.0                                                # column 4 of row 0 lies outside the slice
     assert not s.guards_ok()
     print("mutation %-34s rejected: guard band changed" % "write one element past the output")
+
+
+# ------------------------------------------------------------------------------------------
+# the geometry sweep (tests/geometry_sweep.py): its references, its mutation checks, the generator itself
+# ------------------------------------------------------------------------------------------
+from tests import geometry_sweep as G                                              # noqa: E402
+
+_REFLECT_GEOMS = G.conv_geometries(R.PAD_REFLECT)
+
+
+def _geom_id(g):
+    return "%dx%d-k%d-s%d-pad%d+%d" % (g.H, g.W, g.k, g.stride, g.pad_lo, g.pad_hi)
+
+
+def test_sweep_has_the_geometries_where_the_kernels_were_wrong():
+    have = {(g.H, g.W, g.k, g.stride, g.pad_lo, g.pad_hi) for g in _REFLECT_GEOMS}
+    assert (3, 3, 3, 1, 1, 1) in have                               # a row that mirrors both borders
+    assert (4, 4, 5, 1, 2, 2) in have
+    assert (4, 4, 4, 1, 1, 2) in have and (8, 8, 4, 1, 1, 2) in have                # even k at stride 1: unequal pads
+    assert (4, 4, 5, 2, 1, 2) in have and (4, 4, 5, 2, 2, 1) in have                # k = 5 at stride 2, both splits
+    assert (3, 5, 3, 1, 1, 1) in have and (5, 4, 7, 1, 3, 3) in have                # non-square maps
+
+
+@pytest.mark.parametrize("mode", [R.PAD_REFLECT, R.PAD_ZERO])
+def test_conv_references_match_autograd_at_every_sweep_geometry(mode):
+    """conv_fwd / conv_dgrad / conv_wgrad against float64 autograd of F.pad + conv2d at EVERY geometry of the sweep: the
+    reference must be right exactly where the kernels were wrong (doubly mirrored rows, unequal pads, both splits)."""
+    for g in G.conv_geometries(mode):
+        x = _rand((2, g.H, g.W, 3), 41).requires_grad_(True)
+        w = _rand((g.k, g.k, 3, 2), 42).requires_grad_(True)
+        xp = F.pad(x.permute(0, 3, 1, 2), (g.pad_lo, g.pad_hi, g.pad_lo, g.pad_hi),
+                   mode="reflect" if mode == R.PAD_REFLECT and g.pad_lo + g.pad_hi else "constant")
+        y = F.conv2d(xp, w.permute(3, 2, 0, 1), stride=g.stride).permute(0, 2, 3, 1)
+        assert tuple(y.shape) == (2, g.Ho, g.Wo, 2), _geom_id(g)
+        dy = _rand(tuple(y.shape), 43)
+        y.backward(dy)
+        xd, wd = x.detach(), w.detach()
+        assert torch.allclose(R.conv_fwd(xd, wd, g.stride, g.pad_lo, g.Ho, g.Wo, mode), y.detach(), atol=1e-12), _geom_id(g)
+        assert torch.allclose(R.conv_dgrad(dy, wd, g.stride, g.pad_lo, g.H, g.W, mode), x.grad, atol=1e-12), _geom_id(g)
+        assert torch.allclose(R.conv_wgrad(xd, dy, g.k, g.stride, g.pad_lo, mode), w.grad, atol=1e-11), _geom_id(g)
+
+
+def _mirror_rows(n, n_pad, lo, hi, variant):
+    """Padded positions that fold onto each row of an n-row map, as an input-gradient kernel enumerates them: the row
+    itself, its mirror below the map (1 <= o <= lo) and above it (n - 1 - hi <= o <= n - 2).  variant "truth", or one of the
+    two defects: "else_if" drops the second mirror of a row that has both, "lo_for_hi" takes the high range with lo."""
+    rows = []
+    for o in range(n):
+        pos = [o + lo]
+        low = 1 <= o <= lo
+        high = n - 1 - (lo if variant == "lo_for_hi" else hi) <= o <= n - 2
+        if low:
+            pos.append(lo - o)
+        if high and not (low and variant == "else_if"):
+            pos.append(2 * (n - 1) - o + lo)
+        rows.append([u for u in pos if 0 <= u < n_pad])
+    return rows
+
+
+def _variant_dgrad(dy, w, g, variant):
+    gp = R.tconv_full(dy, w, g.stride)                                # the gradient on the padded grid
+    for axis, n in ((1, g.H), (2, g.W)):
+        rows = _mirror_rows(n, gp.shape[axis], g.pad_lo, g.pad_hi, variant)
+        gp = torch.stack([gp.index_select(axis, torch.tensor(r, dtype=torch.long)).sum(axis) for r in rows], axis)
+    return gp
+
+
+@pytest.mark.parametrize("variant", ["else_if", "lo_for_hi"])
+def test_gate_rejects_a_wrong_mirror_at_every_geometry_where_it_matters(variant):
+    """An input gradient built from a fold that drops the second mirror of a doubly mirrored row, or that takes the high
+    border's range with pad_lo: the gate flags it at every sweep geometry where it differs from the truth, accepts it
+    where it does not (and the truth everywhere)."""
+    flagged = []
+    for g in _REFLECT_GEOMS:
+        dy = _bf16_exact((2, g.Ho, g.Wo, 5), 51)
+        w = _bf16_exact((g.k, g.k, 6, 5), 52, 1.0 / (g.k * math.sqrt(5.0)))
+        ref = R.conv_dgrad(dy, w, g.stride, g.pad_lo, g.H, g.W, R.PAD_REFLECT)
+        A = R.conv_dgrad(dy.abs(), w.abs(), g.stride, g.pad_lo, g.H, g.W, R.PAD_REFLECT)
+        E = R.bound(A, g.k * g.k * 5 * 4)
+        truth = _variant_dgrad(dy, w, g, "truth")
+        assert torch.allclose(truth, ref, atol=1e-12), _geom_id(g)
+        assert R.gate(truth.float(), ref, E)[0], _geom_id(g)
+        got = _variant_dgrad(dy, w, g, variant)
+        differs = bool((got != truth).any())
+        ok = R.gate(got.float(), ref, E)[0]
+        assert ok != differs, (_geom_id(g), differs, ok)
+        if differs:
+            flagged.append((g.H, g.W, g.k, g.stride, g.pad_lo))
+    print("mutation %-34s rejected at %d of %d geometries" % (variant, len(flagged), len(_REFLECT_GEOMS)))
+    if variant == "else_if":
+        assert (3, 3, 3, 1, 1) in flagged and (4, 4, 5, 1, 2) in flagged and (5, 4, 5, 1, 2) in flagged
+        assert (4, 4, 3, 1, 1) not in flagged and (8, 8, 5, 1, 2) not in flagged
+    else:
+        assert (8, 8, 4, 1, 1) in flagged and (6, 6, 4, 1, 1) in flagged             # every even k at stride 1
+        assert (8, 8, 3, 1, 1) not in flagged
+
+
+def test_gate_rejects_unwritten_attention_columns():
+    """d = 16, dv = 256 on a kernel instance that stores columns < 128 only: columns 128 .. 255 keep the NaN prefill."""
+    q, k, v = _bf16_exact((1, 128, 16), 61, 0.5), _bf16_exact((1, 128, 16), 62, 0.5), _bf16_exact((1, 128, 256), 63)
+    ref, _ = R.attn_fwd(q, k, v)
+    P = torch.softmax(q @ k.transpose(1, 2), dim=2)
+    Pv = P @ v.abs()
+    E = R.bound(Pv, 128, R.U16 * Pv)
+    good = ref.to(torch.bfloat16)
+    assert R.gate(good, ref, E)[0]
+    bad = good.clone()
+    bad[:, :, 128:] = float("nan")
+    ok, _, _, _, nbad = R.gate(bad, ref, E)
+    assert not ok and nbad == 128 * 128
+    print("mutation %-34s rejected: %d outputs outside the bound" % ("attention columns 128.. unwritten", nbad))
+
+
+def test_sweep_generator_meets_the_entry_points_preconditions():
+    for mode in (R.PAD_REFLECT, R.PAD_ZERO):
+        geoms = G.conv_geometries(mode)
+        assert len(set(geoms)) == len(geoms)
+        for g in geoms:
+            assert g.H % g.stride == 0 and g.W % g.stride == 0 and 0 <= g.pad_lo < g.k and g.pad_lo < min(g.H, g.W)
+            assert g.pad_hi == (g.Ho - 1) * g.stride + g.k - 1 - g.pad_lo - (g.H - 1) or g.pad_hi == 0
+            for n, no in ((g.H, g.Ho), (g.W, g.Wo)):                # single reflection: pad_index asserts otherwise
+                idx = R.pad_index(n, g.pad_lo, (no - 1) * g.stride + g.k, mode)
+                assert len(idx) >= n or g.stride > 1
+    # every k, both strides and every map survive the preconditions
+    assert {g.k for g in _REFLECT_GEOMS} == set(G.CONV_K) and {g.stride for g in _REFLECT_GEOMS} == {1, 2}
+    assert {(g.H, g.W) for g in _REFLECT_GEOMS} == set(G.CONV_MAPS)
+
+
+def test_sweep_attention_lists_hit_both_sides_of_every_rung():
+    for edge in (16, 32):                                  # DQT rungs of A16_DISPATCH (d <= 16 | 32 | 64)
+        assert edge in G.A16_D and edge + 4 in G.A16_D
+    for edge in (32, 64, 96, 128, 192):                    # DVT rungs 1 | 2 | 3 | 4 | 6 | 8
+        assert edge in G.A16_DV and edge + 4 in G.A16_DV
+    assert min(G.A16_D) == 4 and max(G.A16_D) == 64 and min(G.A16_DV) == 4 and max(G.A16_DV) == 256
+    assert len({G.a16_instance(d, dv) for d in G.A16_D for dv in G.A16_DV}) == 10
+    assert G.a16_instance(16, 256) == (2, 8) and G.a16_instance(16, 128) == (1, 4)
+    assert 16 in G.A2_D and 20 in G.A2_D and max(G.A2_D) == 32 and max(G.A2_DV) == 128
+    for edge in (32, 64, 96):
+        assert edge in G.A2_DV and edge + 4 in G.A2_DV
+    assert len({G.a2_instance(d, dv) for d in G.A2_D for dv in G.A2_DV}) == 8
+    for kind in ("fwd", "dkv", "dq"):
+        calls = G.attention16_calls(kind, 128, 256)
+        assert len(calls) == len(G.A16_D) * len(G.A16_DV)
+        for c in calls:                                    # column slices: every row stride is 4 wider than the row
+            B, N, Nk, d, dv = c.desc[:5]
+            assert (B, N, Nk) == (1, 128, 256) and c.desc[6] == d + 4 and c.desc[10] == dv + 4 and c.desc[12] == dv + 4
+
+
+def test_sweep_lists_are_deterministic_and_bounded():
+    a, b = G.cases(), G.cases()
+    assert list(a) == list(b)
+    for cid in a:
+        assert [c.key() for c in a[cid][1]] == [c.key() for c in b[cid][1]], cid
+        assert 0 < len(a[cid][1]) <= 150, (cid, len(a[cid][1]))
+    fwd = a["conv_fwd_gemm/fp32/reflect"][1]
+    assert 0.4 <= sum(c.flags["bias"] for c in fwd) / len(fwd) <= 0.6
+    assert 0.2 <= sum(c.flags["acc"] for c in fwd) / len(fwd) <= 0.3
+
+
+def test_narrowed_rows_are_documented_and_few():
+    import os
+    header = " ".join(open(os.path.join(os.path.dirname(__file__), "..", "include", "biggan_hip.h")).read()
+                      .replace(" * ", " ").split())
+    for rule, sentence, pred in G.NARROWED:
+        assert " ".join(sentence.split()) in header, rule
+    per_family = {}
+    for cid, (_, calls) in G.cases().items():
+        n, r = per_family.get(G.family(cid), (0, 0))
+        per_family[G.family(cid)] = (n + len(calls), r + sum(G.narrowed(c) is not None for c in calls))
+    assert set(per_family) == {"conv", "deconv", "attention16", "attention2"}
+    for fam, (n, r) in per_family.items():
+        print("%-12s %5d calls, %4d narrowed (%.1f %%)" % (fam, n, r, 100.0 * r / n))
+        assert r <= G.MAX_REJECTED * n, fam
