@@ -608,27 +608,59 @@ void launch_slab_reduce(const float* ws, float* out, int64_t n, int splitk, int6
 // host side
 // ------------------------------------------------------------------------------------------
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline int kc_of(int C) { return (C + BKT - 1) / BKT; }
+
+// The form a call takes.  It is decided once, by the plan function of the pass (plan_conv_fwd ... plan_gram16 below), for
+// the workspace query and the entry point alike.  A new form gets an enumerator here, its predicate in the plan
+// function of its pass and its launch in run_nn / run_tn.
+enum Route {
+    F32_TAP,                // fp32 tap GEMM (nn_kernel): the forward passes, deconv dgrad, conv dgrad without mirrored taps
+    F32_MIRROR,             // fp32 mirrored source: conv dgrad of a reflect-padded conv, the MIRROR kernels
+    F32_PADDED_FOLD,        // fp32 padded grid + fold (conv_dgrad_fold32 geometries)
+    BF16_PLAIN,             // bf16-resident plain gather (launch_nn16: tap or halo-tile kernel)
+    BF16_RING,              // bf16-resident plain gather + the mirrored-tap ring launch (dgrad_ring_ok)
+    BF16_PADDED_FOLD,       // bf16-resident padded grid + fold
+    BF16_THIN_D2S,          // bf16 thin depth-to-space (nn16h_d2s_ok: 8-channel stride-2 input gradients)
+    BF16_THIN_D2S_RING,     //   ... followed by the ring launch
+    TN_F32,                 // pixel-reduction GEMM on fp32 tensors (launch_tn)
+    TN_BF16,                // pixel-reduction GEMM on bf16-resident tensors (launch_tn16)
+};
+static inline bool route_f32(Route r) { return r <= F32_PADDED_FOLD; }
+static inline bool route_ring(Route r) { return r == BF16_RING || r == BF16_THIN_D2S_RING; }
+
+// Everything about a call that follows from its descriptor alone: the route and the parameter block the route launches
+// (nn / nn16 / tn / tn16, tensor pointers null; the others stay zero).  The entry point binds the pointers and the
+// pointer-dependent vec flag; the query returns plan_workspace_bytes.
+struct ConvPlan {
+    Route route;
+    NNParams nn;            // F32_* routes; the BF16_* routes derive nn16 from it
+    NN16Params nn16;
+    TNParams tn;
+    TN16Params tn16;
+    int mode;               // GATHER_*
+    bool bt, mirror;        // fp32 NN kernels: weights read transposed, mirrored sources
+    bool uneven;            // fp32 NN planner: stride phases with unequal tap counts (plan_nn)
+    bool dense;             // fp32 NN: the output is one dense block, so split-K slabs can be reduced into it
+    int zdim, niter_min;    // grid z (stride phases or batch), fewest K iterations of a block
+    int64_t out_elems;      // elements of the launch's output (= of one split-K slab)
+    size_t grid_bytes;      // *_PADDED_FOLD: 256-byte-aligned size of the padded grid at the head of the workspace, else 0
+};
 
 struct NNPlan {
     int bm, bn, splitk;
 };
 
 // tile: the largest that still fills the 256 CUs; split K when even the smallest cannot
-// Stride phases with unequal tap counts (k3 s2: 1, 2, 2, 4 taps): a block of the heaviest phase runs 4x longer
+// uneven: stride phases with unequal tap counts (k3 s2: 1, 2, 2, 4 taps): a block of the heaviest phase runs 4x longer
 // than one of the lightest, so the grid needs more (smaller) blocks to keep 256 CUs busy until the end.
-static thread_local int g_plan_uneven = 0;
-struct UnevenPhases {
-    explicit UnevenPhases(const BgConvDesc* d) { g_plan_uneven = (d && d->stride > 1 && d->k % d->stride != 0) ? 1 : 0; }
-    ~UnevenPhases() { g_plan_uneven = 0; }
-};
-
-static NNPlan plan_nn(int64_t M, int N, int zdim, int niter_min, bool allow_split) {
+static NNPlan plan_nn(int64_t M, int N, int zdim, int niter_min, bool allow_split, bool uneven) {
     auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * zdim; };
     NNPlan pl;
     pl.splitk = 1;
     static const int want_uneven = getenv("BG_WANT_UNEVEN") ? atoi(getenv("BG_WANT_UNEVEN")) : 768;   // measured: 512->1024 8x8 dgrad 50 -> 79 TF/s
     static const int want_even = getenv("BG_WANT") ? atoi(getenv("BG_WANT")) : 768;      // 3 blocks per CU (sweep: profiles/README)
-    const int64_t want = g_plan_uneven ? want_uneven : want_even;
+    const int64_t want = uneven ? want_uneven : want_even;
     // narrow outputs with a long K and a handful of tiles (low-rank Gram of the cond-BN kernels: 32 x 32 x 1024
     // in ONE block = 64 serial K-steps = 44 us): split K
     auto narrow_split = [&](int bm, int bn) {
@@ -726,18 +758,22 @@ static void launch_nn_tile(NNParams& p, const NNPlan& pl, bool vec, bool bf16, i
         launch_nn_inst<1, 1, 4, 1, BT, MODE, MIRROR>(p, vec, grid, s);
 }
 
-static size_t nn_workspace_bytes(int64_t M, int N, int zdim, int niter_min, int64_t out_elems) {
-    NNPlan pl = plan_nn(M, N, zdim, niter_min, true);
-    return pl.splitk > 1 ? (size_t)pl.splitk * out_elems * sizeof(float) : 0;
+static size_t nn_workspace_bytes(const ConvPlan& cp) {
+    if (!cp.dense) return 0;
+    NNPlan pl = plan_nn(cp.nn.M, cp.nn.N, cp.zdim, cp.niter_min, true, cp.uneven);
+    return pl.splitk > 1 ? (size_t)pl.splitk * cp.out_elems * sizeof(float) : 0;
 }
 
 // the (MODE, BT) pairs that exist: CONV/BT0, TCONV/BT1 (+MIRROR), PLAIN/BT0, PLAIN/BT1
-static int launch_nn(NNParams& p, int mode, bool bt, bool mirror, bool vec, int zdim, int niter_min,
-                     int64_t out_elems, bool out_dense, void* ws, size_t ws_bytes, hipStream_t s,
-                     bool bf16 = false) {
-    NNPlan pl = plan_nn(p.M, p.N, zdim, niter_min, out_dense && ws != nullptr);
+static int launch_nn(ConvPlan& cp, bool vec, void* ws, size_t ws_bytes, hipStream_t s, bool bf16) {
+    NNParams& p = cp.nn;
+    const int mode = cp.mode, zdim = cp.zdim, niter_min = cp.niter_min;
+    const bool bt = cp.bt, mirror = cp.mirror;
+    const int64_t out_elems = cp.out_elems;
+    if (!cp.dense) ws = nullptr;
+    NNPlan pl = plan_nn(p.M, p.N, zdim, niter_min, ws != nullptr, cp.uneven);
     if (pl.splitk > 1 && ws_bytes < (size_t)pl.splitk * out_elems * sizeof(float)) {
-        pl = plan_nn(p.M, p.N, zdim, niter_min, false);
+        pl = plan_nn(p.M, p.N, zdim, niter_min, false, cp.uneven);
     }
     p.splitk = pl.splitk;
     p.slabs = reinterpret_cast<float*>(ws);
@@ -950,95 +986,10 @@ static double conv_flops(const BgConvDesc* d, bool deconv) {
     return 2.0 * px * d->k * d->k * d->Cin * d->Cout;
 }
 
-static inline int kc_of(int C) { return (C + BKT - 1) / BKT; }
-
-// ---- parameter builders shared by the entry points and their workspace queries ----
-static void conv_fwd_params(const BgConvDesc* d, NNParams& p) {
-    memset(&p, 0, sizeof(p));
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->H; g.Ws = d->W; g.Ho = d->Ho; g.Wo = d->Wo; g.Hq = d->Ho; g.Wq = d->Wo; g.pstep = 1;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = d->pad_mode == BG_PAD_REFLECT; g.ld = d->Cin;
-    p.C = d->Cin; p.M = d->N * d->Ho * d->Wo; p.N = d->Cout;
-    p.tap_stride = (int64_t)d->Cin * d->Cout; p.ldk = d->Cout; p.ldn = 1;
-    p.out_ld = d->Cout; p.batch = 1;
-}
-
-static void conv_dgrad_params(const BgConvDesc* d, NNParams& p) {
-    memset(&p, 0, sizeof(p));
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->Ho; g.Ws = d->Wo; g.Ho = d->H; g.Wo = d->W;
-    g.pstep = d->stride; g.Hq = d->H / d->stride; g.Wq = d->W / d->stride;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo;
-    g.reflect = (d->pad_mode == BG_PAD_REFLECT) && d->pad_lo > 0; g.ld = d->Cout;
-    p.C = d->Cout; p.M = d->N * g.Hq * g.Wq; p.N = d->Cin;
-    p.tap_stride = (int64_t)d->Cin * d->Cout; p.ldk = 1; p.ldn = d->Cout;   // B[c=co][n=ci] = w[tap][ci][co]
-    p.out_ld = d->Cin; p.batch = 1;
-}
-
-static void deconv_fwd_params(const BgConvDesc* d, NNParams& p) {
-    memset(&p, 0, sizeof(p));
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->H; g.Ws = d->W; g.Ho = d->Ho; g.Wo = d->Wo;
-    g.pstep = d->stride; g.Hq = d->Ho / d->stride; g.Wq = d->Wo / d->stride;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = 0; g.ld = d->Cin;
-    p.C = d->Cin; p.M = d->N * g.Hq * g.Wq; p.N = d->Cout;
-    p.tap_stride = (int64_t)d->Cin * d->Cout; p.ldk = 1; p.ldn = d->Cin;    // B[c=ci][n=co] = w[tap][co][ci]
-    p.out_ld = d->Cout; p.batch = 1;
-}
-
-static void deconv_dgrad_params(const BgConvDesc* d, NNParams& p) {
-    memset(&p, 0, sizeof(p));
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->Ho; g.Ws = d->Wo; g.Ho = d->H; g.Wo = d->W; g.Hq = d->H; g.Wq = d->W; g.pstep = 1;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = 0; g.ld = d->Cout;
-    p.C = d->Cout; p.M = d->N * d->H * d->W; p.N = d->Cin;
-    p.tap_stride = (int64_t)d->Cin * d->Cout; p.ldk = d->Cin; p.ldn = 1;    // B[c=co][n=ci] = w[tap][co][ci]
-    p.out_ld = d->Cin; p.batch = 1;
-}
-
-// fewest K iterations over the phases of a transposed gather (k3 s2 has 1x1 .. 2x2 taps per phase)
-static int tconv_min_iters(const BgConvDesc* d, int C) {
-    int per_axis = d->stride == 1 ? d->k : d->k / d->stride;   // smallest tap count of a phase
-    if (per_axis < 1) per_axis = 1;
-    return per_axis * per_axis * kc_of(C);
-}
-
-// ---- bf16-resident path (igemm16.hip): parameter builders -------------------------------------------
+// ---- route predicates: each is evaluated in exactly one plan function below ----
 static bool resident_fwd(const BgConvDesc* d) { return d->x_dtype == BG_BF16; }
 static bool resident_dgrad(const BgConvDesc* d) { return d->y_dtype == BG_BF16 && d->w_packed; }
 static bool resident_wgrad(const BgConvDesc* d) { return d->x_dtype == BG_BF16 && d->y_dtype == BG_BF16; }
-
-static void nn16_from(const NNParams& q, NN16Params& p) {
-    memset(&p, 0, sizeof(p));
-    p.g = q.g;
-    p.C = q.C; p.M = q.M; p.N = q.N;
-    p.tap_stride = (int64_t)q.N * q.C;
-    p.out_ld = q.out_ld;
-}
-
-// extent of the padded grid the gradient of a reflect-padded conv is computed on (a multiple of the stride)
-static int padded_extent(int out, int k, int stride) {
-    const int used = (out - 1) * stride + k;
-    return (used + stride - 1) / stride * stride;
-}
-
-static void conv16_dgrad_params(const BgConvDesc* d, bool padded, NN16Params& p) {
-    NNParams q;
-    conv_dgrad_params(d, q);
-    nn16_from(q, p);
-    if (padded) {
-        Gather& g = p.g;
-        g.Ho = padded_extent(d->Ho, d->k, d->stride);
-        g.Wo = padded_extent(d->Wo, d->k, d->stride);
-        g.Hq = g.Ho / d->stride;
-        g.Wq = g.Wo / d->stride;
-        g.pad = 0;
-        g.reflect = 0;
-        p.M = d->N * g.Hq * g.Wq;
-    }
-}
-
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // Reflect padding on the HIGH side only: the k = 2 convolution of subpixel_conv (ops.py:23-27: pad 0.5 -> 0 low, 1 high).
 // The mirrored-source forms of the input gradient (the fp32 MIRROR kernels, the ring launches) assume low = high, so this
@@ -1063,17 +1014,6 @@ static bool conv_dgrad_double_mirror(const BgConvDesc* d) {
 }
 static bool conv_dgrad_fold32(const BgConvDesc* d) { return reflect_hi_only(d) || conv_dgrad_double_mirror(d); }
 
-// fp32-tensor launch of the input gradient on the padded grid of a conv_dgrad_fold32 geometry (stride phases as on the
-// map: the extent is a multiple of the stride)
-static void conv_dgrad_padded_params(const BgConvDesc* d, NNParams& p) {
-    conv_dgrad_params(d, p);
-    Gather& g = p.g;
-    g.Ho = padded_extent(d->Ho, d->k, d->stride);
-    g.Wo = padded_extent(d->Wo, d->k, d->stride);
-    g.Hq = g.Ho / d->stride; g.Wq = g.Wo / d->stride; g.pad = 0; g.reflect = 0;
-    p.M = d->N * g.Hq * g.Wq;
-}
-
 // Input gradient of a reflect-padded 3 x 3 convolution WITHOUT the padded grid (ops.py:81-82, 94 under autodiff): the
 // plain transposed gather on the H x W map (zero-padding semantics: halo-tile kernel on 16 / 32 / 64 maps, position-major
 // tap kernel on 4 x 4 / 8 x 8) plus two thin launches that add the taps of the mirrored padded rows / columns into
@@ -1093,23 +1033,293 @@ static bool dgrad_ring_ok(const BgConvDesc* d) {
            d->Wo == d->W / d->stride;
 }
 
+// ---- plans ----
+// The gather of a pass.  from_x: the source is x and the rows enumerate y's grid (forward passes, conv wgrad), else the
+// source is dy and the rows enumerate x's grid.  phases: a transposed gather (conv dgrad, deconv fwd), one launch row
+// range per stride phase of the output grid.
+static Gather pass_gather(const BgConvDesc* d, bool from_x, bool phases, bool reflect) {
+    Gather g{};
+    g.Nb = d->N;
+    if (from_x) { g.Hs = d->H; g.Ws = d->W; g.Ho = d->Ho; g.Wo = d->Wo; g.ld = d->Cin; }
+    else { g.Hs = d->Ho; g.Ws = d->Wo; g.Ho = d->H; g.Wo = d->W; g.ld = d->Cout; }
+    g.pstep = phases ? d->stride : 1;
+    g.Hq = g.Ho / g.pstep; g.Wq = g.Wo / g.pstep;
+    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = reflect;
+    return g;
+}
+
+static void nn16_from(const NNParams& q, NN16Params& p) {
+    p.g = q.g;
+    p.C = q.C; p.M = q.M; p.N = q.N;
+    p.tap_stride = (int64_t)q.N * q.C;
+    p.out_ld = q.out_ld;
+}
+
+// fewest K iterations over the phases of a transposed gather (k3 s2 has 1x1 .. 2x2 taps per phase)
+static int tconv_min_iters(const BgConvDesc* d, int C) {
+    int per_axis = d->stride == 1 ? d->k : d->k / d->stride;   // smallest tap count of a phase
+    if (per_axis < 1) per_axis = 1;
+    return per_axis * per_axis * kc_of(C);
+}
+
+// The four NN passes before any routing: the fp32 parameter block, the kernel form and the planner inputs.
+// Weights are [tap][Cin][Cout] for a conv and [tap][Cout][Cin] for a deconv; a transposed gather reads them as
+// B[c][n] = w[tap][n][c] (bt).
+static ConvPlan plan_nn_pass(const BgConvDesc* d, bool deconv, bool grad) {
+    ConvPlan pl{};
+    const bool phases = deconv != grad;
+    const bool reflect = !deconv && d->pad_mode == BG_PAD_REFLECT && (!grad || d->pad_lo > 0);
+    NNParams& p = pl.nn;
+    p.g = pass_gather(d, !grad, phases, reflect);
+    p.C = p.g.ld; p.N = grad ? d->Cin : d->Cout; p.M = d->N * p.g.Hq * p.g.Wq;
+    p.tap_stride = (int64_t)d->Cin * d->Cout;
+    if (phases) { p.ldk = 1; p.ldn = p.C; } else { p.ldk = p.N; p.ldn = 1; }
+    p.out_ld = p.N; p.batch = 1;
+    pl.route = F32_TAP;
+    pl.mode = phases ? GATHER_TCONV : GATHER_CONV;
+    pl.bt = phases;
+    pl.dense = true;
+    pl.zdim = phases ? d->stride * d->stride : 1;
+    pl.niter_min = phases ? tconv_min_iters(d, p.C) : d->k * d->k * kc_of(p.C);
+    pl.out_elems = (int64_t)d->N * p.g.Ho * p.g.Wo * p.N;
+    return pl;
+}
+
+// the bf16-resident form of pl.nn; out_f32 from the dtype of the tensor the pass writes
+static void plan_resident(ConvPlan& pl, Route route, int out_dtype) {
+    pl.route = route;
+    nn16_from(pl.nn, pl.nn16);
+    pl.nn16.out_f32 = out_dtype == BG_F32;
+}
+
+// extent of the padded grid the gradient of a reflect-padded conv is computed on (a multiple of the stride)
+static int padded_extent(int out, int k, int stride) {
+    const int used = (out - 1) * stride + k;
+    return (used + stride - 1) / stride * stride;
+}
+
+// Move an input-gradient launch onto the reflect-padded grid (plain transposed gather, stride phases as on the map: the
+// extent is a multiple of the stride); launch_reflect_fold then adds every padded position to the pixel it mirrors.
+static void plan_padded_grid(const BgConvDesc* d, ConvPlan& pl, size_t elem_bytes) {
+    Gather& g = pl.nn.g;
+    g.Ho = padded_extent(d->Ho, d->k, d->stride);
+    g.Wo = padded_extent(d->Wo, d->k, d->stride);
+    g.Hq = g.Ho / d->stride; g.Wq = g.Wo / d->stride; g.pad = 0; g.reflect = 0;
+    pl.nn.M = d->N * g.Hq * g.Wq;
+    pl.out_elems = (int64_t)d->N * g.Ho * g.Wo * d->Cin;
+    pl.grid_bytes = align256((size_t)pl.out_elems * elem_bytes);
+}
+
+// d2s_block = 2 (bg_conv2d_fwd_d2s): the same launch with the depth-to-space store (NN16Params::d2s_c) where d describes
+// one; d2s_c stays 0 where it does not.  Whether the kernel form the launch takes has that store is nn16_d2s_ok's answer.
+static ConvPlan plan_conv_fwd(const BgConvDesc* d, int d2s_block = 0) {
+    ConvPlan pl = plan_nn_pass(d, false, false);
+    if (!resident_fwd(d)) return pl;
+    plan_resident(pl, BF16_PLAIN, d->y_dtype);
+    if (d2s_block == 2 && d->w_packed && d->stride == 1 && d->Ho == d->H && d->Wo == d->W && d->Cout % 32 == 0 &&
+        d->Cin % 8 == 0)
+        pl.nn16.d2s_c = d->Cout / 4;
+    return pl;
+}
+
+static ConvPlan plan_conv_dgrad(const BgConvDesc* d) {
+    ConvPlan pl = plan_nn_pass(d, false, true);
+    const bool mirrored = pl.nn.g.reflect != 0;         // reflect padding with pad_lo > 0
+    if (resident_dgrad(d)) {
+        const bool ring = mirrored && dgrad_ring_ok(d);
+        const bool padded = (mirrored && !ring) || reflect_hi_only(d);
+        pl.nn.g.reflect = 0;                            // (the mirrored taps are the ring launches' / the fold's business)
+        if (padded) plan_padded_grid(d, pl, d->x_dtype == BG_F32 ? 4 : 2);
+        plan_resident(pl, padded ? BF16_PADDED_FOLD : (ring ? BF16_RING : BF16_PLAIN), d->x_dtype);
+        // 8-channel image layers, stride 2: one 2 x 2-window launch (igemm16.hip) in place of the tap / halo-tile one
+        if (!padded && nn16h_d2s_ok(pl.nn16)) pl.route = ring ? BF16_THIN_D2S_RING : BF16_THIN_D2S;
+        return pl;
+    }
+    // The ONE pass that plans for uneven phases.  The fp32 transposed-conv forward has the same uneven k3 s2 phases and
+    // does not pass true: that is how round 1 measured both (512 -> 1024 8 x 8 dgrad 50 -> 79 TF/s with the larger grid,
+    // the forward as it is), not an oversight to fix in passing.  The bf16-resident planner (plan_nn16) has no such input.
+    pl.uneven = d->stride > 1 && d->k % d->stride != 0;
+    if (conv_dgrad_fold32(d)) {
+        pl.route = F32_PADDED_FOLD;
+        plan_padded_grid(d, pl, sizeof(float));
+    } else if (mirrored) {
+        pl.route = F32_MIRROR;
+        pl.mirror = true;
+    }
+    return pl;
+}
+
+static ConvPlan plan_deconv_fwd(const BgConvDesc* d) {
+    ConvPlan pl = plan_nn_pass(d, true, false);
+    if (resident_fwd(d)) plan_resident(pl, BF16_PLAIN, d->y_dtype);
+    return pl;
+}
+
+static ConvPlan plan_deconv_dgrad(const BgConvDesc* d) {
+    ConvPlan pl = plan_nn_pass(d, true, true);
+    if (resident_dgrad(d)) plan_resident(pl, BF16_PLAIN, d->x_dtype);
+    return pl;
+}
+
+// Weight gradients: the gather of the conv forward (source x, rows over y) resp. of the deconv input gradient (source dy,
+// rows over x) as operand A, the other tensor as Bv.
+//   deconv: dw[kh,kw,co,ci] = sum_{b,hi,wi} dy[b, hi*s+kh-pad, wi*s+kw-pad, co] * x[b,hi,wi,ci]
+static ConvPlan plan_wgrad(const BgConvDesc* d, bool deconv) {
+    ConvPlan pl{};
+    pl.mode = GATHER_CONV;
+    const Gather g = pass_gather(d, !deconv, false, !deconv && d->pad_mode == BG_PAD_REFLECT);
+    auto fill = [&](auto& p) {
+        p.g = g;
+        p.Ca = g.ld; p.Cb = deconv ? d->Cin : d->Cout; p.Mf = d->k * d->k * p.Ca; p.b_ld = p.Cb; p.M = d->N * g.Ho * g.Wo;
+        p.out_ld = p.Cb;
+    };
+    if (resident_wgrad(d)) {
+        pl.route = TN_BF16;
+        fill(pl.tn16);
+    } else {
+        pl.route = TN_F32;
+        fill(pl.tn);
+        pl.tn.batch = 1;
+    }
+    return pl;
+}
+static ConvPlan plan_conv_wgrad(const BgConvDesc* d) { return plan_wgrad(d, false); }
+static ConvPlan plan_deconv_wgrad(const BgConvDesc* d) { return plan_wgrad(d, true); }
+
+static ConvPlan plan_gemm(const BgGemmDesc* d) {
+    ConvPlan pl{};
+    pl.mode = GATHER_PLAIN;
+    const int batch = d->batch > 0 ? d->batch : 1;
+    Gather g{};
+    g.Nb = d->transA ? d->K : d->M; g.Hs = 1; g.Ws = 1; g.Ho = 1; g.Wo = 1; g.Hq = 1; g.Wq = 1; g.pstep = 1;
+    g.k = 1; g.stride = 1; g.ld = d->lda;
+    if (d->transA) {
+        pl.route = TN_F32;
+        TNParams& p = pl.tn;
+        p.g = g;
+        p.Ca = d->M; p.Cb = d->N; p.Mf = d->M; p.b_ld = d->ldb; p.M = d->K;
+        p.out_ld = d->ldc; p.batch = batch;
+        p.strideA = d->strideA; p.strideB = d->strideB; p.strideC = d->strideC;
+        return pl;
+    }
+    pl.route = F32_TAP;
+    NNParams& p = pl.nn;
+    p.g = g;
+    p.C = d->K; p.M = d->M; p.N = d->N;
+    if (d->transB) { p.ldk = 1; p.ldn = d->ldb; } else { p.ldk = d->ldb; p.ldn = 1; }
+    p.out_ld = d->ldc; p.batch = batch;
+    p.strideA = d->strideA; p.strideB = d->strideB; p.strideC = d->strideC;
+    pl.bt = d->transB != 0;
+    pl.dense = d->ldc == d->N && batch == 1;
+    pl.zdim = batch;
+    pl.niter_min = kc_of(d->K);
+    pl.out_elems = (int64_t)d->M * d->N;
+    return pl;
+}
+
+// Gram matrix of a bf16 row-major matrix: out[c1][c2] = sum_r a[r][c1] a[r][c2] (fp32), the ortho-cosine regulariser's
+// W^T W (utils.py:198) taken from the packed bf16 copy of w / sigma that the spectral-norm pass already wrote: the
+// pixel-reduction kernel in PLAIN mode with both operands the same matrix.
+static ConvPlan plan_gram16(int rows, int cols, int ld) {
+    ConvPlan pl{};
+    pl.route = TN_BF16;
+    pl.mode = GATHER_PLAIN;
+    TN16Params& p = pl.tn16;
+    p.g.ld = ld; p.b_ld = ld;
+    p.Ca = cols; p.Cb = cols; p.Mf = cols; p.M = rows; p.out_ld = cols;
+    return pl;
+}
+
+static size_t plan_workspace_bytes(const ConvPlan& pl) {
+    if (pl.route == TN_F32) return tn_workspace_bytes(pl.tn.Mf, pl.tn.Cb, pl.tn.batch, pl.tn.M);
+    if (pl.route == TN_BF16) return tn16_workspace_bytes(pl.tn16);
+    const size_t slabs = route_f32(pl.route) ? nn_workspace_bytes(pl)
+                                             : nn16_workspace_bytes(pl.nn16, pl.mode, pl.zdim, pl.out_elems);
+    return pl.grid_bytes ? align256(slabs) + pl.grid_bytes : slabs;
+}
+
+// bytes of the partial batch-norm sums a deconv forward with fused statistics writes (0: no such launch)
+static size_t plan_stats_bytes(const BgConvDesc* d, const ConvPlan& pl) {
+    if (pl.route != BF16_PLAIN || d->y_dtype != BG_BF16) return 0;
+    return (size_t)nn16_stats_rows(pl.nn16, pl.mode, pl.zdim) * 2 * (size_t)d->Cout * sizeof(float);
+}
+
+// ---- running a plan ----
+// The NN passes: bind the tensors, run the route.  src / out are x / y of a forward pass and dy / dx of an input gradient.
+static int run_nn(ConvPlan& pl, const BgConvDesc* d, const char* op, bool deconv, const void* src, const void* w,
+                  const float* bias, const float* alpha_dev, void* out, int accumulate, void* ws, size_t ws_bytes,
+                  void* stream) {
+    hipStream_t s = as_stream(stream);
+    Tag tag(op, d);
+    // *_PADDED_FOLD: the gradient on the reflect-padded grid goes to the head of the workspace (split-K slabs behind it),
+    // then every padded position is added to the pixel it mirrors
+    void* const grid = ws;
+    void* target = out;
+    int acc = accumulate;
+    if (pl.grid_bytes) {
+        BG_REQUIRE(ws && ws_bytes >= pl.grid_bytes, "bg_conv2d_dgrad: workspace too small for the padded gradient");
+        target = ws; acc = 0;
+        ws = ws_bytes > pl.grid_bytes ? reinterpret_cast<char*>(ws) + pl.grid_bytes : nullptr;
+        ws_bytes -= pl.grid_bytes;
+    }
+    ProfScope prof(s, conv_flops(d, deconv), tag.s, tag.bytes);
+    int rc;
+    if (route_f32(pl.route)) {
+        NNParams& p = pl.nn;
+        p.A = (const float*)src; p.B = (const float*)w; p.bias = bias; p.alpha = alpha_dev; p.out = (float*)target;
+        p.accumulate = acc;
+        const bool vec = (p.C % 4 == 0) && (pl.bt || p.N % 4 == 0) && aligned16(src) && aligned16(w);
+        rc = launch_nn(pl, vec, ws, ws_bytes, s, d->compute == BG_COMPUTE_BF16);
+    } else {
+        NN16Params& r = pl.nn16;
+        r.A = src; r.B = w; r.bias = bias; r.alpha = alpha_dev; r.out = target; r.accumulate = acc;
+        NN16Params q = r;                       // (the launch fills in its tiling: the ring launch starts from the plain block)
+        if (pl.route == BF16_THIN_D2S || pl.route == BF16_THIN_D2S_RING)
+            rc = launch_nn16h_d2s(r, s);
+        else
+            rc = launch_nn16(r, pl.mode, pl.zdim, pl.out_elems, ws, ws_bytes, s);
+        if (!rc && route_ring(pl.route)) {
+            q.ring = 1;
+            q.ring_lines = d->stride == 1 ? 2 : 1;
+            q.accumulate = 1;
+            rc = launch_nn16_ring(q, s);
+        }
+    }
+    if (rc || !pl.grid_bytes) return rc;
+    return launch_reflect_fold(grid, out, route_f32(pl.route) ? 1 : pl.nn16.out_f32, d->N, d->H, d->W, d->Cin, pl.nn.g.Ho,
+                               pl.nn.g.Wo, d->pad_lo, accumulate, s);
+}
+
+// The weight gradients: a is the gathered tensor (x of a conv, dy of a deconv), b the other one.
+static int run_tn(ConvPlan& pl, const BgConvDesc* d, const char* op, bool deconv, const void* a, const void* b, float* dw,
+                  void* ws, size_t ws_bytes, void* stream) {
+    Tag tag(op, d);
+    ProfScope prof(as_stream(stream), conv_flops(d, deconv), tag.s, tag.bytes);
+    if (pl.route == TN_BF16) {
+        pl.tn16.A = a; pl.tn16.Bv = b;
+        return launch_tn16(pl.tn16, pl.mode, dw, ws, ws_bytes, as_stream(stream));
+    }
+    pl.tn.A = (const float*)a; pl.tn.Bv = (const float*)b;
+    const bool vec = (d->Cin % 4 == 0) && (d->Cout % 4 == 0) && aligned16(a) && aligned16(b);
+    return launch_tn(pl.tn, pl.mode, vec, dw, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
+}
+
 }  // namespace bg
 
 using namespace bg;
 
 extern "C" {
 
-size_t bg_conv2d_fwd_workspace_bytes(const BgConvDesc* d) {
-    if (!d) return 0;
-    if (resident_fwd(d)) {
-        NNParams q;
-        conv_fwd_params(d, q);
-        NN16Params p;
-        nn16_from(q, p);
-        return nn16_workspace_bytes(p, GATHER_CONV, 1, (int64_t)p.M * d->Cout);
-    }
-    return nn_workspace_bytes((int64_t)d->N * d->Ho * d->Wo, d->Cout, 1, d->k * d->k * kc_of(d->Cin),
-                              (int64_t)d->N * d->Ho * d->Wo * d->Cout);
+size_t bg_conv2d_fwd_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_conv_fwd(d)) : 0; }
+size_t bg_conv2d_dgrad_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_conv_dgrad(d)) : 0; }
+size_t bg_conv2d_wgrad_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_conv_wgrad(d)) : 0; }
+size_t bg_deconv2d_fwd_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_deconv_fwd(d)) : 0; }
+size_t bg_deconv2d_dgrad_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_deconv_dgrad(d)) : 0; }
+size_t bg_deconv2d_wgrad_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_deconv_wgrad(d)) : 0; }
+size_t bg_deconv2d_fwd_stats_workspace_bytes(const BgConvDesc* d) { return d ? plan_stats_bytes(d, plan_deconv_fwd(d)) : 0; }
+size_t bg_gemm_workspace_bytes(const BgGemmDesc* d) { return d ? plan_workspace_bytes(plan_gemm(d)) : 0; }
+size_t bg_gram16_workspace_bytes(int rows, int cols) {
+    return rows > 0 && cols > 0 ? plan_workspace_bytes(plan_gram16(rows, cols, cols)) : 0;
 }
 
 int bg_conv2d_fwd(const BgConvDesc* d, const void* x, const void* w, const float* bias, const float* alpha_dev,
@@ -1117,43 +1327,19 @@ int bg_conv2d_fwd(const BgConvDesc* d, const void* x, const void* w, const float
     int rc = check_conv(d);
     if (rc) return rc;
     BG_REQUIRE(x && w && y, "bg_conv2d_fwd: null tensor pointer");
-    Tag tag("conv2d_fwd", d);
-    NNParams p;
-    conv_fwd_params(d, p);
-    if (resident_fwd(d)) {
+    ConvPlan pl = plan_conv_fwd(d);
+    if (pl.route == BF16_PLAIN)
         BG_REQUIRE(d->w_packed, "bg_conv2d_fwd: bf16 input needs the packed bf16 weights (w_packed)");
-        NN16Params r;
-        nn16_from(p, r);
-        r.A = x; r.B = w; r.bias = bias; r.alpha = alpha_dev; r.out = y; r.accumulate = accumulate;
-        r.out_f32 = d->y_dtype == BG_F32;
-        ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-        return launch_nn16(r, GATHER_CONV, 1, (int64_t)r.M * d->Cout, ws, ws_bytes, as_stream(stream));
-    }
-    BG_REQUIRE(d->y_dtype == BG_F32 && !d->w_packed, "bg_conv2d_fwd: fp32 input needs fp32 weights and output");
-    p.A = (const float*)x; p.B = (const float*)w; p.bias = bias; p.alpha = alpha_dev; p.out = (float*)y;
-    p.accumulate = accumulate;
-    const bool vec = (d->Cin % 4 == 0) && (d->Cout % 4 == 0) && aligned16(x) && aligned16(w);
-    ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-    return launch_nn(p, GATHER_CONV, false, false, vec, 1, d->k * d->k * kc_of(d->Cin),
-                     (int64_t)p.M * d->Cout, true, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
-}
-
-// the forward launch of d with the depth-to-space store (NN16Params::d2s_c), or false when d / block do not describe one
-static bool conv16_d2s_params(const BgConvDesc* d, int block, NN16Params& r) {
-    if (!d || block != 2 || !resident_fwd(d) || !d->w_packed || d->stride != 1 || d->Ho != d->H || d->Wo != d->W ||
-        d->Cout % 32 || d->Cin % 8)
-        return false;
-    NNParams p;
-    conv_fwd_params(d, p);
-    nn16_from(p, r);
-    r.d2s_c = d->Cout / 4;
-    return true;
+    else
+        BG_REQUIRE(d->y_dtype == BG_F32 && !d->w_packed, "bg_conv2d_fwd: fp32 input needs fp32 weights and output");
+    return run_nn(pl, d, "conv2d_fwd", false, x, w, bias, alpha_dev, y, accumulate, ws, ws_bytes, stream);
 }
 
 int bg_conv2d_fwd_d2s_supported(const BgConvDesc* d, int block) {
-    NN16Params r;
-    if (!conv16_d2s_params(d, block, r) || check_conv(d) != BG_OK) return 0;
-    return nn16_d2s_ok(r, GATHER_CONV, 1) ? 1 : 0;
+    if (!d) return 0;
+    const ConvPlan pl = plan_conv_fwd(d, block);
+    if (!pl.nn16.d2s_c || check_conv(d) != BG_OK) return 0;
+    return nn16_d2s_ok(pl.nn16, pl.mode, pl.zdim) ? 1 : 0;
 }
 
 int bg_conv2d_fwd_d2s(const BgConvDesc* d, const void* x, const void* w, const float* bias, const float* alpha_dev,
@@ -1161,40 +1347,11 @@ int bg_conv2d_fwd_d2s(const BgConvDesc* d, const void* x, const void* w, const f
     int rc = check_conv(d);
     if (rc) return rc;
     BG_REQUIRE(x && w && y, "bg_conv2d_fwd_d2s: null tensor pointer");
-    NN16Params r;
-    BG_REQUIRE(conv16_d2s_params(d, block, r) && nn16_d2s_ok(r, GATHER_CONV, 1),
+    ConvPlan pl = plan_conv_fwd(d, block);
+    BG_REQUIRE(pl.nn16.d2s_c && nn16_d2s_ok(pl.nn16, pl.mode, pl.zdim),
                "bg_conv2d_fwd_d2s: this launch has no fused depth-to-space store (query bg_conv2d_fwd_d2s_supported)");
     (void)ws; (void)ws_bytes;                  // supported launches never split K
-    Tag tag("conv2d_fwd_d2s", d);
-    r.A = x; r.B = w; r.bias = bias; r.alpha = alpha_dev; r.out = y; r.accumulate = 0;
-    r.out_f32 = d->y_dtype == BG_F32;
-    ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-    return launch_nn16(r, GATHER_CONV, 1, (int64_t)r.M * d->Cout, nullptr, 0, as_stream(stream));
-}
-
-size_t bg_conv2d_dgrad_workspace_bytes(const BgConvDesc* d) {
-    if (!d) return 0;
-    const int z = d->stride * d->stride;
-    if (resident_dgrad(d)) {
-        const bool padded = (d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && !dgrad_ring_ok(d)) || reflect_hi_only(d);
-        NN16Params p;
-        conv16_dgrad_params(d, padded, p);
-        p.g.reflect = 0;
-        const int64_t out_elems = (int64_t)d->N * p.g.Ho * p.g.Wo * d->Cin;
-        size_t b = nn16_workspace_bytes(p, GATHER_TCONV, z, out_elems);
-        if (padded) b = align256(b) + align256((size_t)out_elems * (d->x_dtype == BG_F32 ? 4 : 2));
-        return b;
-    }
-    UnevenPhases uneven(d);
-    if (conv_dgrad_fold32(d)) {
-        NNParams p;
-        conv_dgrad_padded_params(d, p);
-        const int64_t out_elems = (int64_t)d->N * p.g.Ho * p.g.Wo * d->Cin;
-        return align256(nn_workspace_bytes(p.M, d->Cin, z, tconv_min_iters(d, d->Cout), out_elems)) +
-               align256((size_t)out_elems * sizeof(float));
-    }
-    return nn_workspace_bytes((int64_t)d->N * (d->H / d->stride) * (d->W / d->stride), d->Cin, z,
-                              tconv_min_iters(d, d->Cout), (int64_t)d->N * d->H * d->W * d->Cin);
+    return run_nn(pl, d, "conv2d_fwd_d2s", false, x, w, bias, alpha_dev, y, 0, nullptr, 0, stream);
 }
 
 int bg_conv2d_dgrad(const BgConvDesc* d, const void* dy, const void* w, const float* alpha_dev, void* dx,
@@ -1203,89 +1360,10 @@ int bg_conv2d_dgrad(const BgConvDesc* d, const void* dy, const void* w, const fl
     if (rc) return rc;
     BG_REQUIRE(dy && w && dx, "bg_conv2d_dgrad: null tensor pointer");
     BG_REQUIRE(d->H % d->stride == 0 && d->W % d->stride == 0, "conv dgrad: H,W must be multiples of stride");
-    Tag tag("conv2d_dgrad", d);
-    if (resident_dgrad(d)) {
-        const bool ring = d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && dgrad_ring_ok(d);
-        const bool padded = (d->pad_mode == BG_PAD_REFLECT && d->pad_lo > 0 && !ring) || reflect_hi_only(d);
-        NN16Params r;
-        conv16_dgrad_params(d, padded, r);
-        r.g.reflect = 0;                        // (the mirrored taps are the ring launches' / the fold's business)
-        r.A = dy; r.B = w; r.alpha = alpha_dev;
-        r.out_f32 = d->x_dtype == BG_F32;
-        const int64_t out_elems = (int64_t)d->N * r.g.Ho * r.g.Wo * d->Cin;
-        ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-        if (!padded) {
-            r.out = dx; r.accumulate = accumulate;
-            const NN16Params plain = r;
-            if (nn16h_d2s_ok(plain))            // 8-channel image layers, stride 2: one 2 x 2-window launch (igemm16.hip)
-                rc = launch_nn16h_d2s(plain, as_stream(stream));
-            else
-                rc = launch_nn16(r, GATHER_TCONV, d->stride * d->stride, out_elems, ws, ws_bytes, as_stream(stream));
-            if (rc || !ring) return rc;
-            NN16Params q = plain;
-            q.ring = 1;
-            q.ring_lines = d->stride == 1 ? 2 : 1;
-            q.accumulate = 1;
-            return launch_nn16_ring(q, as_stream(stream));
-        }
-        // gradient on the reflect-padded grid, then every padded position is added to the pixel it mirrors
-        const size_t pbytes = align256((size_t)out_elems * (r.out_f32 ? 4 : 2));
-        BG_REQUIRE(ws && ws_bytes >= pbytes, "bg_conv2d_dgrad: workspace too small for the padded gradient");
-        r.out = ws; r.accumulate = 0;
-        char* slabs = reinterpret_cast<char*>(ws) + pbytes;
-        rc = launch_nn16(r, GATHER_TCONV, d->stride * d->stride, out_elems, ws_bytes > pbytes ? slabs : nullptr,
-                         ws_bytes - pbytes, as_stream(stream));
-        if (rc) return rc;
-        return launch_reflect_fold(ws, dx, r.out_f32, d->N, d->H, d->W, d->Cin, r.g.Ho, r.g.Wo, d->pad_lo, accumulate,
-                                   as_stream(stream));
-    }
-    BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32 && !d->w_packed, "bg_conv2d_dgrad: unsupported dtype mix");
-    UnevenPhases uneven(d);
-    if (conv_dgrad_fold32(d)) {
-        // gradient on the reflect-padded grid (plain transposed gather, stride phases), then the fold
-        NNParams p;
-        conv_dgrad_padded_params(d, p);
-        const int64_t out_elems = (int64_t)d->N * p.g.Ho * p.g.Wo * d->Cin;
-        const size_t pbytes = align256((size_t)out_elems * sizeof(float));
-        BG_REQUIRE(ws && ws_bytes >= pbytes, "bg_conv2d_dgrad: workspace too small for the padded gradient");
-        p.A = (const float*)dy; p.B = (const float*)w; p.alpha = alpha_dev; p.out = (float*)ws; p.accumulate = 0;
-        const bool vec = (d->Cout % 4 == 0) && aligned16(dy) && aligned16(w);
-        char* slabs = reinterpret_cast<char*>(ws) + pbytes;
-        ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-        rc = launch_nn(p, GATHER_TCONV, true, false, vec, d->stride * d->stride, tconv_min_iters(d, d->Cout), out_elems,
-                       true, ws_bytes > pbytes ? slabs : nullptr, ws_bytes - pbytes, as_stream(stream),
-                       d->compute == BG_COMPUTE_BF16);
-        if (rc) return rc;
-        return launch_reflect_fold(ws, dx, 1, d->N, d->H, d->W, d->Cin, p.g.Ho, p.g.Wo, d->pad_lo, accumulate,
-                                   as_stream(stream));
-    }
-    NNParams p;
-    conv_dgrad_params(d, p);
-    p.A = (const float*)dy; p.B = (const float*)w; p.alpha = alpha_dev; p.out = (float*)dx; p.accumulate = accumulate;
-    const bool vec = (d->Cout % 4 == 0) && aligned16(dy) && aligned16(w);
-    ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-    return launch_nn(p, GATHER_TCONV, true, p.g.reflect != 0, vec, d->stride * d->stride, tconv_min_iters(d, d->Cout),
-                     (int64_t)d->N * d->H * d->W * d->Cin, true, ws, ws_bytes, as_stream(stream),
-                     d->compute == BG_COMPUTE_BF16);
-}
-
-static void conv16_wgrad_params(const BgConvDesc* d, TN16Params& p) {
-    memset(&p, 0, sizeof(p));
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->H; g.Ws = d->W; g.Ho = d->Ho; g.Wo = d->Wo; g.Hq = d->Ho; g.Wq = d->Wo; g.pstep = 1;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = d->pad_mode == BG_PAD_REFLECT; g.ld = d->Cin;
-    p.Ca = d->Cin; p.Cb = d->Cout; p.Mf = d->k * d->k * d->Cin; p.b_ld = d->Cout; p.M = d->N * d->Ho * d->Wo;
-    p.out_ld = d->Cout;
-}
-
-size_t bg_conv2d_wgrad_workspace_bytes(const BgConvDesc* d) {
-    if (!d) return 0;
-    if (resident_wgrad(d)) {
-        TN16Params p;
-        conv16_wgrad_params(d, p);
-        return tn16_workspace_bytes(p);
-    }
-    return tn_workspace_bytes(d->k * d->k * d->Cin, d->Cout, 1, d->N * d->Ho * d->Wo);
+    ConvPlan pl = plan_conv_dgrad(d);
+    if (route_f32(pl.route))
+        BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32 && !d->w_packed, "bg_conv2d_dgrad: unsupported dtype mix");
+    return run_nn(pl, d, "conv2d_dgrad", false, dy, w, nullptr, alpha_dev, dx, accumulate, ws, ws_bytes, stream);
 }
 
 int bg_conv2d_wgrad(const BgConvDesc* d, const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes,
@@ -1293,40 +1371,10 @@ int bg_conv2d_wgrad(const BgConvDesc* d, const void* x, const void* dy, float* d
     int rc = check_conv(d);
     if (rc) return rc;
     BG_REQUIRE(x && dy && dw, "bg_conv2d_wgrad: null tensor pointer");
-    Tag tag("conv2d_wgrad", d);
-    if (resident_wgrad(d)) {
-        TN16Params r;
-        conv16_wgrad_params(d, r);
-        r.A = x; r.Bv = dy;
-        ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-        return launch_tn16(r, GATHER_CONV, dw, ws, ws_bytes, as_stream(stream));
-    }
-    BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32, "bg_conv2d_wgrad: x and dy must both be fp32 or both bf16");
-    TNParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = (const float*)x; p.Bv = (const float*)dy;
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->H; g.Ws = d->W; g.Ho = d->Ho; g.Wo = d->Wo; g.Hq = d->Ho; g.Wq = d->Wo; g.pstep = 1;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = d->pad_mode == BG_PAD_REFLECT; g.ld = d->Cin;
-    p.Ca = d->Cin; p.Cb = d->Cout; p.Mf = d->k * d->k * d->Cin; p.b_ld = d->Cout; p.M = d->N * d->Ho * d->Wo;
-    p.out_ld = d->Cout; p.batch = 1;
-    const bool vec = (d->Cin % 4 == 0) && (d->Cout % 4 == 0) && aligned16(x) && aligned16(dy);
-    ProfScope prof(as_stream(stream), conv_flops(d, false), tag.s, tag.bytes);
-    return launch_tn(p, GATHER_CONV, vec, dw, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
-}
-
-size_t bg_deconv2d_fwd_workspace_bytes(const BgConvDesc* d) {
-    if (!d) return 0;
-    const int z = d->stride * d->stride;
-    if (resident_fwd(d)) {
-        NNParams q;
-        deconv_fwd_params(d, q);
-        NN16Params p;
-        nn16_from(q, p);
-        return nn16_workspace_bytes(p, GATHER_TCONV, z, (int64_t)d->N * d->Ho * d->Wo * d->Cout);
-    }
-    return nn_workspace_bytes((int64_t)d->N * d->H * d->W, d->Cout, z, tconv_min_iters(d, d->Cin),
-                              (int64_t)d->N * d->Ho * d->Wo * d->Cout);
+    ConvPlan pl = plan_conv_wgrad(d);
+    if (pl.route == TN_F32)
+        BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32, "bg_conv2d_wgrad: x and dy must both be fp32 or both bf16");
+    return run_tn(pl, d, "conv2d_wgrad", false, x, dy, dw, ws, ws_bytes, stream);
 }
 
 int bg_deconv2d_fwd(const BgConvDesc* d, const void* x, const void* w, const float* bias, const float* alpha_dev,
@@ -1334,36 +1382,12 @@ int bg_deconv2d_fwd(const BgConvDesc* d, const void* x, const void* w, const flo
     int rc = check_deconv(d);
     if (rc) return rc;
     BG_REQUIRE(x && w && y, "bg_deconv2d_fwd: null tensor pointer");
-    Tag tag("deconv2d_fwd", d);
-    NNParams p;
-    deconv_fwd_params(d, p);
-    if (resident_fwd(d)) {
+    ConvPlan pl = plan_deconv_fwd(d);
+    if (pl.route == BF16_PLAIN)
         BG_REQUIRE(d->w_packed, "bg_deconv2d_fwd: bf16 input needs the packed bf16 weights (w_packed)");
-        NN16Params r;
-        nn16_from(p, r);
-        r.A = x; r.B = w; r.bias = bias; r.alpha = alpha_dev; r.out = y; r.accumulate = accumulate;
-        r.out_f32 = d->y_dtype == BG_F32;
-        ProfScope prof(as_stream(stream), conv_flops(d, true), tag.s, tag.bytes);
-        return launch_nn16(r, GATHER_TCONV, d->stride * d->stride, (int64_t)d->N * d->Ho * d->Wo * d->Cout, ws, ws_bytes,
-                           as_stream(stream));
-    }
-    BG_REQUIRE(d->y_dtype == BG_F32 && !d->w_packed, "bg_deconv2d_fwd: fp32 input needs fp32 weights and output");
-    p.A = (const float*)x; p.B = (const float*)w; p.bias = bias; p.alpha = alpha_dev; p.out = (float*)y;
-    p.accumulate = accumulate;
-    const bool vec = (d->Cin % 4 == 0) && aligned16(x) && aligned16(w);
-    ProfScope prof(as_stream(stream), conv_flops(d, true), tag.s, tag.bytes);
-    return launch_nn(p, GATHER_TCONV, true, false, vec, d->stride * d->stride, tconv_min_iters(d, d->Cin),
-                     (int64_t)d->N * d->Ho * d->Wo * d->Cout, true, ws, ws_bytes, as_stream(stream),
-                     d->compute == BG_COMPUTE_BF16);
-}
-
-size_t bg_deconv2d_fwd_stats_workspace_bytes(const BgConvDesc* d) {
-    if (!d || !resident_fwd(d) || d->y_dtype != BG_BF16) return 0;
-    NNParams q;
-    deconv_fwd_params(d, q);
-    NN16Params p;
-    nn16_from(q, p);
-    return (size_t)nn16_stats_rows(p, GATHER_TCONV, d->stride * d->stride) * 2 * (size_t)d->Cout * sizeof(float);
+    else
+        BG_REQUIRE(d->y_dtype == BG_F32 && !d->w_packed, "bg_deconv2d_fwd: fp32 input needs fp32 weights and output");
+    return run_nn(pl, d, "deconv2d_fwd", true, x, w, bias, alpha_dev, y, accumulate, ws, ws_bytes, stream);
 }
 
 int bg_deconv2d_fwd_stats(const BgConvDesc* d, const void* x, const void* w, const float* bias, const float* alpha_dev,
@@ -1372,39 +1396,16 @@ int bg_deconv2d_fwd_stats(const BgConvDesc* d, const void* x, const void* w, con
     int rc = check_deconv(d);
     if (rc) return rc;
     BG_REQUIRE(x && w && y && sums && stats_ws, "bg_deconv2d_fwd_stats: null tensor pointer");
-    const size_t need = bg_deconv2d_fwd_stats_workspace_bytes(d);
+    ConvPlan pl = plan_deconv_fwd(d);
+    const size_t need = plan_stats_bytes(d, pl);
     BG_REQUIRE(need > 0 && d->w_packed, "bg_deconv2d_fwd_stats: this launch has no fused statistics (query the workspace)");
     BG_REQUIRE(stats_ws_bytes >= need && (reinterpret_cast<uintptr_t>(stats_ws) & 15) == 0,
                "bg_deconv2d_fwd_stats: statistics workspace too small");
-    Tag tag("deconv2d_fwd", d);
-    NNParams p;
-    deconv_fwd_params(d, p);
-    NN16Params r;
-    nn16_from(p, r);
-    r.A = x; r.B = w; r.bias = bias; r.alpha = alpha_dev; r.out = y; r.accumulate = accumulate;
-    r.out_f32 = 0;
-    r.stats_part = reinterpret_cast<float*>(stats_ws);
-    {
-        ProfScope prof(as_stream(stream), conv_flops(d, true), tag.s, tag.bytes);
-        rc = launch_nn16(r, GATHER_TCONV, d->stride * d->stride, (int64_t)d->N * d->Ho * d->Wo * d->Cout, ws, ws_bytes,
-                         as_stream(stream));
-        if (rc) return rc;
-    }
+    pl.nn16.stats_part = reinterpret_cast<float*>(stats_ws);
+    rc = run_nn(pl, d, "deconv2d_fwd", true, x, w, bias, alpha_dev, y, accumulate, ws, ws_bytes, stream);
+    if (rc) return rc;
     return launch_partial_colsum(reinterpret_cast<const float*>(stats_ws), sums, (int64_t)(need / (2 * (size_t)d->Cout * sizeof(float))),
                                  2 * d->Cout, as_stream(stream));
-}
-
-size_t bg_deconv2d_dgrad_workspace_bytes(const BgConvDesc* d) {
-    if (!d) return 0;
-    if (resident_dgrad(d)) {
-        NNParams q;
-        deconv_dgrad_params(d, q);
-        NN16Params p;
-        nn16_from(q, p);
-        return nn16_workspace_bytes(p, GATHER_CONV, 1, (int64_t)d->N * d->H * d->W * d->Cin);
-    }
-    return nn_workspace_bytes((int64_t)d->N * d->H * d->W, d->Cin, 1, d->k * d->k * kc_of(d->Cout),
-                              (int64_t)d->N * d->H * d->W * d->Cin);
 }
 
 int bg_deconv2d_dgrad(const BgConvDesc* d, const void* dy, const void* w, const float* alpha_dev, void* dx,
@@ -1412,42 +1413,10 @@ int bg_deconv2d_dgrad(const BgConvDesc* d, const void* dy, const void* w, const 
     int rc = check_deconv(d);
     if (rc) return rc;
     BG_REQUIRE(dy && w && dx, "bg_deconv2d_dgrad: null tensor pointer");
-    Tag tag("deconv2d_dgrad", d);
-    NNParams p;
-    deconv_dgrad_params(d, p);
-    if (resident_dgrad(d)) {
-        NN16Params r;
-        nn16_from(p, r);
-        r.A = dy; r.B = w; r.alpha = alpha_dev; r.out = dx; r.accumulate = accumulate;
-        r.out_f32 = d->x_dtype == BG_F32;
-        ProfScope prof(as_stream(stream), conv_flops(d, true), tag.s, tag.bytes);
-        return launch_nn16(r, GATHER_CONV, 1, (int64_t)r.M * d->Cin, ws, ws_bytes, as_stream(stream));
-    }
-    BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32 && !d->w_packed, "bg_deconv2d_dgrad: unsupported dtype mix");
-    p.A = (const float*)dy; p.B = (const float*)w; p.alpha = alpha_dev; p.out = (float*)dx; p.accumulate = accumulate;
-    const bool vec = (d->Cout % 4 == 0) && (d->Cin % 4 == 0) && aligned16(dy) && aligned16(w);
-    ProfScope prof(as_stream(stream), conv_flops(d, true), tag.s, tag.bytes);
-    return launch_nn(p, GATHER_CONV, false, false, vec, 1, d->k * d->k * kc_of(d->Cout),
-                     (int64_t)p.M * d->Cin, true, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
-}
-
-static void deconv16_wgrad_params(const BgConvDesc* d, TN16Params& p) {
-    memset(&p, 0, sizeof(p));
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->Ho; g.Ws = d->Wo; g.Ho = d->H; g.Wo = d->W; g.Hq = d->H; g.Wq = d->W; g.pstep = 1;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = 0; g.ld = d->Cout;
-    p.Ca = d->Cout; p.Cb = d->Cin; p.Mf = d->k * d->k * d->Cout; p.b_ld = d->Cin; p.M = d->N * d->H * d->W;
-    p.out_ld = d->Cin;
-}
-
-size_t bg_deconv2d_wgrad_workspace_bytes(const BgConvDesc* d) {
-    if (!d) return 0;
-    if (resident_wgrad(d)) {
-        TN16Params p;
-        deconv16_wgrad_params(d, p);
-        return tn16_workspace_bytes(p);
-    }
-    return tn_workspace_bytes(d->k * d->k * d->Cout, d->Cin, 1, d->N * d->H * d->W);
+    ConvPlan pl = plan_deconv_dgrad(d);
+    if (route_f32(pl.route))
+        BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32 && !d->w_packed, "bg_deconv2d_dgrad: unsupported dtype mix");
+    return run_nn(pl, d, "deconv2d_dgrad", true, dy, w, nullptr, alpha_dev, dx, accumulate, ws, ws_bytes, stream);
 }
 
 int bg_deconv2d_wgrad(const BgConvDesc* d, const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes,
@@ -1455,35 +1424,10 @@ int bg_deconv2d_wgrad(const BgConvDesc* d, const void* x, const void* dy, float*
     int rc = check_deconv(d);
     if (rc) return rc;
     BG_REQUIRE(x && dy && dw, "bg_deconv2d_wgrad: null tensor pointer");
-    Tag tag("deconv2d_wgrad", d);
-    // dw[kh,kw,co,ci] = sum_{b,hi,wi} dy[b, hi*s+kh-pad, wi*s+kw-pad, co] * x[b,hi,wi,ci]
-    if (resident_wgrad(d)) {
-        TN16Params r;
-        deconv16_wgrad_params(d, r);
-        r.A = dy; r.Bv = x;
-        ProfScope prof(as_stream(stream), conv_flops(d, true), tag.s, tag.bytes);
-        return launch_tn16(r, GATHER_CONV, dw, ws, ws_bytes, as_stream(stream));
-    }
-    BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32, "bg_deconv2d_wgrad: x and dy must both be fp32 or both bf16");
-    TNParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = (const float*)dy; p.Bv = (const float*)x;
-    Gather& g = p.g;
-    g.Nb = d->N; g.Hs = d->Ho; g.Ws = d->Wo; g.Ho = d->H; g.Wo = d->W; g.Hq = d->H; g.Wq = d->W; g.pstep = 1;
-    g.k = d->k; g.stride = d->stride; g.pad = d->pad_lo; g.reflect = 0; g.ld = d->Cout;
-    p.Ca = d->Cout; p.Cb = d->Cin; p.Mf = d->k * d->k * d->Cout; p.b_ld = d->Cin; p.M = d->N * d->H * d->W;
-    p.out_ld = d->Cin; p.batch = 1;
-    const bool vec = (d->Cout % 4 == 0) && (d->Cin % 4 == 0) && aligned16(dy) && aligned16(x);
-    ProfScope prof(as_stream(stream), conv_flops(d, true), tag.s, tag.bytes);
-    return launch_tn(p, GATHER_CONV, vec, dw, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
-}
-
-size_t bg_gemm_workspace_bytes(const BgGemmDesc* d) {
-    if (!d) return 0;
-    const int batch = d->batch > 0 ? d->batch : 1;
-    if (d->transA) return tn_workspace_bytes(d->M, d->N, batch, d->K);
-    if (d->ldc != d->N || batch != 1) return 0;
-    return nn_workspace_bytes(d->M, d->N, 1, kc_of(d->K), (int64_t)d->M * d->N);
+    ConvPlan pl = plan_deconv_wgrad(d);
+    if (pl.route == TN_F32)
+        BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32, "bg_deconv2d_wgrad: x and dy must both be fp32 or both bf16");
+    return run_tn(pl, d, "deconv2d_wgrad", true, dy, x, dw, ws, ws_bytes, stream);
 }
 
 int bg_gemm(const BgGemmDesc* d, const float* A, const float* B, const float* bias, const float* alpha_dev,
@@ -1493,67 +1437,34 @@ int bg_gemm(const BgGemmDesc* d, const float* A, const float* B, const float* bi
     BG_REQUIRE(A && B && C, "bg_gemm: null tensor pointer");
     const double flops = 2.0 * d->M * d->N * d->K * d->batch;
     Tag tag("gemm", d);
-    if (!d->transA) {
-        NNParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = A; p.B = B; p.bias = bias; p.alpha = alpha_dev; p.out = C;
-        Gather& g = p.g;
-        g.Nb = d->M; g.Hs = 1; g.Ws = 1; g.Ho = 1; g.Wo = 1; g.Hq = 1; g.Wq = 1; g.pstep = 1;
-        g.k = 1; g.stride = 1; g.pad = 0; g.reflect = 0; g.ld = d->lda;
-        p.C = d->K; p.M = d->M; p.N = d->N; p.tap_stride = 0;
-        if (d->transB) { p.ldk = 1; p.ldn = d->ldb; } else { p.ldk = d->ldb; p.ldn = 1; }
-        p.out_ld = d->ldc; p.accumulate = accumulate; p.batch = d->batch;
-        p.strideA = d->strideA; p.strideB = d->strideB; p.strideC = d->strideC;
-        bool vec = (d->K % 4 == 0) && (d->lda % 4 == 0) && (d->strideA % 4 == 0) && aligned16(A) &&
-                   (d->ldb % 4 == 0) && (d->strideB % 4 == 0) && aligned16(B);
-        if (!d->transB) vec = vec && (d->N % 4 == 0);
+    ConvPlan pl = plan_gemm(d);
+    // both operands are read in 16-byte pieces along their contiguous dimension
+    bool vec = (d->lda % 4 == 0) && (d->strideA % 4 == 0) && aligned16(A) && (d->ldb % 4 == 0) && (d->strideB % 4 == 0) &&
+               aligned16(B);
+    if (pl.route == F32_TAP) {
+        NNParams& p = pl.nn;
+        p.A = A; p.B = B; p.bias = bias; p.alpha = alpha_dev; p.out = C; p.accumulate = accumulate;
+        vec = vec && (d->K % 4 == 0) && (d->transB || d->N % 4 == 0);
         ProfScope prof(as_stream(stream), flops, tag.s);
-        const bool dense = d->ldc == d->N && d->batch == 1;
-        return launch_nn(p, GATHER_PLAIN, d->transB != 0, false, vec, d->batch, kc_of(d->K), (int64_t)d->M * d->N,
-                         dense, dense ? ws : nullptr, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
+        return launch_nn(pl, vec, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
     }
     BG_REQUIRE(!d->transB, "bg_gemm: transA && transB unsupported");
     BG_REQUIRE(bias == nullptr && !accumulate, "bg_gemm: transA path has no bias / accumulate");
-    TNParams p;
-    memset(&p, 0, sizeof(p));
+    TNParams& p = pl.tn;
     p.A = A; p.Bv = B; p.alpha = alpha_dev;
-    Gather& g = p.g;
-    g.Nb = d->K; g.Hs = 1; g.Ws = 1; g.Ho = 1; g.Wo = 1; g.Hq = 1; g.Wq = 1; g.pstep = 1;
-    g.k = 1; g.stride = 1; g.pad = 0; g.reflect = 0; g.ld = d->lda;
-    p.Ca = d->M; p.Cb = d->N; p.Mf = d->M; p.b_ld = d->ldb; p.M = d->K;
-    p.out_ld = d->ldc; p.batch = d->batch;
-    p.strideA = d->strideA; p.strideB = d->strideB; p.strideC = d->strideC;
-    const bool vec = (d->M % 4 == 0) && (d->lda % 4 == 0) && (d->strideA % 4 == 0) && aligned16(A) &&
-                     (d->N % 4 == 0) && (d->ldb % 4 == 0) && (d->strideB % 4 == 0) && aligned16(B);
+    vec = vec && (d->M % 4 == 0) && (d->N % 4 == 0);
     ProfScope prof(as_stream(stream), flops, tag.s);
-    return launch_tn(p, GATHER_PLAIN, vec, C, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
-}
-
-// Gram matrix of a bf16 row-major matrix: out[c1][c2] = sum_r a[r][c1] a[r][c2] (fp32), the ortho-cosine regulariser's
-// W^T W (utils.py:198) taken from the packed bf16 copy of w / sigma that the spectral-norm pass already wrote: the
-// pixel-reduction kernel in PLAIN mode with both operands the same matrix.
-static void gram16_params(const void* a, int rows, int cols, int ld, TN16Params& p) {
-    memset(&p, 0, sizeof(p));
-    p.A = a; p.Bv = a;
-    p.g.ld = ld; p.b_ld = ld;
-    p.Ca = cols; p.Cb = cols; p.Mf = cols; p.M = rows; p.out_ld = cols;
-}
-
-size_t bg_gram16_workspace_bytes(int rows, int cols) {
-    if (rows <= 0 || cols <= 0) return 0;
-    TN16Params p;
-    gram16_params(nullptr, rows, cols, cols, p);
-    return tn16_workspace_bytes(p);
+    return launch_tn(p, pl.mode, vec, C, ws, ws_bytes, as_stream(stream), d->compute == BG_COMPUTE_BF16);
 }
 
 int bg_gram16(const void* a, int rows, int cols, int ld, float* out, void* ws, size_t ws_bytes, void* stream) {
     BG_REQUIRE(a && out && rows > 0 && cols > 0 && ld >= cols, "bg_gram16: bad argument");
     BG_REQUIRE(cols % 8 == 0 && ld % 8 == 0, "bg_gram16: cols and ld must be multiples of 8");
-    TN16Params p;
-    gram16_params(a, rows, cols, ld, p);
+    ConvPlan pl = plan_gram16(rows, cols, ld);
+    pl.tn16.A = a; pl.tn16.Bv = a;
     Tag tag("gram16", cols, cols, rows);
     ProfScope prof(as_stream(stream), 2.0 * rows * (double)cols * cols, tag.s);
-    return launch_tn16(p, GATHER_PLAIN, out, ws, ws_bytes, as_stream(stream));
+    return launch_tn16(pl.tn16, pl.mode, out, ws, ws_bytes, as_stream(stream));
 }
 
 }  // extern "C"
