@@ -10,6 +10,12 @@
 // then in DOUBLE v = t * 255 (merge copies into a float64 grid), rint (nearest even), clamp to [0,255].  The widening
 // matters: an fp32 product rounds values next to a k + 0.5 tie to the other side.  NaN writes 0.
 //
+//   image_place_u8   the same bytes, but every image of the batch goes to a destination of its own: a device table gives
+//                    each image the byte offset of its first row in an arena and the pitch between its rows (the
+//                    sampling service packs the images of one generator batch into the response strips of several
+//                    request files).  The host cannot read the table, so the kernel checks every entry against the
+//                    arena and writes nothing at all for one that does not fit.
+//
 // HBM-bound, one pass.  With tw = W*C bytes per tile row and tw % 4 == 0, every tile row starts 4-element aligned in the
 // image and in the grid: one thread takes 4 consecutive elements of one tile row (one 16-byte fp32 / 8-byte bf16 load,
 // one 32-bit store of the packed bytes), adjacent lanes walk along the row.  Otherwise one element per thread.
@@ -55,6 +61,14 @@ struct SmVec4<uint16_t> {
     }
 };
 
+// 4 consecutive elements -> their 4 bytes, lowest address in the low byte
+template <typename T>
+__device__ __forceinline__ uint32_t sm_word(const T* src) {
+    float v[4];
+    SmVec4<T>::load(src, v);
+    return sm_byte(v[0]) | (sm_byte(v[1]) << 8) | (sm_byte(v[2]) << 16) | (sm_byte(v[3]) << 24);
+}
+
 struct SmGeom {
     int64_t total;      // work items: images placed * H * (tw / VEC)
     int H, tw, gw, tile0;
@@ -76,10 +90,42 @@ __global__ __launch_bounds__(SM_BLOCK) void image_tiles_u8_kernel(const T* __res
         uint8_t* dst = grid + (gr * g.H + row) * row_bytes + gc * g.tw + q * VEC;
         const T* src = x + i * VEC;                           // the placed images are a contiguous prefix of x
         if constexpr (VEC == 4) {
-            float v[4];
-            SmVec4<T>::load(src, v);
-            const uint32_t word = sm_byte(v[0]) | (sm_byte(v[1]) << 8) | (sm_byte(v[2]) << 16) | (sm_byte(v[3]) << 24);
-            *reinterpret_cast<uint32_t*>(dst) = word;
+            *reinterpret_cast<uint32_t*>(dst) = sm_word<T>(src);
+        } else {
+            dst[0] = (uint8_t)sm_byte(sm_widen(src[0]));
+        }
+    }
+}
+
+// One work item = VEC consecutive elements of one image row.  An entry is used only if the whole image fits:
+// 0 <= offset, tw <= pitch, offset + (H-1)*pitch + tw <= arena_bytes (H <= 16384 and pitch < 2^31: no overflow once
+// the extent itself is known to be <= arena_bytes).  VEC = 4 needs tw % 4 == 0, x 16-byte (fp32) / 8-byte (bf16) aligned
+// and a 4-byte aligned arena; an entry whose offset or pitch is off the 4-byte grid then stores its 4 bytes one by one.
+template <typename T, int VEC>
+__global__ __launch_bounds__(SM_BLOCK) void image_place_u8_kernel(const T* __restrict__ x,
+                                                                  const BgPlaceEntry* __restrict__ table,
+                                                                  uint8_t* __restrict__ arena, int64_t arena_bytes,
+                                                                  int64_t total, int H, int tw) {
+    const int64_t per_row = tw / VEC;
+    for (int64_t i = (int64_t)blockIdx.x * SM_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * SM_BLOCK) {
+        const int64_t r = i / per_row;                        // img * H + row
+        const int64_t q = i - r * per_row;
+        const int64_t img = r / H;
+        const int64_t row = r - img * H;
+        const BgPlaceEntry e = table[img];
+        if (e.skip != 0 || e.offset < 0 || e.pitch < tw) continue;
+        const int64_t extent = (int64_t)(H - 1) * e.pitch + tw;
+        if (extent > arena_bytes || e.offset > arena_bytes - extent) continue;
+        uint8_t* dst = arena + e.offset + row * (int64_t)e.pitch + q * VEC;
+        const T* src = x + i * VEC;
+        if constexpr (VEC == 4) {
+            const uint32_t word = sm_word<T>(src);
+            if (((e.offset | (int64_t)e.pitch) & 3) == 0) {
+                *reinterpret_cast<uint32_t*>(dst) = word;
+            } else {
+                dst[0] = (uint8_t)word; dst[1] = (uint8_t)(word >> 8); dst[2] = (uint8_t)(word >> 16);
+                dst[3] = (uint8_t)(word >> 24);
+            }
         } else {
             dst[0] = (uint8_t)sm_byte(sm_widen(src[0]));
         }
@@ -118,6 +164,37 @@ int bg_image_tiles_u8(const void* x, int x_dtype, int n, int H, int W, int C, ui
     } else {
         if (wide) hipLaunchKernelGGL((image_tiles_u8_kernel<float, 4>), blocks, block, 0, s, (const float*)x, grid, g);
         else hipLaunchKernelGGL((image_tiles_u8_kernel<float, 1>), blocks, block, 0, s, (const float*)x, grid, g);
+    }
+    BG_LAUNCH_CHECK();
+    return BG_OK;
+}
+
+int bg_image_place_u8(const void* x, int x_dtype, int n, int H, int W, int C, const BgPlaceEntry* table, uint8_t* arena,
+                      int64_t arena_bytes, void* stream) {
+    BG_REQUIRE(x && table && arena, "bg_image_place_u8: NULL tensor");
+    BG_REQUIRE(x_dtype == BG_F32 || x_dtype == BG_BF16, "bg_image_place_u8: dtype %d (BG_F32 / BG_BF16)", x_dtype);
+    BG_REQUIRE(C == 1 || C == 3 || C == 4, "bg_image_place_u8: C=%d (1, 3 or 4 channels)", C);
+    BG_REQUIRE(n > 0 && H > 0 && W > 0, "bg_image_place_u8: n=%d H=%d W=%d", n, H, W);
+    BG_REQUIRE(H <= 16384 && W <= 16384, "bg_image_place_u8: H=%d W=%d too large", H, W);
+    BG_REQUIRE(arena_bytes > 0, "bg_image_place_u8: arena_bytes=%lld", (long long)arena_bytes);
+    BG_REQUIRE(((uintptr_t)table & 7) == 0, "bg_image_place_u8: table must be 8-byte aligned");
+    const int tw = W * C;
+    const size_t esz = x_dtype == BG_BF16 ? 2 : 4;
+    BG_REQUIRE(((uintptr_t)x & (esz - 1)) == 0, "bg_image_place_u8: x is not aligned to its element size");
+    const bool wide = tw % 4 == 0 && ((uintptr_t)x & (4 * esz - 1)) == 0 && ((uintptr_t)arena & 3) == 0;
+    const int64_t total = (int64_t)n * H * (wide ? tw / 4 : tw);
+    hipStream_t s = as_stream(stream);
+    const dim3 blocks(sm_blocks(total)), block(SM_BLOCK);
+    if (x_dtype == BG_BF16) {
+        if (wide) hipLaunchKernelGGL((image_place_u8_kernel<uint16_t, 4>), blocks, block, 0, s, (const uint16_t*)x, table,
+                                     arena, arena_bytes, total, H, tw);
+        else hipLaunchKernelGGL((image_place_u8_kernel<uint16_t, 1>), blocks, block, 0, s, (const uint16_t*)x, table, arena,
+                                arena_bytes, total, H, tw);
+    } else {
+        if (wide) hipLaunchKernelGGL((image_place_u8_kernel<float, 4>), blocks, block, 0, s, (const float*)x, table, arena,
+                                     arena_bytes, total, H, tw);
+        else hipLaunchKernelGGL((image_place_u8_kernel<float, 1>), blocks, block, 0, s, (const float*)x, table, arena,
+                                arena_bytes, total, H, tw);
     }
     BG_LAUNCH_CHECK();
     return BG_OK;

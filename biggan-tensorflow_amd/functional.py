@@ -86,6 +86,23 @@ def image_tiles_u8(x, grid, gh, gw, tile0=0):
     return grid
 
 
+def image_place_u8(x, table, arena):
+    """Images x [n,H,W,C] (fp32 or bf16, C in 1/3/4) -> the bytes of image_tiles_u8, image i at
+    ``arena[offset_i + r * pitch_i : ... + W*C]`` for its rows r (csrc/sample.hip).  ``table``: int32 [n,4] on the device,
+    words 0-1 the int64 offset (little-endian), 2 the pitch, 3 skip (service.place_table builds it); ``arena``: uint8
+    [bytes] on the device.  A skip entry and an entry that does not fit the arena write nothing.  No autograd."""
+    if x.dim() != 4:
+        raise RuntimeError("image_place_u8: x must be [n,H,W,C], got %s" % (tuple(x.shape),))
+    n, H, W, C = x.shape
+    if table.dtype != torch.int32 or tuple(table.shape) != (n, 4):
+        raise RuntimeError("image_place_u8: table must be int32 [%d,4], got %s %s" % (n, table.dtype, tuple(table.shape)))
+    if arena.dtype != torch.uint8 or arena.dim() != 1:
+        raise RuntimeError("image_place_u8: arena must be uint8 [bytes], got %s %s" % (arena.dtype, tuple(arena.shape)))
+    x = _c(x.detach())
+    check(lib().bg_image_place_u8(act(x), dt(x), n, H, W, C, i32(table), hip.ptr(arena), arena.numel(), stream()))
+    return arena
+
+
 def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
     the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns

@@ -84,6 +84,11 @@ class BgHistItem(Structure):
     _fields_ = [("x", c_void_p), ("n", c_int64)]
 
 
+class BgPlaceEntry(Structure):
+    """One image of bg_image_place_u8 (functional.image_place_u8 takes them as an int32 [n,4] device tensor)."""
+    _fields_ = [("offset", c_int64), ("pitch", c_int32), ("skip", c_int32)]
+
+
 class BgJpegInfo(Structure):
     """What bg_jpeg_info reads from a JPEG file's headers (host memory)."""
     _fields_ = [(n, c_int32) for n in ("width", "height", "ncomp", "hs", "vs", "restart")] + \
@@ -250,6 +255,7 @@ SIGNATURES = {
     "bg_recon_loss_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_double, _P, _P, c_int, c_int, c_int, c_int, c_int,
                                   _P]),
     "bg_image_tiles_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
+    "bg_image_place_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P]),
     "bg_image_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
     "bg_jpeg_batch_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "bg_jpeg_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int64, c_int, _P, c_int64, _P, c_int, _P, c_size_t, _P]),

@@ -109,9 +109,11 @@ def main(argv=None):
     elif args.phase == 'test':
         gan.test()
         print(" [*] Test finished!")
+    elif args.phase == 'service':
+        gan.service()                                     # answers the latent files of --request_dir until one says quit
+        print(" [*] Service finished!")
     else:
-        raise NotImplementedError("--phase %s (the reference's HTTP sample service) is outside the MI355X hot path"
-                                  % args.phase)
+        raise NotImplementedError("--phase %s: the phases are train, test and service" % args.phase)
 
 
 if __name__ == '__main__':

@@ -1618,8 +1618,13 @@ class BigGAN(GANBase):
         writes (its power iteration advances them)."""
         return [self.store.vars[u] for w, u in self.store.sn_pairs.items() if w.startswith("generator/")]
 
-    def generate(self, z, cls_z=None, ema=True, grid=None, gh=0, gw=0, _synced=False):
-        """BigGAN.py:1397-1445 (without ``with_discriminator``): images of a list of latents (and class vectors; None
+    def _discriminator_u(self):
+        """The spectral-norm ``u`` vectors of the discriminator (what its no-grad, is_training=False pass writes)."""
+        return [self.store.vars[u] for w, u in self.store.sn_pairs.items() if w.startswith("discriminator/")]
+
+    def generate(self, z, cls_z=None, ema=True, grid=None, gh=0, gw=0, _synced=False, with_discriminator=False,
+                 _place=None):
+        """BigGAN.py:1397-1445: images of a list of latents (and class vectors; None
         with --n_labels: zeros).  The list is padded to a multiple of ``batch_size`` by repeating entry 0 and runs
         ``batch_size`` at a time with is_training=False; ``ema`` reads the trainables from their moving averages,
         swapped in once for the whole call.  With ``grid`` (uint8 [gh*S, gw*S, c_dim] on the device) each batch goes straight
@@ -1629,7 +1634,16 @@ class BigGAN(GANBase):
         Unlike ``sample()`` this leaves the model as it found it: the generator's ``u`` vectors are put back before
         every batch and after the last, so each image is a function of its latent alone and the training run does not
         depend on whether anybody looked at samples.  Under a sharded optimiser the caller runs
-        ``sync_sharded_state()`` on every rank first (``_synced``); the generator passes themselves are local."""
+        ``sync_sharded_state()`` on every rank first (``_synced``); the generator passes themselves are local.
+
+        ``with_discriminator``: every batch also runs ``discriminator(img, is_training=False, reuse=True)`` without the
+        reconstruction heads, and the call returns ``(images or grid, {key: fp32 [n, ...]})`` with ``real`` [n,1] and,
+        under --n_labels, ``cls`` [n,n_labels], trimmed to len(z).  The discriminator's ``u`` vectors are put back like
+        the generator's.  (The reference builds this discriminator with is_training=True; under --bn_in_d the padding
+        rows would then move the answer and the moving statistics, so this pass reads the population statistics.)
+        ``_place`` (the sampling service): ``(table int32 [padded n, 4], arena uint8 [bytes])`` on the device - each
+        batch goes through ``functional.image_place_u8`` with its rows of the table instead of being kept, and the arena
+        takes the place of the images in the result."""
         import numpy as np
 
         def dev(a, width):
@@ -1659,8 +1673,14 @@ class BigGAN(GANBase):
         self._wait_params("generator")
         arena = self.g_arena
         u_live = self._generator_u()
-        sn_batches = getattr(self, "sn_batches", {}).get("generator", ())
-        out = []
+        sn_batches = list(getattr(self, "sn_batches", {}).get("generator", ()))
+        if with_discriminator:
+            self._wait_params("discriminator")
+            u_live = u_live + self._discriminator_u()
+            sn_batches += getattr(self, "sn_batches", {}).get("discriminator", ())
+        if _place is not None and tuple(_place[0].shape) != (z.shape[0], 4):
+            raise ValueError("generate: the placement table must be [%d,4], got %s" % (z.shape[0], tuple(_place[0].shape)))
+        out, d_out = [], {}
         with torch.no_grad():
             u_saved = [u.clone() for u in u_live]
             live = None
@@ -1678,7 +1698,12 @@ class BigGAN(GANBase):
                     ops.begin_run(None, 1)
                     img = self.generator(z[b:b + B], None if cls_z is None else cls_z[b:b + B], is_training=False,
                                          reuse=True)
-                    if grid is not None:
+                    if with_discriminator:
+                        for k, v in self.discriminator(img, is_training=False, reuse=True).items():
+                            d_out.setdefault(k, []).append(v.float())
+                    if _place is not None:
+                        Fn.image_place_u8(img, _place[0][b:b + B], _place[1])
+                    elif grid is not None:
                         Fn.image_tiles_u8(img, grid, gh, gw, tile0=b)
                     else:
                         out.append(img)
@@ -1689,9 +1714,10 @@ class BigGAN(GANBase):
                     torch._foreach_copy_(u_live, u_saved)
                 if live is not None:
                     arena.params.copy_(live)
-        if grid is not None:
-            return grid
-        return torch.cat(out)[:n]
+        res = _place[1] if _place is not None else grid if grid is not None else torch.cat(out)[:n]
+        if with_discriminator:
+            return res, {k: torch.cat(v)[:n] for k, v in d_out.items()}
+        return res
 
     def static_sample_set(self):
         """(z [rounded_n,1,1,z_dim], class vectors [rounded_n,n_labels] or None) as fp32 numpy arrays: the static sample
@@ -1787,6 +1813,87 @@ class BigGAN(GANBase):
             paths.append(save_images(samples[:dim * dim, :, :, :], [dim, dim],
                                      result_dir + '/' + self.model_name + '_test_{}.png'.format(i)))
         return paths
+
+    # ---- --phase service (BigGAN.py:1298-1369) -----------------------------------------------
+    def _serve_group(self, group):
+        """Run one group of a round (service.Group) on the device -> (arena uint8 [arena_bytes], {key: fp32 [total, ...]})
+        as numpy arrays on the host.  The latents go up once, ``generate`` swaps the moving averages in once and runs
+        the generator, optionally the discriminator, and one placement launch per batch; the strips come back in one
+        copy into a pinned buffer, the discriminator's outputs, stacked column-wise, in another."""
+        dev = self.device
+        arena = torch.zeros(group.arena_bytes, dtype=torch.uint8, device=dev)
+        table = torch.from_numpy(group.table).to(dev)
+        z = torch.from_numpy(group.z).to(dev)
+        cls_z = None if group.cls is None else torch.from_numpy(group.cls).to(dev)
+        res = self.generate(z, cls_z, ema=group.ema, with_discriminator=group.use_discriminator, _place=(table, arena))
+        host = torch.empty(group.arena_bytes, dtype=torch.uint8, pin_memory=True)
+        host.copy_(arena, non_blocking=True)
+        outs = {}
+        if group.use_discriminator:
+            keys = sorted(res[1])
+            stacked = torch.cat([res[1][k].reshape(group.total, -1) for k in keys], dim=1).cpu()    # (synchronises)
+            col = 0
+            for k in keys:
+                w = res[1][k].numel() // group.total
+                outs[k] = stacked[:, col:col + w].numpy()
+                col += w
+        torch.cuda.current_stream().synchronize()
+        return host.numpy(), outs
+
+    def _serve_round(self, rnd, request_dir, pool):
+        """Answer a planned round (service.Round); returns when every response is written.  Responses are encoded by
+        ``pool`` while the next group runs (zlib releases the GIL).  Returns the number of files answered with images."""
+        from . import service as Sv
+        pending = [pool.submit(Sv.write_error, path, msg) for path, msg in rnd.errors]
+        served = 0
+        for group in rnd.groups:
+            try:
+                if group.load_checkpoint is not None:
+                    self.load_checkpoint(group.load_checkpoint)
+                arena, outs = self._serve_group(group) if group.total else (None, {})
+            except (OSError, KeyError, ValueError) as e:       # (a checkpoint that is not there or does not fit)
+                if group.load_checkpoint is None:
+                    raise
+                pending += [pool.submit(Sv.write_error, req.path, "load_checkpoint %s: %s" % (group.load_checkpoint, e))
+                            for req in group.files]
+                continue
+            for req in group.files:
+                pending.append(pool.submit(Sv.write_response, req, request_dir, arena, outs, self.img_size, self.c_dim))
+                served += 1 if req.n else 0
+        for f in pending:
+            f.result()
+        return served
+
+    def service(self, poll_s=0.005, idle_timeout_s=None):
+        """--phase service (BigGAN.py:1298-1369): load the latest checkpoint, then answer the request files of
+        ``--request_dir`` until one of them says ``quit``.  ``NAME.txt`` holds latents (utils.read_vectors) and is
+        answered with ``NAME.png``, the strip of its images, and under ``use_discriminator=1`` with ``NAME_<key>.out``
+        (utils.write_vectors).  The pending files of a poll round share generator batches (service.plan_round).
+        ``idle_timeout_s``: return after this long without a request (None: never).  Returns the number of files answered
+        with images."""
+        from concurrent.futures import ThreadPoolExecutor
+        from . import service as Sv
+        from .utils import check_folder
+        if self.world > 1:
+            raise RuntimeError("--phase service runs in one process (world size %d)" % self.world)
+        could_load, _ = self.load(self.checkpoint_dir)
+        print(" [*] Load SUCCESS" if could_load else " [!] Load failed...")
+        request_dir = check_folder(self.args.request_dir)
+        served, last = 0, time.monotonic()
+        with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))) as pool:
+            while True:
+                paths = Sv.list_requests(request_dir)
+                if paths:
+                    rnd = Sv.plan_round(Sv.read_requests(paths), self.batch_size, self.z_dim, self.n_labels if self.acgan
+                                        else 0, self.img_size, self.c_dim)
+                    served += self._serve_round(rnd, request_dir, pool)
+                    if rnd.quit is not None:
+                        os.remove(rnd.quit)                                            # BigGAN.py:1324-1326
+                        return served
+                    last = time.monotonic()
+                elif idle_timeout_s is not None and time.monotonic() - last >= idle_timeout_s:
+                    return served
+                time.sleep(poll_s)
 
     # ---- checkpoints (BigGAN.py:1255-1284) ---------------------------------------------------
     def _ckpt_dir(self, checkpoint_dir):

@@ -108,6 +108,39 @@ def save_images(images, size, image_path):
 
 
 ##################################################################################
+# Vector files of the sampling service (utils.py:53-69, 395-407)
+##################################################################################
+def read_vectors(path):
+    """utils.py:53-69: ``(cmds, vectors)`` of a tab-separated file with ``"`` as the quote character.  A row whose first
+    field starts with ``!`` is a command row of ``key[=value]`` fields (a key without a value maps to ''); empty rows are
+    skipped; every other row is one vector of floats (ValueError for a field that is no number)."""
+    import csv
+    vectors, cmds = [], {}
+    with open(path, 'r', newline='') as f:
+        for row in csv.reader(f, delimiter='\t', quotechar='"'):
+            if len(row) == 0:
+                continue
+            if row[0][:1] == '!':
+                row[0] = row[0][1:]
+                for cmd in row:
+                    p = cmd.split('=', 1)
+                    cmds[p[0]] = p[1] if len(p) > 1 else ''
+            else:
+                vectors.append([float(v) for v in row])
+    return cmds, vectors
+
+
+def write_vectors(path, rows):
+    """utils.py:395-407: one line per sample, fields tab-separated, each number as ``str(numpy.float32(v))`` (the
+    shortest text that reads back to the same float32).  A sample is a scalar or a sequence of numbers."""
+    import numpy as np
+    with open(path, 'w') as f:
+        for row in rows:
+            f.write('\t'.join(str(np.float32(v)) for v in np.asarray(row, dtype=np.float32).reshape(-1)) + '\n')
+    return path
+
+
+##################################################################################
 # Regularization (utils.py:180-235)
 ##################################################################################
 def orthogonal_regularizer(scale, type='ortho'):

@@ -790,6 +790,22 @@ int bg_recon_loss_bwd(const float* y, const float* target, const int32_t* off_y,
 int bg_image_tiles_u8(const void* x, int x_dtype, int n, int H, int W, int C, uint8_t* grid, int gh, int gw, int tile0,
                       void* stream);
 
+/* bg_image_place_u8: the same bytes, every image to a destination of its own inside one uint8 arena (the sampling service
+ *   packs the images of a generator batch into the response strips of several request files).
+ *   table  n entries of 16 bytes on the device (int32 [n,4], little-endian):
+ *            word 0-1 offset (int64) of the image's first byte in arena   2 pitch (bytes per row)   3 skip (0 / 1)
+ *   Row r of image i goes to arena + offset + r * pitch.  skip != 0 is a padding slot and writes nothing.
+ *   The library cannot read the table: an entry with offset < 0, pitch < W*C or offset + (H-1)*pitch + W*C > arena_bytes
+ *   writes nothing at all.  Overlapping destinations are the caller's error.
+ *   When W*C, offset and pitch are multiples of 4 (and x and arena are aligned for it) a thread converts 4 consecutive
+ *   elements and stores one 32-bit word; otherwise the stores are single bytes. */
+typedef struct BgPlaceEntry {
+    int64_t offset;
+    int32_t pitch, skip;
+} BgPlaceEntry;
+int bg_image_place_u8(const void* x, int x_dtype, int n, int H, int W, int C, const BgPlaceEntry* table, uint8_t* arena,
+                      int64_t arena_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------------
  * Input batches (utils.py:12-38 image_processing, BigGAN.py:768-787; csrc/input.hip).
  * bg_image_batch_u8: the decoded pixels of n images -> the training batch out [n,S,S,C] fp32 in [-1,1], C in {1,3,4}.
