@@ -103,6 +103,68 @@ def image_place_u8(x, table, arena):
     return arena
 
 
+def _u8_arena(name, what, t):
+    if t.dtype != torch.uint8 or t.dim() != 1:
+        raise RuntimeError("%s: %s must be uint8 [bytes], got %s %s" % (name, what, t.dtype, tuple(t.shape)))
+    return hip.ptr(t)                                          # (refuses a host or non-contiguous tensor)
+
+
+def _i32_table(name, what, t, cols, rows=None):
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols or t.shape[0] < 1 or \
+            (rows is not None and t.shape[0] != rows):
+        raise RuntimeError("%s: %s must be int32 [%s,%d], got %s %s"
+                           % (name, what, "n" if rows is None else rows, cols, t.dtype, tuple(t.shape)))
+    return i32(t)
+
+
+def deflate_bound(length):
+    """Bytes a slot of ``deflate_segments`` must hold for a segment of ``length`` bytes (host function)."""
+    return int(lib().bg_deflate_bound(int(length)))
+
+
+def png_filter(src, table, max_h, bpp, dst):
+    """Images inside the uint8 arena ``src`` -> their PNG-filtered streams inside ``dst`` (csrc/png.hip): per row the
+    filter type 0-4 with the smallest sum of abs((int8)residual), ties to the lowest, then the filtered bytes.  ``table``:
+    int32 [n,6] on the device, words 0-1 the int64 source offset, 2 h, 3 row_bytes, 4-5 the int64 destination offset
+    (png.plan builds it); ``max_h`` >= every h; ``bpp`` 1, 3 or 4.  An entry that does not fit either arena writes
+    nothing.  No autograd."""
+    ps, pd = _u8_arena("png_filter", "src", src), _u8_arena("png_filter", "dst", dst)
+    pt = _i32_table("png_filter", "table", table, 6)
+    check(lib().bg_png_filter(ps, src.numel(), pt, table.shape[0], int(max_h), int(bpp), pd, dst.numel(), stream()))
+    return dst
+
+
+def deflate_segments(src, table, seg_bytes, dst, records):
+    """Segments of the uint8 arena ``src`` -> one byte-aligned DEFLATE block each, in their slots of ``dst``
+    (csrc/png.hip).  ``table``: int32 [m,6] on the device, words 0-1 the int64 source offset, 2 len, 3 last, 4-5 the
+    int64 slot offset; ``records``: int32 [m,4] on the device, filled with nbytes, adler_a, adler_b, kind (1 dynamic,
+    0 stored, -1 the entry did not fit).  ``seg_bytes``: a power of two from 256 to 32768, >= every len.  No autograd."""
+    ps, pd = _u8_arena("deflate_segments", "src", src), _u8_arena("deflate_segments", "dst", dst)
+    pt = _i32_table("deflate_segments", "table", table, 6)
+    pr = _i32_table("deflate_segments", "records", records, 4, rows=table.shape[0])
+    check(lib().bg_deflate_segments(ps, src.numel(), pt, table.shape[0], int(seg_bytes), pd, dst.numel(), pr, stream()))
+    return records
+
+
+def deflate_compact(slots, table, records, out, seg_off, totals):
+    """The slots that ``deflate_segments`` filled -> one contiguous buffer ``out`` (csrc/png.hip).  ``seg_off``: int64
+    [m+1] on the device, the offset of every segment in ``out`` and the total; ``totals``: int64 [streams,2] on the
+    device, (offset, bytes) of every stream.  No autograd."""
+    ps, po = _u8_arena("deflate_compact", "slots", slots), _u8_arena("deflate_compact", "out", out)
+    pt = _i32_table("deflate_compact", "table", table, 6)
+    pr = _i32_table("deflate_compact", "records", records, 4, rows=table.shape[0])
+    m = table.shape[0]
+    if seg_off.dtype != torch.int64 or tuple(seg_off.shape) != (m + 1,):
+        raise RuntimeError("deflate_compact: seg_off must be int64 [%d], got %s %s" % (m + 1, seg_off.dtype,
+                                                                                      tuple(seg_off.shape)))
+    if totals.dtype != torch.int64 or totals.dim() != 2 or totals.shape[1] != 2 or not 1 <= totals.shape[0] <= m:
+        raise RuntimeError("deflate_compact: totals must be int64 [streams,2] with 1 <= streams <= %d, got %s %s"
+                           % (m, totals.dtype, tuple(totals.shape)))
+    check(lib().bg_deflate_compact(ps, slots.numel(), pt, pr, m, po, out.numel(), hip.ptr(seg_off), hip.ptr(totals),
+                                   totals.shape[0], stream()))
+    return out
+
+
 def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
     the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns

@@ -256,6 +256,10 @@ SIGNATURES = {
                                   _P]),
     "bg_image_tiles_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
     "bg_image_place_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P]),
+    "bg_deflate_bound": (c_size_t, [c_int]),
+    "bg_png_filter": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, c_int64, _P]),
+    "bg_deflate_segments": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int64, _P, _P]),
+    "bg_deflate_compact": (c_int, [_P, c_int64, _P, _P, c_int, _P, c_int64, _P, _P, c_int, _P]),
     "bg_image_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
     "bg_jpeg_batch_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "bg_jpeg_batch_u8": (c_int, [_P, c_int64, _P, c_int, c_int64, c_int, _P, c_int64, _P, c_int, _P, c_size_t, _P]),

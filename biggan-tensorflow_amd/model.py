@@ -1756,8 +1756,9 @@ class BigGAN(GANBase):
         Every rank calls it (``sync_sharded_state`` is collective); rank 0 runs the generator and writes.  Nothing the
         training run reads is changed: parameters, moving averages, optimiser slots, statistics, every ``u``,
         ``self.gen`` and ``self.counter`` are bit-identical afterwards.  The grids are assembled as bytes on the device
-        and cross to the host once, one byte per element."""
-        from . import sampling as Sp
+        and cross to the host once, one byte per element; under BG_DEVICE_PNG=1 they are also encoded there (png.py) and
+        only the files' bytes cross."""
+        from . import png as Png, sampling as Sp
         from .utils import write_png, check_folder
         self.sync_sharded_state()
         if self.rank != 0:
@@ -1772,7 +1773,13 @@ class BigGAN(GANBase):
             grid = torch.zeros(side * self.img_size, side * self.img_size, self.c_dim, dtype=torch.uint8,
                                device=self.device)
             self.generate(z, cls_z, ema=ema, grid=grid, gh=side, gw=side, _synced=True)
-            paths.append(write_png(grid.cpu().numpy(), os.path.join(self.sample_dir, name)))
+            path = os.path.join(self.sample_dir, name)
+            if Png.enabled():                              # filtered and compressed where it lies (csrc/png.hip)
+                with open(path, "wb") as f:
+                    f.write(Png.encode_device(grid.reshape(-1), [(0,) + tuple(grid.shape)])[0])
+                paths.append(path)
+            else:
+                paths.append(write_png(grid.cpu().numpy(), path))
 
         def plain(kind, ema):
             if self.static_sample_z:
@@ -1819,15 +1826,19 @@ class BigGAN(GANBase):
         """Run one group of a round (service.Group) on the device -> (arena uint8 [arena_bytes], {key: fp32 [total, ...]})
         as numpy arrays on the host.  The latents go up once, ``generate`` swaps the moving averages in once and runs
         the generator, optionally the discriminator, and one placement launch per batch; the strips come back in one
-        copy into a pinned buffer, the discriminator's outputs, stacked column-wise, in another."""
+        copy into a pinned buffer, the discriminator's outputs, stacked column-wise, in another.  Under BG_DEVICE_PNG=1
+        the strips are encoded in the arena (png.encode_device) and the first result is {request path: PNG bytes}."""
+        from . import png as Png
         dev = self.device
         arena = torch.zeros(group.arena_bytes, dtype=torch.uint8, device=dev)
         table = torch.from_numpy(group.table).to(dev)
         z = torch.from_numpy(group.z).to(dev)
         cls_z = None if group.cls is None else torch.from_numpy(group.cls).to(dev)
         res = self.generate(z, cls_z, ema=group.ema, with_discriminator=group.use_discriminator, _place=(table, arena))
-        host = torch.empty(group.arena_bytes, dtype=torch.uint8, pin_memory=True)
-        host.copy_(arena, non_blocking=True)
+        device_png = Png.enabled()
+        if not device_png:
+            host = torch.empty(group.arena_bytes, dtype=torch.uint8, pin_memory=True)
+            host.copy_(arena, non_blocking=True)
         outs = {}
         if group.use_discriminator:
             keys = sorted(res[1])
@@ -1837,6 +1848,11 @@ class BigGAN(GANBase):
                 w = res[1][k].numel() // group.total
                 outs[k] = stacked[:, col:col + w].numpy()
                 col += w
+        if device_png:                                     # every strip of the group in one launch of each kernel
+            served = [r for r in group.files if r.n]
+            S_, C_ = self.img_size, self.c_dim
+            files = Png.encode_device(arena, [(r.offset, S_, r.n * S_, C_) for r in served])
+            return {r.path: f for r, f in zip(served, files)}, outs
         torch.cuda.current_stream().synchronize()
         return host.numpy(), outs
 

@@ -177,8 +177,8 @@ def read_requests(paths):
 
 
 def write_response(req, request_dir, arena, outs, img_size, c_dim):
-    """Answer one request from its group's results (``arena`` uint8 [arena_bytes] and ``outs`` {key: fp32 [total, ...]}
-    on the host): the ``.out`` files, then ``NAME.tmp.png`` renamed to ``NAME.png``, then the request file goes - a
+    """Answer one request from its group's results (``arena`` uint8 [arena_bytes], or under BG_DEVICE_PNG=1 the files'
+    PNG bytes by request path, and ``outs`` {key: fp32 [total, ...]} on the host): the ``.out`` files, then ``NAME.tmp.png`` renamed to ``NAME.png``, then the request file goes - a
     client that waits for the PNG finds everything.  A file without vectors is only removed (BigGAN.py:1350, 1366)."""
     from .utils import write_png, write_vectors
     if req.n:
@@ -188,8 +188,12 @@ def write_response(req, request_dir, arena, outs, img_size, c_dim):
                 if req.wants(key):
                     write_vectors(stem + "_" + key + ".out", outs[key][req.first:req.first + req.n])
         S = int(img_size)
-        strip = arena[req.offset:req.offset + S * req.pitch].reshape(S, req.n * S, int(c_dim))
-        write_png(strip, stem + ".tmp.png")
+        if isinstance(arena, dict):                                                    # encoded on the device (png.py)
+            with open(stem + ".tmp.png", "wb") as f:
+                f.write(arena[req.path])
+        else:
+            strip = arena[req.offset:req.offset + S * req.pitch].reshape(S, req.n * S, int(c_dim))
+            write_png(strip, stem + ".tmp.png")
         os.rename(stem + ".tmp.png", stem + ".png")
     os.remove(req.path)
     return req.name

@@ -807,6 +807,49 @@ int bg_image_place_u8(const void* x, int x_dtype, int n, int H, int W, int C, co
                       int64_t arena_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Device-side PNG encoding (csrc/png.hip; an addition to ABI 10: new symbols only, nothing existing changes).  The bytes of
+ * bg_image_tiles_u8 / bg_image_place_u8 are filtered and DEFLATE-compressed where they lie; the host adds the zlib and PNG
+ * framing (png.py).  All three launchers are stream-ordered, allocate nothing, and cannot read their device tables: a
+ * kernel checks every entry against the arena sizes it was given and writes nothing for one that does not fit.
+ *
+ * bg_png_filter: images inside the uint8 arena src -> their filtered streams inside dst.  Image i is h rows of row_bytes
+ *   bytes at src + src_offset; its stream is h rows of 1 + row_bytes bytes at dst + dst_offset: the filter type, then the
+ *   filtered bytes.  The type of a row is the type 0-4 with the smallest sum of abs((int8)residual), ties to the lowest
+ *   type; the row above the first is zeros; bpp (1, 3 or 4) is common to the launch.  max_h >= every h (an entry with
+ *   h > max_h writes nothing).  One workgroup per row.
+ * bg_deflate_segments: segment j, len bytes (1 <= len <= seg_bytes) at src + src_offset, is compressed on its own - no match
+ *   reaches outside it - into its slot of bg_deflate_bound(len) bytes at dst + dst_offset, byte-aligned: one dynamic-Huffman
+ *   block (literals and distance-1 matches of 3..258 bytes, code lengths <= 15, code-length code <= 7) or, when that is not
+ *   smaller, one stored block; with last == 0 an empty stored block follows (000, zero padding, 00 00 FF FF), with last != 0
+ *   the block carries BFINAL and is zero-padded to a byte.  The slots of one stream, end to end, are a raw DEFLATE stream.
+ *   records[4*j .. 4*j+3] = nbytes, adler_a, adler_b (the Adler-32 halves of the segment on its own), kind (1 dynamic,
+ *   0 stored, -1 the entry did not fit: nbytes 0, nothing written).  seg_bytes: a power of two from 256 to 32768.
+ *   Same input, same bytes: on every call, whatever else shares the launch.
+ * bg_deflate_bound: what a slot must hold (a true upper bound of nbytes); host function.
+ * bg_deflate_compact: seg_off[j] = sum of nbytes before segment j (seg_off[n_segs] = the total), the slots gathered into
+ *   out at those offsets, and totals[2*k], totals[2*k+1] = (offset in out, bytes) of stream k, a stream ending at every
+ *   segment with last != 0.  seg_off: int64 [n_segs + 1]; totals: int64 [2 * n_streams].
+ * ------------------------------------------------------------------------------------------ */
+typedef struct BgPngImage {
+    int64_t src_offset;
+    int32_t h, row_bytes;
+    int64_t dst_offset;
+} BgPngImage;
+typedef struct BgDeflateSeg {
+    int64_t src_offset;
+    int32_t len, last;
+    int64_t dst_offset;
+} BgDeflateSeg;
+size_t bg_deflate_bound(int len);
+int bg_png_filter(const uint8_t* src, int64_t src_bytes, const BgPngImage* table, int n, int max_h, int bpp, uint8_t* dst,
+                  int64_t dst_bytes, void* stream);
+int bg_deflate_segments(const uint8_t* src, int64_t src_bytes, const BgDeflateSeg* table, int n_segs, int seg_bytes,
+                        uint8_t* dst, int64_t dst_bytes, int32_t* records, void* stream);
+int bg_deflate_compact(const uint8_t* slots, int64_t slots_bytes, const BgDeflateSeg* table, const int32_t* records,
+                       int n_segs, uint8_t* out, int64_t out_bytes, int64_t* seg_off, int64_t* totals, int n_streams,
+                       void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Input batches (utils.py:12-38 image_processing, BigGAN.py:768-787; csrc/input.hip).
  * bg_image_batch_u8: the decoded pixels of n images -> the training batch out [n,S,S,C] fp32 in [-1,1], C in {1,3,4}.
  *   raw    one packed uint8 buffer of raw_bytes bytes; image i is [h,w,C] row-major at table[i].offset, a multiple of 16
