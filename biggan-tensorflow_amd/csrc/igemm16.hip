@@ -10,7 +10,8 @@
 // K loop is {issue next tile's LDS-DMA ; ds_read_b128 fragments ; MFMA ; barrier}.
 //
 //   nn16_kernel  out[m, n] = sum_tap sum_c A(pixel(m), tap)[c] * B[tap][n][c]        (forward, input gradients)
-//       block tile 128 x (32*TN) x 64, 4 waves (2 x 2), v_mfma_f32_16x16x32_bf16, fp32 accumulate.
+//       block tile 128 x (32*TN) x 64, 4 waves (2 x 2), v_mfma_f32_16x16x32_bf16, fp32 accumulate (this is the two-stage
+//       form; SLOTS = 3: a ring of 32-channel stages under the same or a 256-row tile, see the kernel's header).
 //       LDS image: rows of 64 bf16 (128 B); 16-byte chunk c of row r is stored at chunk position c ^ ((r >> 1) & 7):
 //       LDS-DMA writes are lane-linear, so the swizzle is applied to the SOURCE chunk each lane fetches, and the
 //       ds_read_b128 operand reads (lane -> row lane & 15, chunk lane >> 4) are bank-conflict free.
@@ -98,6 +99,12 @@ constexpr int nn16_lds_bytes(int TN, int TAPS = NN16_TAPS) {
     // moves the stages off their 1 KB alignment, which costs the LDS-DMA writes of the HBM-bound layers ~25 %)
     return (2 * stage + tab > epi ? 2 * stage + tab : epi) + NN16_BM * 4 + 16;
 }
+// ring forms (SLOTS = 3): three stages of 32 channels (64-byte rows), row tables [axis 0: int32 | axis 1: int16], the
+// epilogue passes through the ring area in parts of 64 rows
+constexpr int nn16_pipe_lds_bytes(int TN, int WM, int TAPS = NN16_TAPS) {
+    const int bm = 64 * WM;
+    return 3 * (bm + 32 * TN) * 64 + TAPS * bm * (4 + 2) + bm * 4 + 16;
+}
 constexpr int NN16_NOSRC = -(1 << 30);                         // table entry of a tap without a source pixel
 
 // element offset of the source pixel of row r under tap (kh, kw), or -1 (selects, no divergent branches)
@@ -168,19 +175,52 @@ __device__ __forceinline__ RowPos nn16_row(const NN16Params& p, int m, int ph, i
 // instantiation because the tap bookkeeping costs the short-K launches (1 x 1 convolutions: 3 K steps) 25 %.
 // RING (NN16Params::ring; PM launches of transposed gathers only): 8 tap slots per axis = real taps followed by the taps
 // of the mirrored padded position.
-template <int TN, int MODE, bool PM, bool RING = false>
-__global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
+//
+// SLOTS / WM - how deep the operand pipeline of a block is (chosen per launch by nn16_form):
+//   SLOTS = 2, WM = 2  two 64-channel stages, ONE tile in flight: stage(next) ; 8 TN MFMAs per wave ; vmcnt(0) ; barrier.
+//       At TN = 4 the MFMAs of a step take ~0.21 us and the tile they wait for was issued that long ago, while an LDS-DMA
+//       takes on the order of a microsecond from issue to landing: a block is parked for most of a step and only the CU's
+//       second block (70 KB of LDS each) fills the matrix pipe - mfma_busy 0.50, 39 % of wave cycles waiting (r02 counters,
+//       384 -> 384 at 32^2).
+//   SLOTS = 3, WM = 2  the same 128 x 32 TN tile on a 3-slot ring of 32-channel stages (64-byte LDS rows, chunk c of row r at
+//       c ^ ((r >> 1) & 2)): tile s + 2 is issued right after the barrier of step s and the wait in front of that barrier is
+//       a counted vmcnt that leaves the newest tile in flight (tn16x_kernel's kstep).  Two tiles in flight per block, and
+//       52.7 KB of LDS (the epilogue goes through LDS in halves) let three blocks share a CU.
+//   SLOTS = 3, WM = 4  the same ring under a 256 x 32 TN tile on 8 waves (2 A + <= 1 B LDS-DMA per wave and stage): a quarter
+//       fewer L2 -> LDS bytes per FLOP; two blocks per CU, <= 128 VGPRs.
+// Every form feeds an accumulator the same sequence of 32-channel MFMA K blocks (the split-K partition stays in 64-channel
+// steps = two stages), so their results are bit-identical.
+// Measured (profiles/nn16_pipe_ab.txt; 384 -> 384 at 32^2 on this kernel, 256 images): mfma_busy 0.495 with two stages, 0.414
+// with the 128-row ring, 0.530 with the wide form; no LDS bank conflicts in any.  The 64-byte rows cost more than the deeper
+// pipeline buys wherever weights stream (each 128-byte line is requested twice, a step apart: the CU's L2 read requests
+// double), so the 128-row ring is a default nowhere and the wide form takes the image-major launches with C <= 192 - see
+// nn16_form for the per-layer numbers.
+template <int TN, int MODE, bool PM, bool RING = false, int SLOTS = 2, int WM = 2>
+__global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void nn16_kernel(const NN16Params p) {
     static_assert(!RING || (PM && MODE == GATHER_TCONV), "ring launches are position-major transposed gathers");
+    static_assert((SLOTS == 2 && WM == 2) || (SLOTS == 3 && (WM == 2 || WM == 4)), "two stages, or a 3-slot ring on 4 / 8 waves");
+    constexpr bool PIPE = SLOTS == 3;
     constexpr int TAPS = RING ? NN16_RING_TAPS : NN16_TAPS;
-    constexpr int LDS_BYTES = nn16_lds_bytes(TN, TAPS);
+    constexpr int LDS_BYTES = PIPE ? nn16_pipe_lds_bytes(TN, WM, TAPS) : nn16_lds_bytes(TN, TAPS);
     typedef typename std::conditional<RING, uint64_t, unsigned>::type mask_t;
-    constexpr int BM = NN16_BM, BN = 32 * TN;
-    constexpr int JA = BM / 32, JB = BN / 32;      // LDS-DMA instructions per wave and K step
-    constexpr int A_BYTES = BM * 128, STAGE = (BM + BN) * 128;
+    typedef typename std::conditional<PIPE, int16_t, int>::type tabw_t;     // column table entries (source column, < 0: none)
+    constexpr int BM = 64 * WM, BN = 32 * TN, NTHR = 128 * WM, NWV = 2 * WM;
+    constexpr int CPS = PIPE ? 4 : 8;              // 16-byte chunks of K per stage = per LDS row
+    constexpr int ROWB = 16 * CPS;                 // bytes of an LDS row
+    constexpr int RSTR = PIPE ? 16 * NWV : 32;     // rows between the LDS-DMA instructions of a wave (1 KB = 1024 / ROWB rows each)
+    // LDS-DMA instructions per wave and stage; PIPE: wave w stages the 16-row groups w, w + NWV, ... below BN / 16
+    constexpr int JA = BM / RSTR, JB = PIPE ? (BN / 16 + NWV - 1) / NWV : BN / 32;
+    constexpr int A_BYTES = BM * ROWB, STAGE = (BM + BN) * ROWB;
+    static_assert(BM == NN16_BM || PIPE, "the two-stage form has 128-row tiles");
+    static_assert(A_BYTES % 1024 == 0 && STAGE % 1024 == 0 && (RSTR * ROWB) % 1024 == 0,
+                  "every LDS-DMA destination is 1 KB aligned");
+    static_assert(!PIPE || 64 * (BN + 4) * 4 <= SLOTS * STAGE, "a 64-row part of the epilogue fits in front of the tables");
+    static_assert(!PIPE || RING || LDS_BYTES * (WM == 4 ? 2 : 3) <= 160 * 1024, "ring forms: 3 (8 waves: 2) blocks per CU");
+    static_assert(!PIPE || LDS_BYTES * 2 <= 160 * 1024, "mirrored-tap ring launches: 2 blocks per CU");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int t = threadIdx.x;
-    const int lane = t & 63, w = t >> 6;
+    const int lane = t & 63, w = PIPE ? __builtin_amdgcn_readfirstlane(t >> 6) : t >> 6;
     const int wm = w >> 1, wn = w & 1;
     const Gather& g = p.g;
 
@@ -253,9 +293,9 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
         __syncthreads();
     }
     unsigned any_local = 0;
-    int* tabh = reinterpret_cast<int*>(smem + 2 * STAGE);
-    int* tabw = tabh + TAPS * BM;
-    for (int e = t; e < 2 * TAPS * BM; e += 256) {
+    int* tabh = reinterpret_cast<int*>(smem + SLOTS * STAGE);
+    tabw_t* tabw = reinterpret_cast<tabw_t*>(tabh + TAPS * BM);
+    for (int e = t; e < 2 * TAPS * BM; e += NTHR) {
         const int axis = e / (TAPS * BM), i = (e / BM) % TAPS, row = e % BM;
         const RowPos r = nn16_row<MODE, PM, RING>(p, m0 + row, ph, pw);
         int v = NN16_NOSRC;
@@ -277,7 +317,8 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
                 any_local |= 1u << (axis * TAPS + i);
             }
         }
-        tabh[e] = v;
+        if (PIPE && axis) tabw[e - TAPS * BM] = (tabw_t)(v < 0 ? -1 : v);      // (source columns < 2^15: nn16_form)
+        else tabh[e] = v;
     }
     if (PM && any_local) atomicOr(&s_any, any_local);
     // output pixel of every row (transposed gathers: rows enumerate a stride phase, possibly of a padded grid), behind
@@ -290,8 +331,12 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
     }
 
     // ---- staging role of this lane: 16-byte chunk `cch` of the K step, rows 32 j + rsub of both tiles ----
-    const int cch = (lane & 7) ^ ((((w & 1) << 2) | (lane >> 4)) & 7);
-    const int rsub = 8 * w + (lane >> 3);
+    // (PIPE: 4 chunks per row, an instruction covers 16 rows; chunk c of row r sits at c ^ ((r >> 1) & 2))
+    const int cch = PIPE ? (lane & 3) ^ ((lane >> 3) & 2) : (lane & 7) ^ ((((w & 1) << 2) | (lane >> 4)) & 7);
+    const int rsub = PIPE ? 16 * w + (lane >> 2) : 8 * w + (lane >> 3);
+    // PIPE: B instructions of this wave per stage (wave-uniform; the counted waits need it as a constant per branch)
+    constexpr int NB_HI = JB, NB_LO = (BN / 16) / NWV;
+    const int nbw = (PIPE && NB_HI != NB_LO) ? (BN / 16 - w + NWV - 1) / NWV : JB;
     const unsigned char* abase = reinterpret_cast<const unsigned char*>(p.A);
     const unsigned char* bbase = reinterpret_cast<const unsigned char*>(p.B);
     const unsigned char* zero = reinterpret_cast<const unsigned char*>(g_zero_page);
@@ -342,10 +387,12 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
             kvalid = tidx < ntap;
         }
         const int* th = tabh + (ih & (TAPS - 1)) * BM + rsub;
-        const int* tw = tabw + (iw & (TAPS - 1)) * BM + rsub;
+        const tabw_t* tw = tabw + (iw & (TAPS - 1)) * BM + rsub;
 #pragma unroll
         for (int j = 0; j < JA; ++j) {
-            const int pix = th[32 * j] + tw[32 * j];
+            int col = tw[RSTR * j];
+            if (PIPE) col = col < 0 ? NN16_NOSRC : col;
+            const int pix = th[RSTR * j] + col;
             asrc[j] = (kvalid & (pix >= 0)) ? abase + (uint64_t)(unsigned)pix * ald2 : zero;
         }
         const int kh = RING ? (ih >= nrh ? ih - nrh : ih) : kh0 + ih * kstep;
@@ -353,23 +400,13 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
         const unsigned char* wt = bbase + 2 * (int64_t)(kh * g.k + kw) * p.tap_stride;
 #pragma unroll
         for (int j = 0; j < JB; ++j) {
-            const int n = n0 + 32 * j + rsub;
+            const int n = n0 + RSTR * j + rsub;
             wsrc[j] = (kvalid & (n < p.N)) ? wt + 2 * (uint64_t)((unsigned)n * (unsigned)p.C) : zero;
         }
     };
     set_tap();
-
-    // LDS-DMA through glds16_asm: the table reads of set_tap follow the DMA issue in program order, and behind the
-    // builtin the compiler would drain the queue (vmcnt(0)) in front of them; the wait before the barrier is explicit
-    auto stage = [&](int buf) {
-        const uint32_t sa = lds0 + buf * STAGE + (8 * w) * 128;
-        const uint32_t sb = sa + A_BYTES;
-        const unsigned cbyte = 16u * (unsigned)c8;
-#pragma unroll
-        for (int j = 0; j < JA; ++j) glds16_asm(asrc[j] + cbyte, sa + j * 32 * 128);
-#pragma unroll
-        for (int j = 0; j < JB; ++j) glds16_asm(wsrc[j] + cbyte, sb + j * 32 * 128);
-        c8 += 8;
+    auto advance = [&]() {               // the K cursor moves on by one stage
+        c8 += CPS;
         if (c8 >= C8) {
             do {
                 c8 -= C8;
@@ -387,6 +424,20 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
         }
     };
 
+    // LDS-DMA through glds16_asm: the table reads of set_tap follow the DMA issue in program order, and behind the
+    // builtin the compiler would drain the queue (vmcnt(0)) in front of them; the wait before the barrier is explicit
+    auto stage = [&](int buf) {
+        const uint32_t sa = lds0 + buf * STAGE + w * 1024;       // (1 KB = the rows of one instruction)
+        const uint32_t sb = sa + A_BYTES;
+        const unsigned cbyte = 16u * (unsigned)c8;
+#pragma unroll
+        for (int j = 0; j < JA; ++j) glds16_asm(asrc[j] + cbyte, sa + j * RSTR * ROWB);
+#pragma unroll
+        for (int j = 0; j < JB; ++j)
+            if (!PIPE || j < nbw) glds16_asm(wsrc[j] + cbyte, sb + j * RSTR * ROWB);
+        advance();
+    };
+
     f32x4_t acc[4][TN];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -395,6 +446,44 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
+    if constexpr (PIPE) {
+        // operand reads: lane -> row (lane & 15) of a 16-row fragment, chunk (lane >> 4) of the stage's one K block
+        const int frag = (lane & 15) * ROWB + 16 * ((lane >> 4) ^ (((lane & 15) >> 1) & 2));
+        const unsigned char* a_ad = smem + wm * 64 * ROWB + frag;
+        const unsigned char* b_ad = smem + A_BYTES + wn * 16 * TN * ROWB + frag;
+        const int nst = 2 * nsteps;                // a 64-channel K step = two stages
+        if (nst > 0) stage(0);
+        if (nst > 1) stage(1);
+        // one stage on ring slot SLOT (a compile-time constant: operand addresses = base + immediate)
+        auto kstep = [&](int it, auto slot_c) {
+            constexpr int SLOT = decltype(slot_c)::value;
+            // tile `it` has landed (this wave's part; the barrier extends that to every wave), tile it + 1 stays in flight:
+            // JA + nbw LDS-DMA instructions of this wave
+            if (it + 1 < nst) {
+                if (NB_HI == NB_LO || nbw == NB_HI) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(JA + NB_HI) : "memory");
+                else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(JA + NB_LO) : "memory");
+            } else
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (it + 2 < nst) stage((SLOT + 2) % 3);    // the slot every wave finished reading before this barrier
+            bf16x8_t a[4], b[TN];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(a_ad + SLOT * STAGE + i * 16 * ROWB);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const bf16x8_t*>(b_ad + SLOT * STAGE + j * 16 * ROWB);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+        };
+        for (int it = 0; it < nst; it += 3) {
+            kstep(it, std::integral_constant<int, 0>());
+            if (it + 1 < nst) kstep(it + 1, std::integral_constant<int, 1>());
+            if (it + 2 < nst) kstep(it + 2, std::integral_constant<int, 2>());
+        }
+        __syncthreads();                           // every wave has read its last stage: the epilogue overlays the ring
+    } else {
     // operand reads: lane -> row (lane & 15) of a 16-row fragment, chunk 4 s + (lane >> 4), swizzled by (row >> 1) & 7
     const int fsw = (lane & 15) >> 1;
     const int a_row = (wm * 64 + (lane & 15)) * 128;
@@ -434,29 +523,39 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
+    }
 
-    // ---- epilogue: accumulators -> LDS [128][BN + 4] fp32 -> whole 16-byte row segments ----
+    // ---- epilogue: accumulators -> LDS [PR][BN + 4] fp32 -> whole 16-byte row segments ----
+    // (two stages: all 128 rows at once; ring forms: the 64 rows of wave row `part` at a time, in front of the tables)
+    constexpr int PARTS = PIPE ? WM : 1, PR = BM / PARTS;
     constexpr int ELD = BN + 4;
     float* est = reinterpret_cast<float*>(smem);
     const bool partial = p.splitk > 1;
     const float alpha = (!partial && p.alpha) ? *p.alpha : 1.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int row = wm * 64 + 16 * i + (lane & 15);
-            const int col = wn * 16 * TN + 16 * j + 4 * (lane >> 4);
-            f32x4_t v = acc[i][j];
-            v[0] *= alpha; v[1] *= alpha; v[2] *= alpha; v[3] *= alpha;
-            *reinterpret_cast<f32x4_t*>(est + row * ELD + col) = v;
-        }
-    __syncthreads();
     constexpr int CPR = BN / 8;                     // 8-column chunks per row
     float* slab = partial ? p.slabs + (int64_t)zs * p.slab_stride : nullptr;
 #pragma unroll
-    for (int q = 0; q < BM * CPR / 256; ++q) {
-        const int idx = t + 256 * q;
-        const int row = idx / CPR, cc = idx - row * CPR;
+    for (int part = 0; part < PARTS; ++part) {
+    if (part > 0) __syncthreads();                  // (the previous part is stored)
+    if (!PIPE || wm == part) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int row = (PIPE ? 0 : wm * 64) + 16 * i + (lane & 15);
+                const int col = wn * 16 * TN + 16 * j + 4 * (lane >> 4);
+                f32x4_t v = acc[i][j];
+                v[0] *= alpha; v[1] *= alpha; v[2] *= alpha; v[3] *= alpha;
+                *reinterpret_cast<f32x4_t*>(est + row * ELD + col) = v;
+            }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < (PR * CPR + NTHR - 1) / NTHR; ++q) {
+        const int idx = t + NTHR * q;
+        if ((PR * CPR) % NTHR != 0 && idx >= PR * CPR) continue;
+        const int erow = idx / CPR, cc = idx - erow * CPR;
+        const int row = part * PR + erow;
         const int m = m0 + row, col = n0 + cc * 8;
         if (m >= p.M || col >= p.N) continue;
         int64_t ooff;
@@ -483,8 +582,8 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
         } else {
             ooff = (int64_t)m * p.out_ld + col;
         }
-        f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(est + row * ELD + cc * 8);
-        f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(est + row * ELD + cc * 8 + 4);
+        f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(est + erow * ELD + cc * 8);
+        f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(est + erow * ELD + cc * 8 + 4);
         if (partial) {
             *reinterpret_cast<f32x4_t*>(slab + ooff) = v0;
             *reinterpret_cast<f32x4_t*>(slab + ooff + 4) = v1;
@@ -518,6 +617,7 @@ __global__ __launch_bounds__(256, 2) void nn16_kernel(const NN16Params p) {
             r.w = pack_bf16x2(v1[2], v1[3]);
             *reinterpret_cast<uint4*>(o) = r;
         }
+    }
     }
 }
 
@@ -1572,13 +1672,53 @@ size_t nn16_workspace_bytes(const NN16Params& p, int mode, int zdim, int64_t out
 
 static int nn16_mfast(const NN16Params& p, int tiles_m, int tiles_n);
 
+// Which pipeline form of nn16_kernel a launch takes (see the kernel's header).  The forms give bit-identical results, so
+// this is a matter of speed alone; the plan (tile width, split-K) does not depend on it.
+//   tn: the plan's tile width; wide_blocks: blocks of the launch with 256-row tiles; mirrored: a mirrored-tap launch
+//   (NN16Params::ring), which has no 8-wave instantiation.
+// BG_NN16_PIPE (read per call: tests/test_gpu_nn16_pipe.py compares the forms) = 0: two stages everywhere, 1: the ring form at
+// the 128-row block wherever it applies, 2: the wide form wherever it applies; unset: the rule below.
+//
+// The rule, from the per-layer tables of profiles/nn16_pipe_ab.txt (config 3 at 256 and at 32 images, forward / input
+// gradient, ms, two stages -> wide form):
+//   C <= 192 per tap, image-major rows, a grid of at least one round of blocks (2 per CU) - the wide form:
+//       conv 96 -> 192 k3 s2 at 64^2 0.33 / 0.45 -> 0.27 / 0.39, 192 -> 384 k3 s2 at 32^2 0.20 / 0.27 -> 0.18 / 0.25, input
+//       gradients of the k4 s2 transposed convs 192 -> 96 at 64^2 0.93 -> 0.81 and 384 -> 192 at 32^2 0.65 -> 0.62, the 1 x 1
+//       convs 192 -> 96 0.14 / 0.23 -> 0.13 / 0.19, 96 -> 192 0.22 / 0.14 -> 0.19 / 0.13, 192 -> 24 input gradient 0.20 -> 0.14.
+//       These layers re-read activations, not weights: the 256-row tile halves the weight-tile traffic per row and its
+//       ring keeps two tiles in flight per block.
+//   32-column tiles (192 -> 24 forward: 0.091 -> 0.097), C >= 384 (within +-0.01 of the two-stage form at 256 images, up to
+//       20 % slower at 32, where the 256-row grid falls under one round) and position-major rows: two stages.
+//   The ring at the 128-row block is the default nowhere: where it gains (the C <= 192 layers above) the wide form gains
+//       more, and on the C >= 768 maps of 4^2 ... 8^2 it LOSES 25 - 40 % (1536 -> 1536 k3 at 8^2: 0.62 -> 0.87): those launches
+//       stream 10 - 40 MB of weights through L2 and a 32-channel stage reads only half of every 128-byte line per
+//       LDS-DMA, so each line is requested twice, one step apart - with three blocks per CU streaming 48 KB per step
+//       through the CU's 32 KB vector cache in between.  It stays behind the switch for the comparison.
+enum { NN16_FORM_TWO = 0, NN16_FORM_RING = 1, NN16_FORM_WIDE = 2 };
+static int nn16_form(const NN16Params& p, int tn, int64_t wide_blocks, bool mirrored) {
+    if (p.g.Ws >= (1 << 15)) return NN16_FORM_TWO;         // the ring forms keep the source column of a row as int16
+    // The wide form is for image-major rows only: a position-major tile walks the taps that ITS rows have sources under, so
+    // a 256-row tile would walk other taps (and split K elsewhere) than the two 128-row tiles it replaces - other sums.
+    const bool wide_ok = !mirrored && !p.posmajor;
+    if (const char* e = getenv("BG_NN16_PIPE")) {
+        const int v = atoi(e);
+        if (v == 2) return wide_ok ? NN16_FORM_WIDE : NN16_FORM_TWO;
+        return v == 1 ? NN16_FORM_RING : NN16_FORM_TWO;
+    }
+    return (wide_ok && p.C <= 192 && tn >= 2 && wide_blocks >= 512) ? NN16_FORM_WIDE : NN16_FORM_TWO;
+}
+
 // ring launches (NN16Params::ring): mirrored taps of the gradient of tf.pad(REFLECT), accumulated into dx
-template <int TN>
+template <int TN, int SLOTS = 2>
 static int launch_nn16_ring_inst(const NN16Params& p, dim3 grid, hipStream_t s) {
-    constexpr int lds = nn16_lds_bytes(TN, NN16_RING_TAPS);
-    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16_kernel<TN, GATHER_TCONV, true, true>), lds)) return BG_ERR_LAUNCH;
-    hipLaunchKernelGGL((nn16_kernel<TN, GATHER_TCONV, true, true>), grid, dim3(256), lds, s, p);
+    constexpr int lds = SLOTS == 3 ? nn16_pipe_lds_bytes(TN, 2, NN16_RING_TAPS) : nn16_lds_bytes(TN, NN16_RING_TAPS);
+    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16_kernel<TN, GATHER_TCONV, true, true, SLOTS>), lds)) return BG_ERR_LAUNCH;
+    hipLaunchKernelGGL((nn16_kernel<TN, GATHER_TCONV, true, true, SLOTS>), grid, dim3(256), lds, s, p);
     return BG_OK;
+}
+template <int TN>
+static int launch_nn16_ring_tn(const NN16Params& p, int form, dim3 grid, hipStream_t s) {
+    return form == NN16_FORM_RING ? launch_nn16_ring_inst<TN, 3>(p, grid, s) : launch_nn16_ring_inst<TN>(p, grid, s);
 }
 
 int launch_nn16_ring(NN16Params& p, hipStream_t s) {
@@ -1605,41 +1745,51 @@ int launch_nn16_ring(NN16Params& p, hipStream_t s) {
     p.tiles_n = (p.N + 32 * tn - 1) / (32 * tn);
     p.mfast = nn16_mfast(p, p.tiles_m, p.tiles_n);
     dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
+    const int form = nn16_form(p, tn, 0, true);
     int rc;
     switch (tn) {
-        case 1: rc = launch_nn16_ring_inst<1>(p, grid, s); break;
-        case 2: rc = launch_nn16_ring_inst<2>(p, grid, s); break;
-        case 3: rc = launch_nn16_ring_inst<3>(p, grid, s); break;
-        default: rc = launch_nn16_ring_inst<4>(p, grid, s); break;
+        case 1: rc = launch_nn16_ring_tn<1>(p, form, grid, s); break;
+        case 2: rc = launch_nn16_ring_tn<2>(p, form, grid, s); break;
+        case 3: rc = launch_nn16_ring_tn<3>(p, form, grid, s); break;
+        default: rc = launch_nn16_ring_tn<4>(p, form, grid, s); break;
     }
     if (rc) return rc;
     BG_LAUNCH_CHECK();
     return BG_OK;
 }
 
-template <int TN, int MODE, bool PM>
+template <int TN, int MODE, bool PM, int SLOTS = 2, int WM = 2>
 static int launch_nn16_inst(const NN16Params& p, dim3 grid, hipStream_t s) {
-    constexpr int lds = nn16_lds_bytes(TN);
+    constexpr int lds = SLOTS == 3 ? nn16_pipe_lds_bytes(TN, WM) : nn16_lds_bytes(TN);
     // > 48 KB of dynamic LDS needs the opt-in once per kernel and device
-    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16_kernel<TN, MODE, PM>), lds)) return BG_ERR_LAUNCH;
-    prof_kernel("nn16_kernel<%d, %d, %s>", TN, MODE, PM ? "true" : "false");
-    hipLaunchKernelGGL((nn16_kernel<TN, MODE, PM>), grid, dim3(256), lds, s, p);
+    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16_kernel<TN, MODE, PM, false, SLOTS, WM>), lds)) return BG_ERR_LAUNCH;
+    if (SLOTS == 2) prof_kernel("nn16_kernel<%d, %d, %s>", TN, MODE, PM ? "true" : "false");
+    else prof_kernel("nn16_kernel<%d, %d, %s, false, %d, %d>", TN, MODE, PM ? "true" : "false", SLOTS, WM);
+    hipLaunchKernelGGL((nn16_kernel<TN, MODE, PM, false, SLOTS, WM>), grid, dim3(128 * WM), lds, s, p);
     return BG_OK;
 }
 
+template <int TN, int MODE, bool PM>
+static int launch_nn16_tn(const NN16Params& p, int form, dim3 grid, hipStream_t s) {
+    if (form == NN16_FORM_RING) return launch_nn16_inst<TN, MODE, PM, 3, 2>(p, grid, s);
+    if constexpr (!PM)                             // (nn16_form: image-major rows only)
+        if (form == NN16_FORM_WIDE) return launch_nn16_inst<TN, MODE, PM, 3, 4>(p, grid, s);
+    return launch_nn16_inst<TN, MODE, PM>(p, grid, s);
+}
+
 template <int MODE, bool PM>
-static int launch_nn16_pm(const NN16Params& p, int tn, dim3 grid, hipStream_t s) {
+static int launch_nn16_pm(const NN16Params& p, int tn, int form, dim3 grid, hipStream_t s) {
     switch (tn) {
-        case 1: return launch_nn16_inst<1, MODE, PM>(p, grid, s);
-        case 2: return launch_nn16_inst<2, MODE, PM>(p, grid, s);
-        case 3: return launch_nn16_inst<3, MODE, PM>(p, grid, s);
-        default: return launch_nn16_inst<4, MODE, PM>(p, grid, s);
+        case 1: return launch_nn16_tn<1, MODE, PM>(p, form, grid, s);
+        case 2: return launch_nn16_tn<2, MODE, PM>(p, form, grid, s);
+        case 3: return launch_nn16_tn<3, MODE, PM>(p, form, grid, s);
+        default: return launch_nn16_tn<4, MODE, PM>(p, form, grid, s);
     }
 }
 
 template <int MODE>
-static int launch_nn16_mode(const NN16Params& p, int tn, dim3 grid, hipStream_t s) {
-    return p.posmajor ? launch_nn16_pm<MODE, true>(p, tn, grid, s) : launch_nn16_pm<MODE, false>(p, tn, grid, s);
+static int launch_nn16_mode(const NN16Params& p, int tn, int form, dim3 grid, hipStream_t s) {
+    return p.posmajor ? launch_nn16_pm<MODE, true>(p, tn, form, grid, s) : launch_nn16_pm<MODE, false>(p, tn, form, grid, s);
 }
 
 // ---- halo-tile form: which launches take it ----
@@ -1792,15 +1942,18 @@ int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, 
     p.slabs = reinterpret_cast<float*>(ws);
     p.slab_stride = out_elems;
     const int bn = 32 * pl.tn;
-    p.tiles_m = (p.M + NN16_BM - 1) / NN16_BM;
     p.tiles_n = (p.N + bn - 1) / bn;
+    p.posmajor = nn16_posmajor_fraction(p, mode) < 1.0;
+    // the pipeline form: by the grid the 256-row tile would leave
+    const int form = nn16_form(p, pl.tn, (int64_t)((p.M + 255) / 256) * p.tiles_n * zdim * pl.splitk, false);
+    const int bm = form == NN16_FORM_WIDE ? 256 : NN16_BM;
+    p.tiles_m = (p.M + bm - 1) / bm;
     p.pow2 = 0;
     if (p.g.Wq > 0 && p.g.Hq > 0 && (p.g.Wq & (p.g.Wq - 1)) == 0 && (p.g.Hq & (p.g.Hq - 1)) == 0) {
         p.pow2 = 1;
         p.wq_shift = __builtin_ctz(p.g.Wq);
         p.hq_shift = __builtin_ctz(p.g.Hq);
     }
-    p.posmajor = nn16_posmajor_fraction(p, mode) < 1.0;
     p.mfast = nn16_mfast(p, p.tiles_m, p.tiles_n);
     dim3 grid(p.tiles_m * p.tiles_n, 1, zdim * p.splitk);
     p.zfold = 0;
@@ -1810,9 +1963,9 @@ int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, 
     }
     int rc;
     if (mode == GATHER_CONV)
-        rc = launch_nn16_mode<GATHER_CONV>(p, pl.tn, grid, s);
+        rc = launch_nn16_mode<GATHER_CONV>(p, pl.tn, form, grid, s);
     else
-        rc = launch_nn16_mode<GATHER_TCONV>(p, pl.tn, grid, s);
+        rc = launch_nn16_mode<GATHER_TCONV>(p, pl.tn, form, grid, s);
     if (rc) return rc;
     BG_LAUNCH_CHECK();
     if (pl.splitk > 1) {
