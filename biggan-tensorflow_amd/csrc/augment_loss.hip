@@ -325,9 +325,10 @@ __global__ __launch_bounds__(AL_BLOCK) void ortho_cosine_kernel(const float* __r
 // ortho-cosine regulariser, low-rank form for wide kernels (rows < c, e.g. first/dense2 [184, 16384]):
 // with G = W W^T, s = W 1, P = G W (all O(rows^2 c)) the c x c Gram matrix is never formed:
 //   n_i^2 = q_i = w_i^T G w_i = sum_r W[r,i] P[r,i],  sum_k A[i,k] = t_i = w_i^T s,
-//   loss = kappa sum_i t_i^2/q_i + scale c / (2(c-1)),  kappa = scale (c-2) / (2(c-1))
+//   loss = kappa sum_i t_i^2/qc_i + k2 sum_i q_i/qc_i,  qc = max(q, 1e-12), kappa = scale (c-2) / (2(c-1)),
+//   k2 = scale / (2(c-1))   (q_i/qc_i = sum_j Ahat[i,j]^2: 1 unless l2_normalize clamps the row)
 //   dW = s alpha^T + (W alpha) 1^T + 2 P diag(beta) + 2 (W diag(beta) W^T) W,
-//   alpha_i = 2 kappa t_i / q_i, beta_i = -kappa t_i^2 / q_i^2
+//   alpha_i = 2 kappa t_i / qc_i, beta_i = d loss / d q_i = -kappa t_i^2 / q_i^2  (clamped: k2 / 1e-12)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(AL_BLOCK) void ortho_lowrank_cols_kernel(const float* __restrict__ W,
                                                                        const float* __restrict__ P,
@@ -360,12 +361,15 @@ __global__ __launch_bounds__(AL_BLOCK) void ortho_lowrank_cols_kernel(const floa
             t += w * s[r];
         }
         const float kappa = c > 1 ? scale * (float)(c - 2) / (2.f * (float)(c - 1)) : 0.f;
+        const float k2 = c > 1 ? scale / (2.f * (float)(c - 1)) : 0.f;
         const bool clamped = q < 1e-12f;
         const float qc = fmaxf(q, 1e-12f);
         const float a = 2.f * kappa * t / qc;
-        const float b = clamped ? 0.f : -kappa * t * t / (qc * qc);
+        // clamped (q < 1e-12): l2_normalize divides by the constant 1e-6, so sum_j Ahat[i,j]^2 = q / 1e-12 (not 1) and
+        // d/dq of the column's loss is k2 / 1e-12 (kappa t^2 / qc no longer depends on q) - as ortho_cosine_kernel has it
+        const float b = clamped ? k2 / 1e-12f : -kappa * t * t / (qc * qc);
         alpha[i] = a;
-        contrib = kappa * t * t / qc + (c > 1 ? scale / (2.f * (float)(c - 1)) * (clamped ? 0.f : 1.f) : 0.f);
+        contrib = kappa * t * t / qc + k2 * (clamped ? q / qc : 1.f);
         r = 0;
         for (; r + 8 <= rows; r += 8) {
             float wv[8];
