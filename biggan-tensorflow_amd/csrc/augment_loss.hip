@@ -274,13 +274,33 @@ __global__ __launch_bounds__(AL_BLOCK) void sigmoid_ce_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------
+// The regulariser kernels below end with one loss term per block.  Float atomics would add them in arrival order, and
+// the loss would differ in its last bit from run to run; each block stores its term in part[blockIdx.x] instead
+// (the per-device workspace of the deterministic reductions) and one block adds them in index order.  A launch of a
+// single block (part == nullptr) adds its term to the loss itself.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void loss_term(float* loss_accum, float* part, float v) {
+    if (part) part[blockIdx.x] = v;
+    else *loss_accum += v;
+}
+
+__global__ __launch_bounds__(AL_BLOCK) void loss_terms_finalize_kernel(const float* part, int n, float* loss_accum) {
+    __shared__ float sh[4];
+    float a = 0.f;
+    for (int i = threadIdx.x; i < n; i += AL_BLOCK) a += part[i];
+    a = block_sum_256(a, sh);
+    if (threadIdx.x == 0) *loss_accum += a;
+}
+
+// ------------------------------------------------------------------------------------------
 // ortho-cosine regulariser on the Gram matrix A [c,c]: one block per row
 //   Ahat = l2n_rows(A); R[i,j] = (sum_k Ahat[i,k] - Ahat[i,j]) / sqrt(c-1); loss += scale/2 sum R^2
 //   dR = scale R ; dAhat[i,j] = (sum_j' dR[i,j'] - dR[i,j]) / sqrt(c-1) ;
 //   dA[i,j] = rn_i (dAhat[i,j] - Ahat[i,j] sum_k dAhat[i,k] Ahat[i,k])   (when sum A^2 >= 1e-12)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(AL_BLOCK) void ortho_cosine_kernel(const float* __restrict__ A, float scale,
-                                                                 float* loss_accum, float* __restrict__ dA, int c) {
+                                                                 float* loss_accum, float* part, float* __restrict__ dA,
+                                                                 int c) {
     __shared__ float sh[4];
     const int i = blockIdx.x;
     const float* a = A + (int64_t)i * c;
@@ -308,7 +328,7 @@ __global__ __launch_bounds__(AL_BLOCK) void ortho_cosine_kernel(const float* __r
     s2 = block_sum_256(s2, sh);
     s1 = block_sum_256(s1, sh);
     sra = block_sum_256(sra, sh);
-    if (threadIdx.x == 0) atomicAdd(loss_accum, 0.5f * scale * s2);
+    if (threadIdx.x == 0) loss_term(loss_accum, part, 0.5f * scale * s2);
     if (!dA) return;
     // dAhat[j] = scale*isq*(s1 - R_j); T = sum_k dAhat[k]*Ahat[k] = scale*isq*(s1*r - sra)
     const float T = scale * isq * (s1 * r - sra);
@@ -335,7 +355,7 @@ __global__ __launch_bounds__(AL_BLOCK) void ortho_lowrank_cols_kernel(const floa
                                                                        const float* __restrict__ s, float scale,
                                                                        float* __restrict__ alpha,
                                                                        float* __restrict__ Wb, float* loss_accum,
-                                                                       int rows, int c) {
+                                                                       float* part, int rows, int c) {
     __shared__ float sh[4];
     const int i = blockIdx.x * AL_BLOCK + threadIdx.x;
     float contrib = 0.f;
@@ -384,7 +404,7 @@ __global__ __launch_bounds__(AL_BLOCK) void ortho_lowrank_cols_kernel(const floa
         alpha[c + i] = b;
     }
     contrib = block_sum_256(contrib, sh);
-    if (threadIdx.x == 0) atomicAdd(loss_accum, contrib);
+    if (threadIdx.x == 0) loss_term(loss_accum, part, contrib);
 }
 
 // dW = 2*T + s alpha^T + (W alpha) 1^T + 2 P diag(beta), T = (W diag(beta) W^T) W given in dW
@@ -623,7 +643,8 @@ __global__ __launch_bounds__(AL_BLOCK) void symmetrize_kernel(const float* __res
 
 // plain 'ortho' regulariser (utils.py:199-200): reg = A - I, loss = scale * l2_loss(reg), dA = scale * reg
 __global__ __launch_bounds__(AL_BLOCK) void ortho_identity_kernel(const float* __restrict__ A, float scale,
-                                                                   float* loss_accum, float* __restrict__ dA, int c) {
+                                                                   float* loss_accum, float* part, float* __restrict__ dA,
+                                                                   int c) {
     __shared__ float sh[4];
     const int64_t n = (int64_t)c * c;
     float acc = 0.f;
@@ -633,7 +654,17 @@ __global__ __launch_bounds__(AL_BLOCK) void ortho_identity_kernel(const float* _
         if (dA) dA[i] = scale * r;
     }
     acc = block_sum_256(acc, sh);
-    if (threadIdx.x == 0) atomicAdd(loss_accum, 0.5f * scale * acc);
+    if (threadIdx.x == 0) loss_term(loss_accum, part, 0.5f * scale * acc);
+}
+
+// the partial-term workspace of a launch of `grid` blocks (nullptr for one block); false: no workspace, the error is set
+static bool loss_terms_begin(int grid, hipStream_t s, float** part) {
+    *part = grid > 1 ? colreduce_workspace((size_t)grid, s) : nullptr;
+    return grid <= 1 || *part;
+}
+
+static void loss_terms_end(const float* part, int grid, float* loss_accum, hipStream_t s) {
+    if (part) hipLaunchKernelGGL(loss_terms_finalize_kernel, dim3(1), dim3(AL_BLOCK), 0, s, part, grid, loss_accum);
 }
 
 }  // namespace bg
@@ -756,8 +787,12 @@ int bg_sigmoid_ce(const float* logits, const float* truth, const float* weights,
 int bg_ortho_lowrank_cols(const float* W, const float* P, const float* s, float scale, float* alpha_beta, float* Wb,
                           float* loss_accum, int rows, int c, void* stream) {
     BG_REQUIRE(W && P && s && alpha_beta && Wb && loss_accum && rows > 0 && c > 0, "bg_ortho_lowrank_cols: bad argument");
-    hipLaunchKernelGGL(ortho_lowrank_cols_kernel, dim3((c + AL_BLOCK - 1) / AL_BLOCK), dim3(AL_BLOCK), 0,
-                       as_stream(stream), W, P, s, scale, alpha_beta, Wb, loss_accum, rows, c);
+    const int grid = (c + AL_BLOCK - 1) / AL_BLOCK;
+    float* part;
+    if (!loss_terms_begin(grid, as_stream(stream), &part)) return BG_ERR_LAUNCH;
+    hipLaunchKernelGGL(ortho_lowrank_cols_kernel, dim3(grid), dim3(AL_BLOCK), 0, as_stream(stream), W, P, s, scale,
+                       alpha_beta, Wb, loss_accum, part, rows, c);
+    loss_terms_end(part, grid, loss_accum, as_stream(stream));
     BG_LAUNCH_CHECK();
     return BG_OK;
 }
@@ -775,7 +810,11 @@ int bg_ortho_lowrank_finish(float* dW, const float* P, const float* s, const flo
 
 int bg_ortho_cosine_fwd_bwd(const float* A, float scale, float* loss_accum, float* dA, int c, void* stream) {
     BG_REQUIRE(A && loss_accum && c > 0, "bg_ortho_cosine_fwd_bwd: bad argument");
-    hipLaunchKernelGGL(ortho_cosine_kernel, dim3(c), dim3(AL_BLOCK), 0, as_stream(stream), A, scale, loss_accum, dA, c);
+    float* part;
+    if (!loss_terms_begin(c, as_stream(stream), &part)) return BG_ERR_LAUNCH;
+    hipLaunchKernelGGL(ortho_cosine_kernel, dim3(c), dim3(AL_BLOCK), 0, as_stream(stream), A, scale, loss_accum, part, dA,
+                       c);
+    loss_terms_end(part, c, loss_accum, as_stream(stream));
     BG_LAUNCH_CHECK();
     return BG_OK;
 }
@@ -855,8 +894,11 @@ int bg_ortho_identity_fwd_bwd(const float* A, float scale, float* loss_accum, fl
     BG_REQUIRE(A && loss_accum && c > 0, "bg_ortho_identity_fwd_bwd: bad argument");
     int64_t blocks = ((int64_t)c * c + AL_BLOCK - 1) / AL_BLOCK;
     if (blocks > 256) blocks = 256;
+    float* part;
+    if (!loss_terms_begin((int)blocks, as_stream(stream), &part)) return BG_ERR_LAUNCH;
     hipLaunchKernelGGL(ortho_identity_kernel, dim3((unsigned)blocks), dim3(AL_BLOCK), 0, as_stream(stream), A, scale,
-                       loss_accum, dA, c);
+                       loss_accum, part, dA, c);
+    loss_terms_end(part, (int)blocks, loss_accum, as_stream(stream));
     BG_LAUNCH_CHECK();
     return BG_OK;
 }

@@ -165,6 +165,138 @@ def deflate_compact(slots, table, records, out, seg_off, totals):
     return out
 
 
+# ---- sliced Wasserstein distance (csrc/swd.hip; metrics.py drives them).  No autograd anywhere. ----
+SWD_PATCHES, SWD_TAPS = 128, 49
+
+
+def _swd_images(op, x, dtypes=(torch.float32, torch.bfloat16)):
+    if x.dim() != 4 or x.shape[1] != x.shape[2] or x.dtype not in dtypes:
+        raise RuntimeError("%s: images must be [B,H,H,C] %s, got %s %s"
+                           % (op, " or ".join(str(d) for d in dtypes), x.dtype, tuple(x.shape)))
+    return _c(x.detach())
+
+
+def _swd_typed(op, name, t, dtype, shape):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be a contiguous %s %s, got %s %s" % (op, name, dtype, tuple(shape), t.dtype,
+                                                                            tuple(t.shape)))
+    return hip.ptr(t)
+
+
+def swd_pyr_down(x, out=None):
+    """One Gaussian-pyramid step: x [B,H,H,C] fp32 or bf16 -> fp32 [B,H/2,H/2,C], the 5-tap binomial blur with the mirror
+    boundary, every second pixel."""
+    x = _swd_images("swd_pyr_down", x)
+    B, H, _, C = x.shape
+    if out is None:
+        out = torch.empty(B, H // 2, H // 2, C, dtype=torch.float32, device=x.device)
+    po = _swd_typed("swd_pyr_down", "out", out, torch.float32, (B, H // 2, H // 2, C))
+    check(lib().bg_swd_pyr_down(act(x), dt(x), po, B, H, C, stream()))
+    return out
+
+
+def swd_pyr_lap(g, g1, out=None):
+    """One Laplacian level: g [B,H,H,C] fp32 or bf16 minus the up-sampled g1 fp32 [B,H/2,H/2,C] -> fp32 [B,H,H,C]."""
+    g = _swd_images("swd_pyr_lap", g)
+    B, H, _, C = g.shape
+    p1 = _swd_typed("swd_pyr_lap", "g1", g1, torch.float32, (B, H // 2, H // 2, C))
+    if out is None:
+        out = torch.empty(B, H, H, C, dtype=torch.float32, device=g.device)
+    po = _swd_typed("swd_pyr_lap", "out", out, torch.float32, (B, H, H, C))
+    check(lib().bg_swd_pyr_lap(act(g), dt(g), p1, po, B, H, C, stream()))
+    return out
+
+
+def swd_partials(n_images, C, device):
+    """The fp64 buffer [n_images, C, 2] that ``swd_descriptors`` fills and ``swd_stats`` reduces."""
+    nb = int(lib().bg_swd_stats_workspace_bytes(int(n_images), int(C)))
+    return torch.zeros(nb // 8, dtype=torch.float64, device=device).view(int(n_images), int(C), 2)
+
+
+def swd_descriptors(x, pos, desc, row_offset, partials):
+    """128 patches of 7 x 7 per image of x fp32 [B,H,H,C] at the centres pos int32 [B,128,2] = (y, x) -> rows
+    ``row_offset + b * 128 + k`` of desc fp32 [N, 49 C] in [c, dy, dx] order, and the images' rows of ``partials``.
+    A centre outside [3, H-4] gives a zero row."""
+    x = _swd_images("swd_descriptors", x, (torch.float32,))
+    B, H, _, C = x.shape
+    pp = _swd_typed("swd_descriptors", "pos", pos, torch.int32, (B, SWD_PATCHES, 2))
+    if desc.dim() != 2:
+        raise RuntimeError("swd_descriptors: desc must be [N, %d], got %s" % (SWD_TAPS * C, tuple(desc.shape)))
+    n_rows = desc.shape[0]
+    pd = _swd_typed("swd_descriptors", "desc", desc, torch.float32, (n_rows, SWD_TAPS * C))
+    pw = _swd_typed("swd_descriptors", "partials", partials, torch.float64, (n_rows // SWD_PATCHES, C, 2))
+    check(lib().bg_swd_descriptors(f32(x), pp, B, H, C, pd, n_rows, int(row_offset), pw, partials.numel() * 8, stream()))
+    return desc
+
+
+def swd_stats(partials, out=None):
+    """partials fp64 [n_images, C, 2] -> fp64 [C, 2]: per channel the mean and the reciprocal of the biased standard
+    deviation of the set's descriptor values (0 for a channel without deviation), added in a fixed order."""
+    if partials.dim() != 3:
+        raise RuntimeError("swd_stats: partials must be [n_images, C, 2], got %s" % (tuple(partials.shape),))
+    n_images, C, _ = partials.shape
+    pw = _swd_typed("swd_stats", "partials", partials, torch.float64, (n_images, C, 2))
+    if out is None:
+        out = torch.empty(C, 2, dtype=torch.float64, device=partials.device)
+    po = _swd_typed("swd_stats", "out", out, torch.float64, (C, 2))
+    check(lib().bg_swd_stats_finish(pw, partials.numel() * 8, n_images, C, po, stream()))
+    return out
+
+
+def swd_project(desc_a, stats_a, dirs, out, desc_b=None, stats_b=None):
+    """Normalised descriptors times directions: out[set * S + s][n] for set a and, when given, set b.  desc fp32 [N, K],
+    stats fp64 [K / 49, 2], dirs fp32 [K, S], out fp32 [sets * S, N]."""
+    if desc_a.dim() != 2 or desc_a.shape[1] % SWD_TAPS:
+        raise RuntimeError("swd_project: desc must be [N, 49 C], got %s" % (tuple(desc_a.shape),))
+    N, K = desc_a.shape
+    C = K // SWD_TAPS
+    if dirs.dim() != 2:
+        raise RuntimeError("swd_project: dirs must be [%d, S], got %s" % (K, tuple(dirs.shape)))
+    S_ = dirs.shape[1]
+    sets = 1 if desc_b is None else 2
+    ptrs = []
+    for name, d, s in (("a", desc_a, stats_a), ("b", desc_b, stats_b))[:sets]:
+        ptrs += [_swd_typed("swd_project", "desc_" + name, d, torch.float32, (N, K)),
+                 _swd_typed("swd_project", "stats_" + name, s, torch.float64, (C, 2))]
+    if sets == 1:
+        ptrs += [None, None]
+    pdir = _swd_typed("swd_project", "dirs", dirs, torch.float32, (K, S_))
+    po = _swd_typed("swd_project", "out", out, torch.float32, (sets * S_, N))
+    check(lib().bg_swd_project(ptrs[0], ptrs[1], ptrs[2], ptrs[3], pdir, po, N, C, S_, stream()))
+    return out
+
+
+def swd_sort_tile():
+    """Floats of the sort's LDS tile (segments up to this length sort in one launch)."""
+    return int(lib().bg_swd_sort_tile())
+
+
+def swd_sort_segments(data, seg_len):
+    """Sort the adjacent segments of ``seg_len`` floats (a power of two) of the contiguous fp32 tensor ``data`` ascending,
+    in place."""
+    if data.dtype != torch.float32 or not data.is_contiguous() or data.numel() % int(seg_len) or data.numel() == 0:
+        raise RuntimeError("swd_sort_segments: data must be contiguous fp32 with a multiple of %d elements, got %s %s"
+                           % (seg_len, data.dtype, tuple(data.shape)))
+    check(lib().bg_swd_sort_segments(f32(data), data.numel() // int(seg_len), int(seg_len), stream()))
+    return data
+
+
+def swd_l1(a, b, n_out=1, out=None):
+    """fp64 [n_out]: sum |a - b| over each of the n_out equal, contiguous parts of the fp32 tensors a and b."""
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel() or a.numel() % int(n_out) \
+            or a.numel() == 0 or not a.is_contiguous() or not b.is_contiguous():
+        raise RuntimeError("swd_l1: a and b must be contiguous fp32 of one size, a multiple of %d, got %s %s and %s %s"
+                           % (n_out, a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    n = a.numel() // int(n_out)
+    nb = int(lib().bg_swd_l1_workspace_bytes(n, int(n_out)))
+    ws = torch.empty(nb // 8, dtype=torch.float64, device=a.device)
+    if out is None:
+        out = torch.empty(int(n_out), dtype=torch.float64, device=a.device)
+    po = _swd_typed("swd_l1", "out", out, torch.float64, (int(n_out),))
+    check(lib().bg_swd_l1(f32(a), f32(b), n, int(n_out), po, hip.ptr(ws), nb, stream()))
+    return out
+
+
 def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
     the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns

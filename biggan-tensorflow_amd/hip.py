@@ -271,6 +271,16 @@ SIGNATURES = {
     "bg_var_hist_plan": (c_int, [_P, c_int, _P, c_size_t]),
     "bg_var_hist_workspace_bytes": (c_size_t, [c_int, c_int]),
     "bg_var_hist": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "bg_swd_pyr_down": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P]),
+    "bg_swd_pyr_lap": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "bg_swd_stats_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "bg_swd_descriptors": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int64, c_int64, _P, c_size_t, _P]),
+    "bg_swd_stats_finish": (c_int, [_P, c_size_t, c_int, c_int, _P, _P]),
+    "bg_swd_project": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
+    "bg_swd_sort_tile": (c_size_t, []),
+    "bg_swd_sort_segments": (c_int, [_P, c_int, c_int, _P]),
+    "bg_swd_l1_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "bg_swd_l1": (c_int, [_P, _P, c_int64, c_int, _P, _P, c_size_t, _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

@@ -60,7 +60,10 @@ FLAGS = [
 #               bf16        BASELINE configs 3-5: bf16-resident activations + packed bf16 weights, fp32 accumulate,
 #                           fp32 master weights / optimiser / statistics
 #   the default can also be given by the environment variable BIGGAN_PRECISION
-EXTRA_FLAGS = [("precision", T, None)]
+#   --swd_freq N            every N iterations: the sliced Wasserstein scores of the generator (metrics.py) as scalars in
+#                           the event file and one "SWD: ..." line; 0 (default) is off.  --phase test: computed once
+#   --swd_images M          images per set, rounded down to a power of two (and to the number of dataset files)
+EXTRA_FLAGS = [("precision", T, None), ("swd_freq", I, 0), ("swd_images", I, 2048)]
 
 
 def build_parser():

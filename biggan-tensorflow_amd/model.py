@@ -173,6 +173,10 @@ class BigGAN(GANBase):
         self.labels = None                     # the dataset's label table (open_dataset); None: synthetic one-hots
         self.label_table = None                # the same table as a device fp32 [rows, n_labels] (draw_labels)
         self._static_set = None                # (z, class vectors) of the static sample set, drawn on first use
+        # in-training quality score (extension flags --swd_freq / --swd_images; metrics.py)
+        self.swd_freq = int(getattr(args, "swd_freq", 0) or 0)
+        self.swd_images = int(getattr(args, "swd_images", 2048) or 2048)
+        self._swd = None                       # metrics.Swd with the kept real set, built at the first event
         self.recon_plan = self._recon_plan()
         self.deep = args.deep                                                          # BigGAN.py:20
         self.g_mixed_resblocks = args.g_mixed_resblocks                                # BigGAN.py:40-41
@@ -1553,6 +1557,13 @@ class BigGAN(GANBase):
                         self._log_writer.flush()
                 if samples and (idx + 1) % self.print_freq == 0:                      # BigGAN.py:1125
                     self.save_samples(epoch, idx + 1)
+                if self.swd_freq > 0 and self.counter % self.swd_freq == 0:
+                    scores = self.swd()                                                # (collective: every rank enters)
+                    if self.rank == 0:
+                        from .metrics import format_scores
+                        print("SWD: " + format_scores(scores), flush=True)
+                        if self._log_writer is not None:
+                            self._log_writer.add_scalars(self.counter - 1, scores)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
             if self._log_writer is not None:
@@ -1623,7 +1634,7 @@ class BigGAN(GANBase):
         return [self.store.vars[u] for w, u in self.store.sn_pairs.items() if w.startswith("discriminator/")]
 
     def generate(self, z, cls_z=None, ema=True, grid=None, gh=0, gw=0, _synced=False, with_discriminator=False,
-                 _place=None):
+                 _place=None, _consume=None):
         """BigGAN.py:1397-1445: images of a list of latents (and class vectors; None
         with --n_labels: zeros).  The list is padded to a multiple of ``batch_size`` by repeating entry 0 and runs
         ``batch_size`` at a time with is_training=False; ``ema`` reads the trainables from their moving averages,
@@ -1643,7 +1654,8 @@ class BigGAN(GANBase):
         rows would then move the answer and the moving statistics, so this pass reads the population statistics.)
         ``_place`` (the sampling service): ``(table int32 [padded n, 4], arena uint8 [bytes])`` on the device - each
         batch goes through ``functional.image_place_u8`` with its rows of the table instead of being kept, and the arena
-        takes the place of the images in the result."""
+        takes the place of the images in the result.  ``_consume`` (the quality score): a callable that takes each batch of
+        images, padding included, as it is produced; nothing is kept and the result is None."""
         import numpy as np
 
         def dev(a, width):
@@ -1701,7 +1713,9 @@ class BigGAN(GANBase):
                     if with_discriminator:
                         for k, v in self.discriminator(img, is_training=False, reuse=True).items():
                             d_out.setdefault(k, []).append(v.float())
-                    if _place is not None:
+                    if _consume is not None:
+                        _consume(img)
+                    elif _place is not None:
                         Fn.image_place_u8(img, _place[0][b:b + B], _place[1])
                     elif grid is not None:
                         Fn.image_tiles_u8(img, grid, gh, gw, tile0=b)
@@ -1714,7 +1728,8 @@ class BigGAN(GANBase):
                     torch._foreach_copy_(u_live, u_saved)
                 if live is not None:
                     arena.params.copy_(live)
-        res = _place[1] if _place is not None else grid if grid is not None else torch.cat(out)[:n]
+        res = None if _consume is not None else (_place[1] if _place is not None else grid if grid is not None
+                                                 else torch.cat(out)[:n])
         if with_discriminator:
             return res, {k: torch.cat(v)[:n] for k, v in d_out.items()}
         return res
@@ -1803,9 +1818,81 @@ class BigGAN(GANBase):
             write(Sp.sample_names(self.model_name, epoch, idx, tag)["cls"], zs[:dim * dim], cls_z, True, dim)
         return paths
 
+    # ---- in-training quality score (metrics.py) -------------------------------------------------
+    def swd_real_batches(self, plan, root="./dataset"):
+        """The real set of the quality score, ``batch_size`` images at a time on the device: with a dataset folder the
+        first ``plan.n_images`` files of the listing, decoded and resized by the host path without flips (never taken from
+        the training loader); without one, uniform noise from a generator of the metric's own."""
+        B, M = self.batch_size, plan.n_images
+        if plan.from_files:
+            import numpy as np
+            from . import data as D
+            image_data = D.ImageData(self.img_size, self.c_dim, True, False)
+            files = self._swd_files(root)[:M]
+            for lo in range(0, M, B):
+                yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in files[lo:lo + B]])).to(self.device)
+        else:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(plan.seeds["real"])
+            for lo in range(0, M, B):
+                yield torch.rand(min(B, M - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
+                                 generator=gen) * 2.0 - 1.0
+
+    def _swd_files(self, root="./dataset"):
+        """The dataset's file listing (None without a dataset folder), as the training loader would list it."""
+        from . import data as D
+        if not os.path.isdir(os.path.join(root, self.dataset_name)):
+            return None
+        files, _ = D.load_data(self.dataset_name, self.args.label_file, self.args.weight_file,
+                               ignore_missing=self.args.ignore_missing_labels, n_labels=self.n_labels, root=root)
+        return list(files)
+
+    def swd_plan(self, root="./dataset"):
+        from .metrics import SwdPlan
+        files = self._swd_files(root)
+        return SwdPlan(self.img_size, self.c_dim, self.batch_size, self.swd_images, self.static_sample_seed,
+                       n_files=None if files is None else len(files))
+
+    def swd_fake_inputs(self, plan):
+        """(latents [n,1,1,z_dim], class vectors [n,n_labels] or None) of the fake set: drawn from the plan's seeds, with
+        --z_trunc_train's truncation and rows of the label table, the same at every event."""
+        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
+        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
+
+    def swd(self, root="./dataset"):
+        """The sliced Wasserstein scores of the current weights: {``swd_<side>``: 1e3 x distance per pyramid level,
+        ``swd_avg``: their mean} for the moving averages and / or ``swd_noema_*`` for the live weights, as --sample_ema
+        says.  The real set's descriptors are computed at the first call and kept; the fake set is regenerated through
+        ``generate`` a batch at a time from latents drawn once.  Every rank calls it (``sync_sharded_state`` is
+        collective); rank 0 computes, the others return {}.  Nothing the training run reads is changed."""
+        from . import metrics
+        self.sync_sharded_state()
+        if self.rank != 0:
+            return {}
+        with torch.no_grad():
+            if self._swd is None:
+                plan = self.swd_plan(root)
+                m = metrics.Swd(plan, self.device)
+                m.begin("real")
+                for batch in self.swd_real_batches(plan, root):
+                    m.add(batch)
+                m.real = m.finish()
+                m.fake_inputs = self.swd_fake_inputs(plan)
+                self._swd = m
+            m = self._swd
+            out = {}
+            for prefix, ema, wanted in (("swd", True, self.generate_ema_samples),
+                                        ("swd_noema", False, self.generate_noema_samples)):
+                if wanted:
+                    m.begin("fake")
+                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
+                    out.update(m.scores(m.finish(), prefix))
+        return out
+
     def test(self):
         """--phase test (BigGAN.py:1372-1395): load the latest checkpoint and write ``test_num`` grids of
-        floor(sqrt(min(sample_num, batch_size)))^2 EMA samples to ``<result_dir>/<model_dir>/``."""
+        floor(sqrt(min(sample_num, batch_size)))^2 EMA samples to ``<result_dir>/<model_dir>/``.  With --swd_freq > 0 the
+        checkpoint's quality scores are printed and written to ``swd.txt`` beside them."""
         import numpy as np
         from .utils import save_images, check_folder
         could_load, _ = self.load(self.checkpoint_dir)
@@ -1819,6 +1906,14 @@ class BigGAN(GANBase):
             samples = self.sample(B=self.batch_size).detach().cpu().numpy()
             paths.append(save_images(samples[:dim * dim, :, :, :], [dim, dim],
                                      result_dir + '/' + self.model_name + '_test_{}.png'.format(i)))
+        if self.swd_freq > 0:
+            from .metrics import format_scores
+            scores = self.swd()
+            if self.rank == 0:
+                print("SWD: " + format_scores(scores), flush=True)
+                with open(os.path.join(result_dir, "swd.txt"), "w") as f:
+                    for k, v in scores.items():
+                        f.write("%s\t%.6f\n" % (k, v))
         return paths
 
     # ---- --phase service (BigGAN.py:1298-1369) -----------------------------------------------

@@ -986,6 +986,48 @@ int    bg_var_hist(const void* plan, int n_items, int n_chunks, const double* li
                    double* stats, void* ws, size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance on Laplacian-pyramid patches (Karras et al. 2018, section 5; csrc/swd.hip, metrics.py; an
+ * addition to ABI 10: new symbols only).  NHWC images with H = W a power of two, C in {1, 3, 4}.  Every launcher is
+ * stream-ordered and allocates nothing; every sum goes through partial rows added in index order (no float atomics), so
+ * a repeated launch is bit-identical.  BG_ERR_ARG with a message for a NULL pointer, a bad dtype or a bad size.
+ *
+ * bg_swd_pyr_down: x [B,H,H,C] (BG_F32 / BG_BF16) -> y fp32 [B,H/2,H/2,C] = conv(x, f (x) f / 256)[::2, ::2] with
+ *   f = [1 4 6 4 1] and the mirror boundary that does not repeat the edge (d c b | a b c d | c b a); H >= 32.
+ * bg_swd_pyr_lap: y fp32 [B,H,H,C] = g - up(g1), g [B,H,H,C] (BG_F32 / BG_BF16), g1 fp32 [B,H/2,H/2,C]; up puts g1 on the
+ *   even points of a zero [2h,2h] image and convolves it with 4 x the filter, mirror boundary on the 2h grid.  Both
+ *   kernels add their 25 taps in row-major tap order, each term one fp32 fma.
+ * bg_swd_descriptors: 128 patches of 7 x 7 per image of x fp32 [B,H,H,C], centres pos int32 [B,128,2] = (y, x) on the
+ *   device -> rows row_offset + b * 128 + k of desc fp32 [n_rows, 49 C], a row holding the patch in [c, dy, dx] order, and
+ *   partials[row_offset / 128 + b][c] = (sum, sum of squares) of the image's values of channel c in fp64.  partials:
+ *   bg_swd_stats_workspace_bytes(n_rows / 128, C) bytes.  n_rows and row_offset are multiples of 128.  The library cannot
+ *   read the table: a centre outside [3, H-4] writes a zero row.
+ * bg_swd_stats_finish: stats[c] = (mean, 1 / biased standard deviation) in fp64 over the n_images * 128 * 49 values of
+ *   channel c; a channel without deviation gets 0 for the reciprocal, which makes its normalised descriptors zero.
+ * bg_swd_project: out[set * S + s][n] = sum over k ascending of fp32(((double)desc[n][k] - mean) * rstd) * dirs[k][s] in
+ *   fp32 fma; dirs fp32 [49 C, S]; out fp32 [sets * S][N], one contiguous segment per direction.  desc_b / stats_b NULL:
+ *   one set; otherwise set 1 follows set 0 in out.  N is a multiple of 64; out is 16-byte aligned.
+ * bg_swd_sort_segments: sorts n_seg adjacent segments of seg_len floats (a power of two from 2 to 2^24) ascending, in
+ *   place, by a bitonic network: the exchange distances below bg_swd_sort_tile() floats run inside LDS, one launch per
+ *   merge size past the tile, the longer distances as passes over global memory, up to three distances a pass.  +-inf sort
+ *   correctly; NaN is not handled.  Segments of a tile or more need 16-byte aligned data.
+ * bg_swd_l1: out[i] = sum over j < n_per_out of |a[i * n_per_out + j] - b[i * n_per_out + j]|, differences and sums in
+ *   fp64; ws of bg_swd_l1_workspace_bytes(n_per_out, n_out) bytes, 8-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int    bg_swd_pyr_down(const void* x, int x_dtype, float* y, int B, int H, int C, void* stream);
+int    bg_swd_pyr_lap(const void* g, int g_dtype, const float* g1, float* y, int B, int H, int C, void* stream);
+size_t bg_swd_stats_workspace_bytes(int n_images, int C);
+int    bg_swd_descriptors(const float* x, const int32_t* pos, int B, int H, int C, float* desc, int64_t n_rows,
+                          int64_t row_offset, double* partials, size_t partials_bytes, void* stream);
+int    bg_swd_stats_finish(const double* partials, size_t partials_bytes, int n_images, int C, double* stats, void* stream);
+int    bg_swd_project(const float* desc_a, const double* stats_a, const float* desc_b, const double* stats_b,
+                      const float* dirs, float* out, int64_t N, int C, int S, void* stream);
+size_t bg_swd_sort_tile(void);
+int    bg_swd_sort_segments(float* data, int n_seg, int seg_len, void* stream);
+size_t bg_swd_l1_workspace_bytes(int64_t n_per_out, int n_out);
+int    bg_swd_l1(const float* a, const float* b, int64_t n_per_out, int n_out, double* out, void* ws, size_t ws_bytes,
+                 void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
  * (conv / deconv / gemm families) is bracketed by hipEvents on its stream.
  * bg_prof_collect synchronises the events and returns totals since the last reset.
