@@ -11,7 +11,9 @@
 //
 //   nn16_kernel  out[m, n] = sum_tap sum_c A(pixel(m), tap)[c] * B[tap][n][c]        (forward, input gradients)
 //       block tile 128 x (32*TN) x 64, 4 waves (2 x 2), v_mfma_f32_16x16x32_bf16, fp32 accumulate (this is the two-stage
-//       form; SLOTS = 3: a ring of 32-channel stages under the same or a 256-row tile, see the kernel's header).
+//       form; SLOTS = 3: a ring of 32-channel stages under the same or a 256-row tile; SLOTS = 2 with WM = 4: the phased
+//       form, a 256 x 32 TN tile (TN = 4, 6, 8) on 8 waves at one block per CU whose LDS-DMA prefetch stays in flight across
+//       raw barriers - the C >= 384 launches; see the kernel's header).
 //       LDS image: rows of 64 bf16 (128 B); 16-byte chunk c of row r is stored at chunk position c ^ ((r >> 1) & 7):
 //       LDS-DMA writes are lane-linear, so the swizzle is applied to the SOURCE chunk each lane fetches, and the
 //       ds_read_b128 operand reads (lane -> row lane & 15, chunk lane >> 4) are bank-conflict free.
@@ -105,6 +107,11 @@ constexpr int nn16_pipe_lds_bytes(int TN, int WM, int TAPS = NN16_TAPS) {
     const int bm = 64 * WM;
     return 3 * (bm + 32 * TN) * 64 + TAPS * bm * (4 + 2) + bm * 4 + 16;
 }
+// phased form (SLOTS = 2, WM = 4): two 64-channel stages of a 256 x 32 TN tile, int32 row tables, tabo, the tap flags; the
+// epilogue passes through the front in two parts of 128 rows
+constexpr int nn16x_lds_bytes(int TN) {
+    return 2 * (256 + 32 * TN) * 128 + 2 * NN16_TAPS * 256 * 4 + 256 * 4 + 16;
+}
 constexpr int NN16_NOSRC = -(1 << 30);                         // table entry of a tap without a source pixel
 
 // element offset of the source pixel of row r under tap (kh, kw), or -1 (selects, no divergent branches)
@@ -188,30 +195,45 @@ __device__ __forceinline__ RowPos nn16_row(const NN16Params& p, int m, int ph, i
 //       52.7 KB of LDS (the epilogue goes through LDS in halves) let three blocks share a CU.
 //   SLOTS = 3, WM = 4  the same ring under a 256 x 32 TN tile on 8 waves (2 A + <= 1 B LDS-DMA per wave and stage): a quarter
 //       fewer L2 -> LDS bytes per FLOP; two blocks per CU, <= 128 VGPRs.
+//   SLOTS = 2, WM = 4  the phased form: a 256 x 32 TN tile (TN = 4, 6, 8) on 8 waves, ONE block per CU (<= 250 VGPRs, 107 -
+//       140 KB of LDS), two 64-channel stages that keep whole 128-byte lines (the two-stage form's chunk swizzle), filled
+//       half by half (A rows 0 - 127 / 128 - 255, B columns below / from BN / 2) by LDS-DMA that stays in flight across raw
+//       barriers.  A K tile is four phases, one accumulator quadrant each: {ds_read_b128 fragments ; one half of prefetch ;
+//       s_barrier ; lgkmcnt(0) ; s_setprio(1) ; MFMAs ; s_setprio(0) ; s_barrier}, with ONE counted vmcnt per tile - the
+//       schedule and its read-after-write / write-after-read argument stand at the loop.  Row tables, K cursor (set_tap /
+//       advance), zero page, tap mask and the epilogue in parts are the two-stage form's own code.
 // Every form feeds an accumulator the same sequence of 32-channel MFMA K blocks (the split-K partition stays in 64-channel
 // steps = two stages), so their results are bit-identical.
 // Measured (profiles/nn16_pipe_ab.txt; 384 -> 384 at 32^2 on this kernel, 256 images): mfma_busy 0.495 with two stages, 0.414
 // with the 128-row ring, 0.530 with the wide form; no LDS bank conflicts in any.  The 64-byte rows cost more than the deeper
 // pipeline buys wherever weights stream (each 128-byte line is requested twice, a step apart: the CU's L2 read requests
-// double), so the 128-row ring is a default nowhere and the wide form takes the image-major launches with C <= 192 - see
-// nn16_form for the per-layer numbers.
+// double), so the 128-row ring is a default nowhere and the wide form takes the image-major launches with C <= 192; the
+// phased form takes the C >= 384 launches whose one-block-per-CU grid comes out in whole rounds (profiles/nn16x_phase_ab.txt:
+// 1536 -> 768 k4 s2 at 8^2 0.64 -> 0.47 ms at BN = 256, 1536 -> 1536 k3 at 8^2 0.617 -> 0.566 at BN = 192) - see nn16_form for
+// the per-layer numbers.
 template <int TN, int MODE, bool PM, bool RING = false, int SLOTS = 2, int WM = 2>
 __global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void nn16_kernel(const NN16Params p) {
     static_assert(!RING || (PM && MODE == GATHER_TCONV), "ring launches are position-major transposed gathers");
-    static_assert((SLOTS == 2 && WM == 2) || (SLOTS == 3 && (WM == 2 || WM == 4)), "two stages, or a 3-slot ring on 4 / 8 waves");
+    static_assert((SLOTS == 2 && (WM == 2 || WM == 4)) || (SLOTS == 3 && (WM == 2 || WM == 4)),
+                  "two stages (WM = 4: the phased form), or a 3-slot ring on 4 / 8 waves");
     constexpr bool PIPE = SLOTS == 3;
+    constexpr bool PHASED = SLOTS == 2 && WM == 4;
+    static_assert(!PHASED || (!RING && (TN == 4 || TN == 6 || TN == 8)), "phased form: 128, 192 or 256 columns, no mirrored taps");
+    static_assert(PHASED || TN <= 4, "tiles of at most 128 columns");
     constexpr int TAPS = RING ? NN16_RING_TAPS : NN16_TAPS;
-    constexpr int LDS_BYTES = PIPE ? nn16_pipe_lds_bytes(TN, WM, TAPS) : nn16_lds_bytes(TN, TAPS);
+    constexpr int LDS_BYTES = PIPE ? nn16_pipe_lds_bytes(TN, WM, TAPS) : (PHASED ? nn16x_lds_bytes(TN) : nn16_lds_bytes(TN, TAPS));
     typedef typename std::conditional<RING, uint64_t, unsigned>::type mask_t;
     typedef typename std::conditional<PIPE, int16_t, int>::type tabw_t;     // column table entries (source column, < 0: none)
     constexpr int BM = 64 * WM, BN = 32 * TN, NTHR = 128 * WM, NWV = 2 * WM;
     constexpr int CPS = PIPE ? 4 : 8;              // 16-byte chunks of K per stage = per LDS row
     constexpr int ROWB = 16 * CPS;                 // bytes of an LDS row
-    constexpr int RSTR = PIPE ? 16 * NWV : 32;     // rows between the LDS-DMA instructions of a wave (1 KB = 1024 / ROWB rows each)
+    constexpr int RSTR = PIPE ? 16 * NWV : 8 * NWV;     // rows between the LDS-DMA instructions of a wave (1 KB = 1024 / ROWB rows each)
     // LDS-DMA instructions per wave and stage; PIPE: wave w stages the 16-row groups w, w + NWV, ... below BN / 16
-    constexpr int JA = BM / RSTR, JB = PIPE ? (BN / 16 + NWV - 1) / NWV : BN / 32;
+    constexpr int JA = BM / RSTR, JB = PIPE ? (BN / 16 + NWV - 1) / NWV : (PHASED ? 2 * ((BN / 2 + 63) / 64) : BN / RSTR);
     constexpr int A_BYTES = BM * ROWB, STAGE = (BM + BN) * ROWB;
-    static_assert(BM == NN16_BM || PIPE, "the two-stage form has 128-row tiles");
+    static_assert(BM == NN16_BM || PIPE || PHASED, "the two-stage form has 128-row tiles");
+    static_assert(!PHASED || (LDS_BYTES <= 160 * 1024 && 128 * (BN + 4) * 4 <= LDS_BYTES - 16 - BM * 4),
+                  "phased form: one block per CU; a 128-row part of the epilogue ends in front of tabo");
     static_assert(A_BYTES % 1024 == 0 && STAGE % 1024 == 0 && (RSTR * ROWB) % 1024 == 0,
                   "every LDS-DMA destination is 1 KB aligned");
     static_assert(!PIPE || 64 * (BN + 4) * 4 <= SLOTS * STAGE, "a 64-row part of the epilogue fits in front of the tables");
@@ -220,7 +242,7 @@ __global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int t = threadIdx.x;
-    const int lane = t & 63, w = PIPE ? __builtin_amdgcn_readfirstlane(t >> 6) : t >> 6;
+    const int lane = t & 63, w = (PIPE || PHASED) ? __builtin_amdgcn_readfirstlane(t >> 6) : t >> 6;
     const int wm = w >> 1, wn = w & 1;
     const Gather& g = p.g;
 
@@ -400,8 +422,12 @@ __global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void 
         const unsigned char* wt = bbase + 2 * (int64_t)(kh * g.k + kw) * p.tap_stride;
 #pragma unroll
         for (int j = 0; j < JB; ++j) {
-            const int n = n0 + RSTR * j + rsub;
-            wsrc[j] = (kvalid & (n < p.N)) ? wt + 2 * (uint64_t)((unsigned)n * (unsigned)p.C) : zero;
+            // (phased form: the B halves of BN / 2 rows are staged apart, JB / 2 instructions of 64 rows each; at BN = 192 the
+            //  second one of a half covers 32 rows and the waves 4 - 7 have no part in it)
+            const int brow = PHASED ? (BN / 2) * (j / (JB / 2)) + 64 * (j % (JB / 2)) + rsub : RSTR * j + rsub;
+            const bool inside = !PHASED || 64 * (j % (JB / 2)) + rsub < BN / 2;
+            const int n = n0 + brow;
+            wsrc[j] = (kvalid & inside & (n < p.N)) ? wt + 2 * (uint64_t)((unsigned)n * (unsigned)p.C) : zero;
         }
     };
     set_tap();
@@ -438,13 +464,30 @@ __global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void 
         advance();
     };
 
-    f32x4_t acc[4][TN];
+    // ONE accumulator array per instantiation, shaped by the form and named by it: acc[16-row fragment][16-column fragment]
+    // of the wave's tile, or (phased form) accx by quadrant, [A half][16-row fragment][B half][16-column fragment].  Each
+    // name is used only inside the `if constexpr` branches of its form.
+    constexpr int XMI = PHASED ? (TN == 8 ? 4 : 2) : 1, XNJ = PHASED ? (TN == 6 ? 3 : 2) : 1;
+    typedef f32x4_t acc_plain_t[4][TN];
+    typedef f32x4_t acc_quad_t[2][XMI][2][XNJ];
+    typename std::conditional<PHASED, acc_quad_t, acc_plain_t>::type accv;
+    auto& acc = accv;
+    auto& accx = accv;
+    if constexpr (PHASED) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 2 * XMI; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+            for (int j = 0; j < 2 * XNJ; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+                for (int r = 0; r < 4; ++r) accx[i / XMI][i % XMI][j / XNJ][j % XNJ][r] = 0.f;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+    }
 
     if constexpr (PIPE) {
         // operand reads: lane -> row (lane & 15) of a 16-row fragment, chunk (lane >> 4) of the stage's one K block
@@ -483,6 +526,157 @@ __global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void 
             if (it + 2 < nst) kstep(it + 2, std::integral_constant<int, 2>());
         }
         __syncthreads();                           // every wave has read its last stage: the epilogue overlays the ring
+    } else if constexpr (PHASED) {
+        // Two K tiles per loop trip, four phases per tile, one accumulator quadrant per phase.  Waves: 2 (rows) x 4 at BN = 256,
+        // 4 x 2 at BN = 192 and 128.  Wave (wmx, wnx) owns the rows 128 h + 16 XMI wmx + 16 i (i < XMI) and the columns
+        // (BN / 2) hn + 16 XNJ wnx + 16 j (j < XNJ) of the tile (h, hn = 0, 1), so quadrant (h, hn)
+        // reads only the A half h and the B half hn of a stage, and a half is free for the tile after next as soon as its
+        // quadrants are read.  Tile u sits in buffer u & 1; its phases q = 0 .. 3 are
+        //   q  quadrant  ds_read_b128        LDS-DMA issued (2 A / JBH B instructions per wave)
+        //   0  (0, 0)    B half 0, A half 0  A half 1 of tile u + 1, then the K cursor moves on to tile u + 2
+        //   1  (0, 1)    B half 1            A half 0 of tile u + 2   (last read: phase 0)
+        //   2  (1, 1)    A half 1            B half 0 of tile u + 2   (last read: phase 0, kept in registers for phase 3)
+        //   3  (1, 0)    -                   B half 1 of tile u + 2   (last read: phase 1) ; s_waitcnt vmcnt(NFLY)
+        // and every phase is {reads ; issue ; s_barrier ; lgkmcnt(0) ; MFMAs ; s_barrier}.  Write after read: a half is
+        // restaged one phase after its last read, and those reads were retired by the lgkmcnt(0) every wave passes before
+        // the closing barrier of the reading phase.  Read after write: the one counted wait of a tile, in front of the first
+        // barrier of phase 3, leaves the three halves of tile u + 2 in flight (2 + 2 x the B instructions of this wave per
+        // half: JBH, at BN = 192 one fewer in the waves 4 - 7) and so retires everything of tile u + 1, whose first read is a
+        // phase later, behind that barrier.
+        constexpr int WNX = TN == 8 ? 4 : 2, JBH = JB / 2;
+        static_assert(JA == 4 && (8 / WNX) * XMI * 16 == 128 && WNX * XNJ * 16 == BN / 2, "halves of 128 rows / BN / 2 columns");
+        const int wmx = w / WNX, wnx = w % WNX;
+        const bool b_short = TN == 6 && w >= 4;        // (wave-uniform: w is scalar)
+        const int fsw = (lane & 15) >> 1;
+        const int a_row = (wmx * 16 * XMI + (lane & 15)) * 128;
+        const int b_row = A_BYTES + (wnx * 16 * XNJ + (lane & 15)) * 128;
+        int koff[2];
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) koff[s2] = 16 * ((4 * s2 + (lane >> 4)) ^ fsw);
+        // LDS-DMA of one half of the K cursor's tile into buffer `buf` (h: a compile-time constant)
+        auto piece_a = [&](int buf, auto h_c) {
+            constexpr int H = decltype(h_c)::value;
+            const uint32_t sa = lds0 + buf * STAGE + w * 1024;
+            const unsigned cbyte = 16u * (unsigned)c8;
+#pragma unroll
+            for (int j = 2 * H; j < 2 * H + 2; ++j) glds16_asm(asrc[j] + cbyte, sa + j * RSTR * ROWB);
+        };
+        auto piece_b = [&](int buf, auto h_c) {
+            constexpr int H = decltype(h_c)::value;
+            const uint32_t sb = lds0 + buf * STAGE + w * 1024 + A_BYTES;
+            const unsigned cbyte = 16u * (unsigned)c8;
+#pragma unroll
+            for (int jj = 0; jj < JBH; ++jj)
+                if (jj == 0 || !b_short) glds16_asm(wsrc[JBH * H + jj] + cbyte, sb + ((BN / 2) * H + 64 * jj) * ROWB);
+        };
+        auto wait_fly = [&]() {            // everything but this wave's part of the newest three halves has landed
+            if (b_short) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * JBH) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 + 2 * JBH) : "memory");
+        };
+        const std::integral_constant<int, 0> c0;
+        const std::integral_constant<int, 1> c1;
+        auto read_a = [&](bf16x8_t (&a)[2][XMI], const unsigned char* sbuf, int h) {
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                for (int i = 0; i < XMI; ++i)
+                    a[s2][i] = *reinterpret_cast<const bf16x8_t*>(sbuf + a_row + (128 * h + 16 * i) * 128 + koff[s2]);
+        };
+        auto read_b = [&](bf16x8_t (&b)[2][XNJ], const unsigned char* sbuf, int hn) {
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                for (int j = 0; j < XNJ; ++j)
+                    b[s2][j] = *reinterpret_cast<const bf16x8_t*>(sbuf + b_row + ((BN / 2) * hn + 16 * j) * 128 + koff[s2]);
+        };
+        auto mid = [&]() {                 // the phase's reads and LDS-DMA are issued: meet, then wait for the reads alone
+            __builtin_amdgcn_s_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_setprio(1);
+        };
+        auto close = [&]() {
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+        };
+        // weights as the MFMA's first operand; every accumulator takes K block 0, then K block 1 of the tile
+        auto quad = [&](auto h_c, auto hn_c, const bf16x8_t (&a)[2][XMI], const bf16x8_t (&b)[2][XNJ]) {
+            constexpr int H = decltype(h_c)::value, HN = decltype(hn_c)::value;
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                for (int i = 0; i < XMI; ++i)
+#pragma unroll
+                    for (int j = 0; j < XNJ; ++j)
+                        accx[H][i][HN][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[s2][j], a[s2][i], accx[H][i][HN][j], 0, 0, 0);
+        };
+        // TAIL: one of the last two tiles of the range - the issues are conditional and the wait drains the queue
+        auto ktile = [&](int u, auto buf_c, auto tail_c) {
+            constexpr int BUF = decltype(buf_c)::value;
+            constexpr bool TAIL = decltype(tail_c)::value;
+            const unsigned char* sbuf = smem + BUF * STAGE;
+            const bool n1 = !TAIL || u + 1 < nsteps, n2 = !TAIL || u + 2 < nsteps;
+            bf16x8_t a[2][XMI], b0[2][XNJ], b1[2][XNJ];
+            read_b(b0, sbuf, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            read_a(a, sbuf, 0);
+            if (n1) {
+                piece_a(BUF ^ 1, c1);
+                advance();
+            }
+            mid();
+            quad(c0, c0, a, b0);
+            close();
+            read_b(b1, sbuf, 1);
+            if (n2) piece_a(BUF, c0);
+            mid();
+            quad(c0, c1, a, b1);
+            close();
+            read_a(a, sbuf, 1);
+            if (n2) piece_b(BUF, c0);
+            mid();
+            quad(c1, c1, a, b1);
+            close();
+            if (n2) {
+                piece_b(BUF, c1);
+                wait_fly();
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            mid();
+            quad(c1, c0, a, b0);
+            close();
+        };
+        // prologue: tile 0 whole, tile 1 without its A half 1 (phase 0 of tile 0 issues it) - the state every tile starts from
+        if (nsteps > 0) {
+            piece_a(0, c0);
+            piece_b(0, c0);
+            piece_b(0, c1);
+            piece_a(0, c1);
+            advance();
+        }
+        if (nsteps > 1) {
+            piece_a(1, c0);
+            piece_b(1, c0);
+            piece_b(1, c1);
+            wait_fly();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        const std::integral_constant<bool, false> steady;
+        const std::integral_constant<bool, true> tail;
+        int u = 0;
+        for (; u + 4 <= nsteps; u += 2) {          // (tile u + 3 exists: both tiles prefetch unconditionally)
+            ktile(u, c0, steady);
+            ktile(u + 1, c1, steady);
+        }
+        if (u < nsteps) ktile(u, c0, tail);
+        if (u + 1 < nsteps) ktile(u + 1, c1, tail);
+        if (u + 2 < nsteps) ktile(u + 2, c0, tail);
+        // (the closing barrier of the last phase, or the prologue's: every read and LDS-DMA is done, the epilogue overlays)
     } else {
     // operand reads: lane -> row (lane & 15) of a 16-row fragment, chunk 4 s + (lane >> 4), swizzled by (row >> 1) & 7
     const int fsw = (lane & 15) >> 1;
@@ -526,8 +720,9 @@ __global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void 
     }
 
     // ---- epilogue: accumulators -> LDS [PR][BN + 4] fp32 -> whole 16-byte row segments ----
-    // (two stages: all 128 rows at once; ring forms: the 64 rows of wave row `part` at a time, in front of the tables)
-    constexpr int PARTS = PIPE ? WM : 1, PR = BM / PARTS;
+    // (two stages: all 128 rows at once; ring forms: the 64 rows of wave row `part` at a time, in front of the tables;
+    //  phased form: the 128 rows of A half `part` at a time, every wave its quadrants of that half)
+    constexpr int PARTS = PIPE ? WM : (PHASED ? 2 : 1), PR = BM / PARTS;
     constexpr int ELD = BN + 4;
     float* est = reinterpret_cast<float*>(smem);
     const bool partial = p.splitk > 1;
@@ -537,7 +732,20 @@ __global__ __launch_bounds__(128 * WM, SLOTS == 2 ? 2 : (WM == 4 ? 4 : 3)) void 
 #pragma unroll
     for (int part = 0; part < PARTS; ++part) {
     if (part > 0) __syncthreads();                  // (the previous part is stored)
-    if (!PIPE || wm == part) {
+    if constexpr (PHASED) {
+        constexpr int WNX = TN == 8 ? 4 : 2;
+        const int wmx = w / WNX, wnx = w % WNX;
+#pragma unroll
+        for (int i = 0; i < XMI; ++i)
+#pragma unroll
+            for (int hj = 0; hj < 2 * XNJ; ++hj) {
+                const int row = wmx * 16 * XMI + 16 * i + (lane & 15);
+                const int col = (BN / 2) * (hj / XNJ) + wnx * 16 * XNJ + 16 * (hj % XNJ) + 4 * (lane >> 4);
+                f32x4_t v = accx[part][i][hj / XNJ][hj % XNJ];
+                v[0] *= alpha; v[1] *= alpha; v[2] *= alpha; v[3] *= alpha;
+                *reinterpret_cast<f32x4_t*>(est + row * ELD + col) = v;
+            }
+    } else if (!PIPE || wm == part) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1674,10 +1882,13 @@ static int nn16_mfast(const NN16Params& p, int tiles_m, int tiles_n);
 
 // Which pipeline form of nn16_kernel a launch takes (see the kernel's header).  The forms give bit-identical results, so
 // this is a matter of speed alone; the plan (tile width, split-K) does not depend on it.
-//   tn: the plan's tile width; wide_blocks: blocks of the launch with 256-row tiles; mirrored: a mirrored-tap launch
-//   (NN16Params::ring), which has no 8-wave instantiation.
-// BG_NN16_PIPE (read per call: tests/test_gpu_nn16_pipe.py compares the forms) = 0: two stages everywhere, 1: the ring form at
-// the 128-row block wherever it applies, 2: the wide form wherever it applies; unset: the rule below.
+//   tn: the plan's tile width; row_blocks: 256-row tiles x stride phases x K splits of the launch; even_phases: every
+//   stride phase walks the same number of taps; mirrored: a mirrored-tap launch (NN16Params::ring), which has no 8-wave
+//   instantiation; *xtn: the phased form's own column tile BN / 32 (the plan's tn is for the 128-row tile).
+// BG_NN16_PIPE (read per call: tests/test_gpu_nn16_pipe.py and test_gpu_nn16_phased.py compare the forms) = 0: two stages
+// everywhere, 1: the ring form at the 128-row block wherever it applies, 2: the wide form wherever it applies, 3: the phased
+// form wherever it applies; unset: the rule below.  BG_NN16X_BN = 128 | 192 | 256 (read per call; the tests and
+// tools/kbench.py only) overrides the phased form's column tile.
 //
 // The rule, from the per-layer tables of profiles/nn16_pipe_ab.txt (config 3 at 256 and at 32 images, forward / input
 // gradient, ms, two stages -> wide form):
@@ -1687,24 +1898,74 @@ static int nn16_mfast(const NN16Params& p, int tiles_m, int tiles_n);
 //       convs 192 -> 96 0.14 / 0.23 -> 0.13 / 0.19, 96 -> 192 0.22 / 0.14 -> 0.19 / 0.13, 192 -> 24 input gradient 0.20 -> 0.14.
 //       These layers re-read activations, not weights: the 256-row tile halves the weight-tile traffic per row and its
 //       ring keeps two tiles in flight per block.
-//   32-column tiles (192 -> 24 forward: 0.091 -> 0.097), C >= 384 (within +-0.01 of the two-stage form at 256 images, up to
-//       20 % slower at 32, where the 256-row grid falls under one round) and position-major rows: two stages.
+//   32-column tiles (192 -> 24 forward: 0.091 -> 0.097), the ring forms at C >= 384 (within +-0.01 of the two-stage form at
+//       256 images, up to 20 % slower at 32, where the 256-row grid falls under one round) and position-major rows: two stages.
+//   C >= 384 per tap, image-major rows or position-major rows with Nb % 256 == 0, a grid of WHOLE rounds of one block per CU -
+//       the phased form (profiles/nn16x_phase_ab.txt; config 3 at 256 images, ms per call, two stages -> BN 128 / 192 / 256,
+//       forward ; input gradient; blocks at BN 128 / 192 / 256):
+//         deconv 4^2 1536 -> 1536 k4 s2    0.341 -> 0.318 / 0.300 / 0.333 ; 0.348 -> 0.333 / 0.318 / 0.343   (768 / 512 / 384)
+//         deconv 8^2 1536 -> 1536 k3       0.617 -> 0.627 / 0.566 / 0.678 ; 0.605 -> 0.600 / 0.548 / 0.651   (768 / 512 / 384)
+//         deconv 8^2 1536 -> 768 k4 s2     0.639 -> 0.559 / 0.493 / 0.466 (1536 / 1024 / 768) ; 0.539 -> 0.531 / 0.482 / 0.574
+//         deconv 16^2 768 -> 384 k4 s2     (forward: halo kernel) ; 0.586 -> 0.607 / 0.559 / 0.515   (1536 / 1024 / 768)
+//         deconv 32^2 384 -> 192 k4 s2     (forward: halo kernel) ; 0.644 -> 0.660 / 0.583 / 0.702   (3072 / 2048 / 2048)
+//         conv 16^2 384 -> 768 k3 s2       0.159 -> 0.170 / 0.152 / 0.176 ; 0.224 -> 0.243 / 0.218 / 0.246
+//         conv 8^2 768 -> 768 k3           0.298 -> 0.311 / 0.275 / 0.329 ; 0.408 -> 0.419 / 0.384 / 0.441   (768 / 512 / 384)
+//         conv 8^2 768 -> 1536 k3 s2       0.186 -> 0.193 / 0.178 / 0.208 ; 0.260 -> 0.261 / 0.248 / 0.255
+//         conv 4^2 1536 -> 1536 k3         0.323 -> 0.334 / 0.298 / 0.350 ; 0.552 -> 0.552 / 0.534 / 0.560   (768 / 512 / 384)
+//       (repeat spread of a layer: 0.001 - 0.006).  The form runs ONE block per CU, so what decides is whether the grid comes
+//       out in whole rounds of 256 blocks: BN = 256 wins only where it does (768 blocks: 1330 TF/s on 1536 -> 768 k4 s2) and
+//       loses at 384 blocks = 1.5 rounds; BN = 128 fills the rounds but fetches 3/4 of the two-stage form's L2 -> LDS bytes
+//       per FLOP and ties it.  1536, 768 and 384 output channels are whole multiples of 192, and 192-column tiles bring every
+//       one of these launches to 512, 1024 or 2048 blocks.  Hence: BN = 256 when N % 256 == 0, the grid is whole rounds at
+//       256 columns and the stride phases are even (k3 s2 phases walk 1 / 2 / 2 / 4 taps: 768 -> 1536 k3 s2 input gradient,
+//       1536 blocks at BN 256, is slower there than at 192); otherwise BN = 192 when 192-column tiles pad N to no more columns
+//       than the plan's own tiles do (N % 192 == 0 here; at N = 256, 512 or 1024 they would add 12 - 50 % of MFMA work, at
+//       N <= 64 many times the plan's - none of those measured, all left on two stages), the grid leaves at most 1/16 of the
+//       256 slots of its last round empty, however many rounds there are (a round half empty costs BN = 256 the 8 - 10 %
+//       the form gains) and, with uneven phases, has at least two rounds (768 -> 1536 k3 s2 input gradient at 256 images, ONE round of 256 blocks: 0.195 -> 0.215 per call in the
+//       step, the CUs that drew a 1-tap phase idle while the 4-tap blocks finish; at 512 images, two rounds, 0.259 -> 0.251);
+//       otherwise two stages.  At 32 images the rule leaves most of these launches on two stages and every C >= 384 layer is
+//       within the repeat spread (0.002 - 0.008 ms) of BG_NN16_PIPE=0.  Grids of partly filled rounds other than the 1.5
+//       above: not measured.
 //   The ring at the 128-row block is the default nowhere: where it gains (the C <= 192 layers above) the wide form gains
 //       more, and on the C >= 768 maps of 4^2 ... 8^2 it LOSES 25 - 40 % (1536 -> 1536 k3 at 8^2: 0.62 -> 0.87): those launches
 //       stream 10 - 40 MB of weights through L2 and a 32-channel stage reads only half of every 128-byte line per
 //       LDS-DMA, so each line is requested twice, one step apart - with three blocks per CU streaming 48 KB per step
 //       through the CU's 32 KB vector cache in between.  It stays behind the switch for the comparison.
-enum { NN16_FORM_TWO = 0, NN16_FORM_RING = 1, NN16_FORM_WIDE = 2 };
-static int nn16_form(const NN16Params& p, int tn, int64_t wide_blocks, bool mirrored) {
-    if (p.g.Ws >= (1 << 15)) return NN16_FORM_TWO;         // the ring forms keep the source column of a row as int16
-    // The wide form is for image-major rows only: a position-major tile walks the taps that ITS rows have sources under, so
-    // a 256-row tile would walk other taps (and split K elsewhere) than the two 128-row tiles it replaces - other sums.
-    const bool wide_ok = !mirrored && !p.posmajor;
+enum { NN16_FORM_TWO = 0, NN16_FORM_RING = 1, NN16_FORM_WIDE = 2, NN16_FORM_PHASED = 3 };
+constexpr int NN16X_CUS = 256;                // one phased block per CU (plan_nn16 counts 512 slots of two blocks per CU)
+static int nn16_form(const NN16Params& p, int tn, int64_t row_blocks, bool even_phases, bool mirrored, int* xtn) {
+    // The 256-row forms on position-major rows: a position-major tile walks the taps that ITS rows have sources under, so a
+    // 256-row tile would walk other taps (and split K elsewhere) than the two 128-row tiles it replaces - other sums -
+    // unless it lies inside one position, as both of those tiles then do: Nb % 256 == 0.  The wide form has no
+    // position-major instantiation at all.
+    const bool wide_ok = !mirrored && !p.posmajor && p.g.Ws < (1 << 15);   // (the ring forms keep source columns as int16)
+    const bool phased_ok = !mirrored && (!p.posmajor || p.g.Nb % 256 == 0);
+    const int64_t wide_blocks = row_blocks * ((p.N + 32 * tn - 1) / (32 * tn));
+    // BN of the phased form by the rule (0: the rule leaves the launch on two stages)
+    const int64_t nb256 = row_blocks * ((p.N + 255) / 256), nb192 = row_blocks * ((p.N + 191) / 192);
+    const int64_t last192 = (nb192 + NN16X_CUS - 1) / NN16X_CUS * NN16X_CUS - nb192;      // empty slots of the last round
+    // columns the 192-wide tiles pad N to, against the plan's own tiles: never more MFMA work than the plan's
+    const int pad192 = (p.N + 191) / 192 * 192, pad_plan = (p.N + 32 * tn - 1) / (32 * tn) * (32 * tn);
+    int bn = 0;
+    if (phased_ok && p.C >= 384) {
+        if (p.N % 256 == 0 && nb256 % NN16X_CUS == 0 && even_phases) bn = 256;
+        else if (pad192 <= pad_plan && nb192 >= (even_phases ? 1 : 2) * NN16X_CUS && last192 * 16 <= NN16X_CUS) bn = 192;
+    }
+    const int rule_bn = bn;
+    if (bn == 0) bn = p.N <= 128 ? 128 : (p.N <= 192 ? 192 : 256);       // (forced by the switch)
+    if (const char* e = getenv("BG_NN16X_BN")) {
+        const int v = atoi(e);
+        if (v == 128 || v == 192 || v == 256) bn = v;
+    }
+    *xtn = bn / 32;
     if (const char* e = getenv("BG_NN16_PIPE")) {
         const int v = atoi(e);
+        if (v == 3) return phased_ok ? NN16_FORM_PHASED : NN16_FORM_TWO;
         if (v == 2) return wide_ok ? NN16_FORM_WIDE : NN16_FORM_TWO;
-        return v == 1 ? NN16_FORM_RING : NN16_FORM_TWO;
+        return (v == 1 && p.g.Ws < (1 << 15)) ? NN16_FORM_RING : NN16_FORM_TWO;
     }
+    if (rule_bn) return NN16_FORM_PHASED;
     return (wide_ok && p.C <= 192 && tn >= 2 && wide_blocks >= 512) ? NN16_FORM_WIDE : NN16_FORM_TWO;
 }
 
@@ -1745,7 +2006,8 @@ int launch_nn16_ring(NN16Params& p, hipStream_t s) {
     p.tiles_n = (p.N + 32 * tn - 1) / (32 * tn);
     p.mfast = nn16_mfast(p, p.tiles_m, p.tiles_n);
     dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
-    const int form = nn16_form(p, tn, 0, true);
+    int xtn;
+    const int form = nn16_form(p, tn, 0, true, true, &xtn);
     int rc;
     switch (tn) {
         case 1: rc = launch_nn16_ring_tn<1>(p, form, grid, s); break;
@@ -1760,10 +2022,10 @@ int launch_nn16_ring(NN16Params& p, hipStream_t s) {
 
 template <int TN, int MODE, bool PM, int SLOTS = 2, int WM = 2>
 static int launch_nn16_inst(const NN16Params& p, dim3 grid, hipStream_t s) {
-    constexpr int lds = SLOTS == 3 ? nn16_pipe_lds_bytes(TN, WM) : nn16_lds_bytes(TN);
+    constexpr int lds = SLOTS == 3 ? nn16_pipe_lds_bytes(TN, WM) : (WM == 4 ? nn16x_lds_bytes(TN) : nn16_lds_bytes(TN));
     // > 48 KB of dynamic LDS needs the opt-in once per kernel and device
     if (!lds_opt_in(reinterpret_cast<const void*>(&nn16_kernel<TN, MODE, PM, false, SLOTS, WM>), lds)) return BG_ERR_LAUNCH;
-    if (SLOTS == 2) prof_kernel("nn16_kernel<%d, %d, %s>", TN, MODE, PM ? "true" : "false");
+    if (SLOTS == 2 && WM == 2) prof_kernel("nn16_kernel<%d, %d, %s>", TN, MODE, PM ? "true" : "false");
     else prof_kernel("nn16_kernel<%d, %d, %s, false, %d, %d>", TN, MODE, PM ? "true" : "false", SLOTS, WM);
     hipLaunchKernelGGL((nn16_kernel<TN, MODE, PM, false, SLOTS, WM>), grid, dim3(128 * WM), lds, s, p);
     return BG_OK;
@@ -1779,6 +2041,10 @@ static int launch_nn16_tn(const NN16Params& p, int form, dim3 grid, hipStream_t 
 
 template <int MODE, bool PM>
 static int launch_nn16_pm(const NN16Params& p, int tn, int form, dim3 grid, hipStream_t s) {
+    if (form == NN16_FORM_PHASED)                  // (tn: the form's own column tile, 4, 6 or 8)
+        return tn == 8   ? launch_nn16_inst<8, MODE, PM, 2, 4>(p, grid, s)
+               : tn == 6 ? launch_nn16_inst<6, MODE, PM, 2, 4>(p, grid, s)
+                         : launch_nn16_inst<4, MODE, PM, 2, 4>(p, grid, s);
     switch (tn) {
         case 1: return launch_nn16_tn<1, MODE, PM>(p, form, grid, s);
         case 2: return launch_nn16_tn<2, MODE, PM>(p, form, grid, s);
@@ -1941,12 +2207,15 @@ int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, 
     p.splitk = pl.splitk;
     p.slabs = reinterpret_cast<float*>(ws);
     p.slab_stride = out_elems;
-    const int bn = 32 * pl.tn;
-    p.tiles_n = (p.N + bn - 1) / bn;
     p.posmajor = nn16_posmajor_fraction(p, mode) < 1.0;
-    // the pipeline form: by the grid the 256-row tile would leave
-    const int form = nn16_form(p, pl.tn, (int64_t)((p.M + 255) / 256) * p.tiles_n * zdim * pl.splitk, false);
-    const int bm = form == NN16_FORM_WIDE ? 256 : NN16_BM;
+    // the pipeline form: by the grid the 256-row tile would leave; the phased form brings its own column tile
+    int xtn;
+    const int form = nn16_form(p, pl.tn, (int64_t)((p.M + 255) / 256) * zdim * pl.splitk,
+                               zdim == 1 || p.g.k % p.g.stride == 0, false, &xtn);
+    const int ltn = form == NN16_FORM_PHASED ? xtn : pl.tn;
+    const int bn = 32 * ltn;
+    p.tiles_n = (p.N + bn - 1) / bn;
+    const int bm = (form == NN16_FORM_WIDE || form == NN16_FORM_PHASED) ? 256 : NN16_BM;
     p.tiles_m = (p.M + bm - 1) / bm;
     p.pow2 = 0;
     if (p.g.Wq > 0 && p.g.Hq > 0 && (p.g.Wq & (p.g.Wq - 1)) == 0 && (p.g.Hq & (p.g.Hq - 1)) == 0) {
@@ -1963,9 +2232,9 @@ int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, 
     }
     int rc;
     if (mode == GATHER_CONV)
-        rc = launch_nn16_mode<GATHER_CONV>(p, pl.tn, form, grid, s);
+        rc = launch_nn16_mode<GATHER_CONV>(p, ltn, form, grid, s);
     else
-        rc = launch_nn16_mode<GATHER_TCONV>(p, pl.tn, form, grid, s);
+        rc = launch_nn16_mode<GATHER_TCONV>(p, ltn, form, grid, s);
     if (rc) return rc;
     BG_LAUNCH_CHECK();
     if (pl.splitk > 1) {

@@ -5,6 +5,9 @@
 fp32 / bf16-staged: fp32 tensors (BgConvDesc.compute); bf16: the bf16-resident kernels (bf16 tensors + packed weights).
 Prints ms and TFLOP/s of the forward, input-gradient and weight-gradient launch of every layer shape of the chosen
 BASELINE config (per-GPU batch).  Random (gaussian) data; timings with events on the launch stream.
+The tap kernel's pipeline form follows the library's switches, read per call: BG_NN16_PIPE = 0 | 1 | 2 | 3 (3: the phased form
+wherever it applies, with BG_NN16X_BN = 128 | 192 | 256 as its column tile) - the per-layer tables of csrc/igemm16.hip's
+nn16_form come from runs of this script under them.
 """
 import os
 import sys
