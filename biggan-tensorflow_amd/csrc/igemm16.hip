@@ -32,6 +32,8 @@
 //       are read transposed with ds_read_b64_tr_b16; fp32 split-K slabs over pixel ranges.
 //   tn16x_kernel  the wide form of it: 256 x 128 output tile, 8 waves, v_mfma_f32_32x32x16_bf16, 3-stage LDS ring of
 //       32-pixel stages filled by hand-counted LDS-DMA (s_waitcnt vmcnt(N)), two blocks per CU.
+//   tn16x_phased_kernel  the same product on a 256 x 192 / 256 x 256 tile at ONE block per CU: a ring of 16-pixel K blocks,
+//       operand reads one block ahead of the MFMAs, one raw barrier per block (launches chosen by tn16x_phased_bn).
 #include <stdlib.h>
 
 #include "common.h"
@@ -1666,6 +1668,223 @@ __global__ __launch_bounds__(512, (BK == 32 && NBI == 1) ? 4 : 2) void tn16x_ker
 }
 
 // ------------------------------------------------------------------------------------------
+// TN kernel, phased form: 256 x BN tile (BN = 192, 256), 8 waves as 4 (rows) x 2 (columns), ONE block per CU.
+//   tn16x_kernel<.., 32, 2> already had the 256 x 256 tile and bought nothing with it: alone on its CU, two waves per SIMD,
+//   a ring schedule idles the matrix pipe at every barrier.  This is that tile under nn16_kernel's phased schedule, and a
+//   192-column tile beside it (Cb = 192, 384, 768, 1536 are whole multiples of 192: no padding columns, 110 FLOP per staged
+//   byte; 256 columns: 131).  Wave (wm, wn) owns rows 64 wm .. + 63 and the 32-column fragments NBJ wn + j (j < NBJ = BN / 64);
+//   fragment f is 32-column block f & 3 of B image f >> 2.  At BN = 192 only chunks 0 - 7 of B image 1 are staged (the
+//   other lanes of those LDS-DMA instructions are masked) and read.
+//   LDS is a ring of NKB K BLOCKS of 16 pixels: [A image 0 | A image 1 | B image 0 | B image 1], 4 KB each ([16 pixels][128
+//   channels] bf16, tr16_swz as in the kernels above) = 16 KB per block, NKB = 6 (96 KB) or 8 (128 KB: measured, no faster).
+//   A K block is one phase and moves as 16 LDS-DMA instructions, two per wave (one A, one B): pixel rows
+//   4 (w & 3) + (lane >> 4) of image w >> 2.  The operands of a block are read into registers one phase ahead, so the
+//   transposed LDS reads of block n + 1 run under the MFMAs of block n.  Phase n (K block n, ring slot n % NKB):
+//     {s_waitcnt vmcnt(2 (NKB - 2)) lgkmcnt(0) ; s_barrier ; ds_read_tr16_b64 operands of block n + 1 ;
+//      s_setprio(1) ; NBJ MFMAs of block n ; s_setprio(0) ; LDS-DMA of block n + NKB into slot n % NKB ;
+//      s_setprio(1) ; NBJ MFMAs of block n ; s_setprio(0)}
+//   ONE barrier per phase.  The row -> source arithmetic and the two LDS-DMA of a phase sit between the halves of its MFMAs,
+//   where the matrix pipe has the first half queued (measured against the issue in front of the barrier, the pipe idle
+//   behind it: 1 - 4 % per launch; and against waves 0 - 3 issuing before and waves 4 - 7 after their MFMAs: that lost 7 %).
+//   Write after read: slot n % NKB was last read for block n, in phase n - 1; every wave retires those reads with the
+//   lgkmcnt(0) in front of the barrier of phase n, and the LDS-DMA into the slot is issued behind that barrier.  Read after
+//   write: at the wait of phase n a wave has issued the blocks up to n + NKB - 1, two instructions each, so
+//   vmcnt(2 (NKB - 2)) leaves the NKB - 2 youngest in flight and retires its part of block n + 1; the barrier extends that
+//   to every wave, and block n + 1 is read behind it.  The blocks n + 2 ... stay in flight across the barrier.  The last
+//   NKB phases have nothing to issue; there the wait drains the queue (vmcnt(0)), outside the steady loop.
+//   Sums: every accumulator takes the 16-pixel K blocks of its split in increasing pixel order, the same MFMA on the same
+//   operands as tn16x_kernel, over the same (zero-padded to 32 pixels) range - bit-identical to it under the same split.
+// ------------------------------------------------------------------------------------------
+constexpr int tn16xp_lds_bytes(int NKB) { return NKB * 4 * 16 * 256; }
+
+template <int MODE, int BN, int NKB>
+__global__ __launch_bounds__(512, 2) void tn16x_phased_kernel(const TN16Params p) {
+    static_assert(BN == 192 || BN == 256, "column tile: B image 0 and half or all of B image 1");
+    static_assert(NKB >= 3, "ring: the block being read, the block that lands next, at least one more in flight");
+    constexpr int NBJ = BN / 64;                        // 32-column MFMA tiles per wave
+    constexpr int IMG = 16 * 256;                       // bytes of one [16 pixels][128 channels] bf16 image
+    constexpr int KBLK = 4 * IMG;                       // A image 0 | A image 1 | B image 0 | B image 1
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // NKB K blocks
+
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wm = w >> 1, wn = w & 1;
+    const Gather& g = p.g;
+
+    const int ntile = p.tiles_m * p.tiles_n;
+    const int lin = xcd_remap(blockIdx.x, ntile * p.splitk);
+    const int zs = lin / ntile;
+    const int tile = lin - zs * ntile;
+    const int tile_n = tile % p.tiles_n, tile_m = tile / p.tiles_n;
+    const int mf0 = tile_m * 256, cb0 = tile_n * BN;
+    const int row_begin = zs * p.rows_per_split;
+    const int row_end = min(p.M, row_begin + p.rows_per_split);
+    const int nkb = 2 * max(0, (row_end - row_begin + 31) / 32);      // (tn16x_kernel's range: whole 32-pixel tiles)
+
+    // staging role: pixel row 4 wq + prow of the K block, channel chunk `ch` of A image ia and of B image ia
+    const int prow = lane >> 4;
+    const int wq = w & 3, ia = w >> 2;
+    const int ch = (lane & 15) ^ ((prow << 2) | wq);
+    const int mf = mf0 + 128 * ia + 8 * ch;
+    int a_kh = 0, a_kw = 0, a_c = mf;
+    if (MODE != GATHER_PLAIN) {
+        const int tap = mf / p.Ca;
+        a_c = mf - tap * p.Ca;
+        a_kh = tap / g.k;
+        a_kw = tap - a_kh * g.k;
+    }
+    const int cb = cb0 + 128 * ia + 8 * ch;
+    const bool b_lane = BN == 256 || ia == 0 || ch < 8;           // BN = 192: the next tile's columns are not staged
+    const void* zero = reinterpret_cast<const void*>(g_zero_page);
+    int m_next = row_begin + 4 * wq + prow;
+    const uint32_t lds0 = static_cast<uint32_t>(
+        reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) unsigned char*)smem));
+
+    // row -> source address as in tn16x_kernel: shifts on a power-of-two pixel grid, no divisions or branches
+    const int dh = a_kh - g.pad, dw = a_kw - g.pad;
+    const unsigned hmax = g.reflect ? 0xffffffffu : (unsigned)g.Hs - 1u;
+    const unsigned wmax = g.reflect ? 0xffffffffu : (unsigned)g.Ws - 1u;
+    const int h2 = 2 * (g.Hs - 1), w2 = 2 * (g.Ws - 1);
+    const int wmask = g.Wq - 1, hmask = g.Hq - 1, bsh = p.wq_shift + p.hq_shift;
+    const int a_lim = mf < p.Mf ? row_end : 0, b_lim = cb < p.Cb ? row_end : 0;
+    const unsigned char* abase = reinterpret_cast<const unsigned char*>(reinterpret_cast<const __bf16*>(p.A) + a_c);
+    const unsigned char* bbase = reinterpret_cast<const unsigned char*>(reinterpret_cast<const __bf16*>(p.Bv) + cb);
+    const unsigned ald2 = 2u * (unsigned)g.ld, bld2 = 2u * (unsigned)p.b_ld;
+
+    const uint32_t sa0 = __builtin_amdgcn_readfirstlane(lds0 + ia * IMG + (4 * wq) * 256);
+    const uint32_t sb0 = __builtin_amdgcn_readfirstlane(lds0 + (2 + ia) * IMG + (4 * wq) * 256);
+    // LDS-DMA of the K cursor's block into ring slot `slot`: two instructions per wave, always (the counted waits rely on it)
+    auto issue = [&](int slot) __attribute__((always_inline)) {
+        const int m = m_next;
+        unsigned pix = (unsigned)m;
+        bool ok = m < a_lim;
+        if (MODE != GATHER_PLAIN) {
+            const int wo = m & wmask, ho = (m >> p.wq_shift) & hmask, b = m >> bsh;
+            const int h = __mul24(ho, g.stride) + dh, wsrc = __mul24(wo, g.stride) + dw;
+            const int ha = h < 0 ? -h : h, wa = wsrc < 0 ? -wsrc : wsrc;          // tf.pad(REFLECT): -1 -> 1, n -> n - 2
+            const int hr = min(ha, h2 - ha), wr = min(wa, w2 - wa);
+            ok = ok & ((unsigned)h <= hmax) & ((unsigned)wsrc <= wmax);
+            pix = __umul24(__umul24((unsigned)b, (unsigned)g.Hs) + (unsigned)hr, (unsigned)g.Ws) + (unsigned)wr;
+        }
+        const void* srca = ok ? static_cast<const void*>(abase + (uint64_t)pix * ald2) : zero;
+        glds16_asm(srca, sa0 + slot * KBLK);
+        const void* srcb = m < b_lim ? static_cast<const void*>(bbase + (uint64_t)(unsigned)m * bld2) : zero;
+        if (b_lane) glds16_asm(srcb, sb0 + slot * KBLK);
+        m_next += 16;
+    };
+
+    f32x16_t acc[2][NBJ];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NBJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // transposed-read addresses (slot 0): as in tn16x_kernel, rows 0 .. 15 of the K block
+    const int kblk = lane >> 5, g16 = (lane >> 4) & 1, q = (lane & 15) >> 2, pq = lane & 3;
+    uint32_t a_ad[2][2], b_ad[NBJ][2];
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+        const int row = 8 * kblk + 4 * jj + q;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            a_ad[i][jj] = lds0 + (wm >> 1) * IMG +
+                          tr16_swz(row, 4 * ((wm & 1) * 2 + i) + 2 * g16 + (pq >> 1)) + 8 * (pq & 1);
+#pragma unroll
+        for (int j = 0; j < NBJ; ++j) {
+            const int f = NBJ * wn + j;
+            b_ad[j][jj] = lds0 + (2 + (f >> 2)) * IMG + tr16_swz(row, 4 * (f & 3) + 2 * g16 + (pq >> 1)) + 8 * (pq & 1);
+        }
+    }
+    auto operand = [&](uint32_t lo_addr, uint32_t hi_addr) __attribute__((always_inline)) {
+        const s16x4v lo = lds_tr16(lo_addr), hi = lds_tr16(hi_addr);
+        const s16x8v v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        return __builtin_bit_cast(bf16x8_t, v);
+    };
+
+    // operands of block n in registers of parity n & 1: block n + 1 is read from LDS while block n is multiplied
+    bf16x8_t ra[2][2], rb[2][NBJ];
+    auto read_block = [&](auto slot_c) __attribute__((always_inline)) {
+        constexpr int SLOT = decltype(slot_c)::value;
+        constexpr uint32_t off = (uint32_t)SLOT * (uint32_t)KBLK;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) ra[SLOT & 1][i] = operand(a_ad[i][0] + off, a_ad[i][1] + off);
+#pragma unroll
+        for (int j = 0; j < NBJ; ++j) rb[SLOT & 1][j] = operand(b_ad[j][0] + off, b_ad[j][1] + off);
+    };
+    // one phase on ring slot SLOT (a compile-time constant); TAIL: one of the phases at the end of the range, where the issue
+    // may be past it and the queue drains
+    auto phase = [&](int n, auto slot_c, auto tail_c) __attribute__((always_inline)) {
+        constexpr int SLOT = decltype(slot_c)::value;
+        constexpr bool TAIL = decltype(tail_c)::value;
+        if (!TAIL || n + NKB <= nkb) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * (NKB - 2)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0) once more, where the compiler's own wait counting sees it
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        if (!TAIL || n + 1 < nkb) read_block(std::integral_constant<int, (SLOT + 1) % NKB>());
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int j = 0; j < NBJ; ++j)
+            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ra[SLOT & 1][0], rb[SLOT & 1][j], acc[0][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (!TAIL || n + NKB < nkb) issue(SLOT);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int j = 0; j < NBJ; ++j)
+            acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ra[SLOT & 1][1], rb[SLOT & 1][j], acc[1][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto round = [&](int n, auto tail_c) __attribute__((always_inline)) {            // NKB phases from block n (n % NKB == 0), as far as the range goes
+        phase(n, std::integral_constant<int, 0>(), tail_c);
+        if (n + 1 < nkb) phase(n + 1, std::integral_constant<int, 1>(), tail_c);
+        if (n + 2 < nkb) phase(n + 2, std::integral_constant<int, 2>(), tail_c);
+        if (n + 3 < nkb) phase(n + 3, std::integral_constant<int, 3>(), tail_c);
+        if (n + 4 < nkb) phase(n + 4, std::integral_constant<int, 4>(), tail_c);
+        if (n + 5 < nkb) phase(n + 5, std::integral_constant<int, 5>(), tail_c);
+        if constexpr (NKB == 8) {
+            if (n + 6 < nkb) phase(n + 6, std::integral_constant<int, 6>(), tail_c);
+            if (n + 7 < nkb) phase(n + 7, std::integral_constant<int, 7>(), tail_c);
+        }
+    };
+    static_assert(NKB == 6 || NKB == 8, "round() spells the phases out");
+
+    // prologue: blocks 0 .. NKB - 1 issued, block 0 landed and read - the state every phase starts from
+#pragma unroll
+    for (int k = 0; k < NKB; ++k)
+        if (k < nkb) issue(k);
+    if (nkb >= NKB) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (NKB - 1)) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (nkb > 0) read_block(std::integral_constant<int, 0>());
+    const std::integral_constant<bool, false> steady;
+    const std::integral_constant<bool, true> tail;
+    int n = 0;
+    for (; n + 2 * NKB <= nkb; n += NKB) round(n, steady);            // (the round's last phase still has a block to issue)
+    if (n < nkb) round(n, tail);
+    if (n + NKB < nkb) round(n + NKB, tail);
+
+    float* obase = p.out + (int64_t)zs * p.slab_stride;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = mf0 + wm * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (row >= p.Mf) continue;
+#pragma unroll
+            for (int j = 0; j < NBJ; ++j) {
+                const int col = cb0 + 32 * (NBJ * wn + j) + (lane & 31);
+                if (col < p.Cb) obase[(int64_t)row * p.out_ld + col] = acc[i][j][r];
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // transpose of tf.pad(REFLECT) (ops.py:82): fold the gradient on the padded grid back onto the image
 // ------------------------------------------------------------------------------------------
 template <bool F32>
@@ -2274,6 +2493,74 @@ static int tn16x_nbi(const TN16Params& p) {
     return (p.Cb >= 512 && p.Cb % 256 == 0 && p.Mf >= 256) ? 2 : 1;
 }
 
+// Column tile of the phased form (tn16x_phased_kernel) for a launch that plan_tn16x accepts; 0: the launch keeps
+// tn16x_kernel<.., 32>.  The K partition is plan_tn16x's for 128-column tiles whatever the tile (same sums, same workspace):
+// tm: 256-row tiles, sk: K splits of that plan, so the phased grid is tm * ceil(Cb / BN) * sk blocks.
+// Switches, read per call (tests/test_gpu_tn16x_phased.py, tools/kbench.py): BG_TN16X_PHASED = 0: never, 1: every launch
+// the wide form accepts (gathered operands only: the regulariser's Gram keeps the ring form - not measured); unset: the
+// rule.  BG_TN16X_PHASED_BN = 192 / 256 sets the column tile of a launch that takes the form.  With BG_TN16X_NBI=2 set, the
+// launches that switch applies to go where it sends them.  (BG_TN16X_PHASED_RING=8: the 128 KB ring, for A/B.)
+//
+// The rule, from the per-layer table of profiles/tn16x_phase_ab.txt (config 3 at 256 images, tools/kbench.py wgrad column,
+// ms per call: tn16x_kernel<0, 32> -> BN 192 / BN 256 ; Cb ; blocks at 128 / 192 / 256 columns; repeat spread 0.001 - 0.010):
+//   deconv 64^2 192 -> 96 k4 s2      0.889 -> 0.694 / 0.780   Cb  192   504 / 252 / 252
+//   deconv 64^2 192 -> 192 k3        0.976 -> 0.781 / 0.870   Cb  192   504 / 252 / 252
+//   conv 64^2 96 -> 192 k3 s2        0.290 -> 0.221 / 0.246   Cb  192   512 / 256 / 256
+//   conv 32^2 192 -> 192 k3          0.502 -> 0.385 / 0.419   Cb  192   504 / 252 / 252
+//   deconv 32^2 384 -> 192 k4 s2     0.693 -> 0.866 / 0.952   Cb  384   504 / 336 / 336
+//   deconv 32^2 384 -> 384 k3        0.769 -> 1.000 / 1.163   Cb  384   504 / 336 / 336
+//   conv 32^2 192 -> 384 k3 s2       0.210 -> 0.283 / 0.307   Cb  384   504 / 336 / 336
+//   conv 16^2 384 -> 384 k3          0.359 -> 0.506 / 0.566   Cb  384   504 / 336 / 336
+//   deconv 16^2 768 -> 384 k4 s2     0.742 -> 0.994 / 0.635   Cb  768   432 / 288 / 216
+//   deconv 16^2 768 -> 768 k3        0.684 -> 0.989 / 0.588   Cb  768   486 / 324 / 243
+//   conv 16^2 384 -> 768 k3 s2       0.205 -> 0.279 / 0.184   Cb  768   504 / 336 / 252
+//   conv 8^2 768 -> 768 k3           0.385 -> 0.525 / 0.349   Cb  768   486 / 324 / 243
+//   deconv 8^2 1536 -> 768 k4 s2     0.777 -> 0.749 / 0.802   Cb 1536   576 / 384 / 288
+//   deconv 8^2 1536 -> 1536 k3       0.821 -> 0.796 / 0.842   Cb 1536   648 / 432 / 324
+//   deconv 4^2 1536 -> 1536 k4 s2    0.370 -> 0.338 / 0.355   Cb 1536  1152 / 768 / 576
+//   conv 8^2 768 -> 1536 k3 s2       0.259 -> 0.195 / 0.224   Cb 1536   324 / 216 / 162
+//   conv 4^2 1536 -> 1536 k3         0.414 -> 0.401 / 0.446   Cb 1536   648 / 432 / 324
+//   (forced onto Cb = 96 and 24 the form loses 8 - 60 %: one partly filled tile.)
+// The form runs ONE block per CU under a split that was planned for 512 slots of 128 columns, and the split stays (the sums
+// depend on it).  What decides is therefore how the grid falls into rounds of 256 blocks.  With whole 192-column tiles the
+// Cb = 192 layers come out at 252 - 256 blocks without the parent's half-empty second tile (-20 ... -24 %), 768 -> 1536 k3 s2
+// at 216 (-25 %) and 1536 -> 1536 k4 s2 at three whole rounds (-9 %).  At Cb = 768 three 256-column tiles make 216 - 252
+// blocks (-9 ... -14 %) where four 192-column tiles make 1.1 - 1.3 rounds (+35 ... 45 %).  Cb = 384 has no tile that fills
+// its rounds (336 blocks: +25 ... 40 %).  The Cb = 1536 launches of 1.5 - 1.7 rounds gain 3 - 4 % at 192 (their parent grids,
+// 576 - 648 blocks on 512 slots, do not fill their rounds either) and lose at 256.  Hence: BN = 192 where Cb % 192 == 0,
+// else BN = 256 where Cb % 256 == 0, each only if the last round of its grid is at least half full (measured: 0 - 128 empty
+// slots gain, 176 and more lose; grids under half a round and Cb % 256 == 0 with Cb % 192 != 0: not measured) - otherwise the
+// parent form: Cb = 96, 24, 8, every tail, every grid that does not fill its rounds.
+constexpr int TN16XP_CUS = 256;
+static int tn16x_phased_bn(const TN16Params& p, int mode, int tm, int sk) {
+    if (mode != GATHER_CONV || tn16x_nbi(p) != 1) return 0;
+    int bn = 0;
+    for (int c = 192; c <= 256 && bn == 0; c += 64) {
+        const int64_t blocks = (int64_t)tm * (p.Cb / c) * sk;
+        const int64_t last = (blocks + TN16XP_CUS - 1) / TN16XP_CUS * TN16XP_CUS - blocks;      // empty slots of the last round
+        if (p.Cb % c == 0 && last * 2 <= TN16XP_CUS) bn = c;
+    }
+    if (const char* e = getenv("BG_TN16X_PHASED")) {
+        if (atoi(e) == 0) return 0;
+        if (bn == 0) bn = (p.Cb > 192 && p.Cb % 256 == 0) ? 256 : 192;       // (forced by the switch)
+    }
+    if (bn == 0) return 0;
+    if (const char* e = getenv("BG_TN16X_PHASED_BN")) {
+        const int v = atoi(e);
+        if (v == 192 || v == 256) bn = v;
+    }
+    return bn;
+}
+
+template <int BN, int NKB>
+static int launch_tn16x_phased(const TN16Params& p, dim3 grid, hipStream_t s) {
+    constexpr int lds = tn16xp_lds_bytes(NKB);
+    if (!lds_opt_in(reinterpret_cast<const void*>(&tn16x_phased_kernel<GATHER_CONV, BN, NKB>), lds)) return BG_ERR_LAUNCH;
+    prof_kernel("tn16x_phased_kernel<%d, %d, %d>", (int)GATHER_CONV, BN, NKB);
+    hipLaunchKernelGGL((tn16x_phased_kernel<GATHER_CONV, BN, NKB>), grid, dim3(512), lds, s, p);
+    return BG_OK;
+}
+
 static bool plan_tn16x(const TN16Params& p, int* sk_out, int* rps_out) {
     static const int use_wide = getenv("BG_TN16_WIDE") ? atoi(getenv("BG_TN16_WIDE")) : 1;
     if (!use_wide || p.Mf <= 128 || p.M < 8 * TN16_BK) return false;
@@ -2343,6 +2630,22 @@ int launch_tn16(TN16Params& p, int mode, float* final_out, void* ws, size_t ws_b
             p.tiles_m = tm;
             p.tiles_n = tn;
             static const int bk = getenv("BG_TN16X_BK") ? atoi(getenv("BG_TN16X_BK")) : 32;
+            if (const int pbn = tn16x_phased_bn(p, mode, tm, sk)) {
+                const char* ring = getenv("BG_TN16X_PHASED_RING");     // K blocks of the ring: 6 (96 KB), 8 (128 KB, for A/B)
+                const int nkb = ring ? atoi(ring) : 6;
+                p.tiles_n = (p.Cb + pbn - 1) / pbn;
+                dim3 gridp(tm * p.tiles_n * sk, 1, 1);
+                int rc;
+                if (pbn == 256) rc = nkb == 8 ? launch_tn16x_phased<256, 8>(p, gridp, s) : launch_tn16x_phased<256, 6>(p, gridp, s);
+                else rc = nkb == 8 ? launch_tn16x_phased<192, 8>(p, gridp, s) : launch_tn16x_phased<192, 6>(p, gridp, s);
+                if (rc) return rc;
+                BG_LAUNCH_CHECK();
+                if (sk > 1) {
+                    launch_slab_reduce(reinterpret_cast<const float*>(ws), final_out, total, sk, total, s);
+                    BG_LAUNCH_CHECK();
+                }
+                return BG_OK;
+            }
             if (nbi == 2) {
                 constexpr int ldsw = 3 * 4 * 32 * 256;
                 const void* fw = mode == GATHER_CONV ? reinterpret_cast<const void*>(&tn16x_kernel<GATHER_CONV, 32, 2>)

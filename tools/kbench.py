@@ -1,13 +1,14 @@
 """Per-layer kernel micro-benchmark through the C ABI.
 
-    python tools/kbench.py [filter] [fp32 | bf16-staged | bf16] [c2 | c3] [batch multiplier]
+    python tools/kbench.py [filter] [fp32 | bf16-staged | bf16] [c2 | c3] [batch multiplier] [fwd | dgrad | wgrad]
 
 fp32 / bf16-staged: fp32 tensors (BgConvDesc.compute); bf16: the bf16-resident kernels (bf16 tensors + packed weights).
 Prints ms and TFLOP/s of the forward, input-gradient and weight-gradient launch of every layer shape of the chosen
 BASELINE config (per-GPU batch).  Random (gaussian) data; timings with events on the launch stream.
 The tap kernel's pipeline form follows the library's switches, read per call: BG_NN16_PIPE = 0 | 1 | 2 | 3 (3: the phased form
 wherever it applies, with BG_NN16X_BN = 128 | 192 | 256 as its column tile) - the per-layer tables of csrc/igemm16.hip's
-nn16_form come from runs of this script under them.
+nn16_form come from runs of this script under them.  Likewise the weight gradients: BG_TN16X_PHASED = 0 | 1 with
+BG_TN16X_PHASED_BN = 192 | 256 (tn16x_phased_bn).  A fifth argument times that pass alone (the other columns print 0).
 """
 import os
 import sys
@@ -64,6 +65,7 @@ flt = sys.argv[1] if len(sys.argv) > 1 else ""
 mode = sys.argv[2] if len(sys.argv) > 2 else "fp32"
 cfg = sys.argv[3] if len(sys.argv) > 3 else "c3"
 scale = int(sys.argv[4]) if len(sys.argv) > 4 else 1       # 8: config 3 at its global batch 256 on one GPU
+only = sys.argv[5] if len(sys.argv) > 5 else ""
 Fn.set_precision(mode)
 res = mode == "bf16"
 adt = torch.bfloat16 if res else torch.float32
@@ -118,7 +120,7 @@ for kind, N, H, Cin, Cout, k, s in cases(cfg):
         ws = hip.workspace(nb, dev)
         dw = torch.empty_like(w)
         wg = lambda: check(L.bg_deconv2d_wgrad(d, act(x), act(y), f32(dw), f32(ws), nb, stream()))
-    r = [T(f, fl) for f in (fw, dg, wg)]
+    r = [T(f, fl) if only in ("", tag) else (0.0, 0.0) for f, tag in ((fw, "fwd"), (dg, "dgrad"), (wg, "wgrad"))]
     for i in range(3):
         tot[i] += r[i][0]
     print("%-44s %8.3f %8.1f  %8.3f %8.1f  %8.3f %8.1f" % (name, r[0][0], r[0][1], r[1][0], r[1][1], r[2][0], r[2][1]),
