@@ -297,6 +297,54 @@ def swd_l1(a, b, n_out=1, out=None):
     return out
 
 
+# ---- nearest training images (csrc/nearest.hip; neighbours.py drives them).  No autograd anywhere. ----
+def nn_pack(x, f=1, mirror=False, out=None):
+    """Search descriptors of an image batch: x [B,S,S,C] fp32 or bf16 -> bf16 [B, (S/f)(S/f)C], the f x f box mean (fp32
+    sum, rounded to nearest even); ``mirror``: of the horizontally flipped images."""
+    x = _swd_images("nn_pack", x)
+    B, S, _, C = x.shape
+    f = int(f)
+    if f < 1 or S % f:
+        raise RuntimeError("nn_pack: f=%d does not divide S=%d" % (f, S))
+    D = (S // f) * (S // f) * C
+    if out is None:
+        out = torch.empty(B, D, dtype=BF16, device=x.device)
+    po = _swd_typed("nn_pack", "out", out, BF16, (B, D))
+    check(lib().bg_nn_pack(act(x), dt(x), B, S, C, f, 1 if mirror else 0, po, stream()))
+    return out
+
+
+def nn_distances(q, set_, out=None):
+    """Squared distances of q bf16 [Q,D] to the rows of set_ bf16 [N,D] -> fp32 [Q,N], summed as fp32 differences in a
+    fixed order (a row equal to a query gives exactly 0)."""
+    if q.dim() != 2 or set_.dim() != 2 or q.shape[1] != set_.shape[1]:
+        raise RuntimeError("nn_distances: q [Q,D] and set [N,D], got %s and %s" % (tuple(q.shape), tuple(set_.shape)))
+    (Q, D), N = q.shape, set_.shape[0]
+    pq = _swd_typed("nn_distances", "q", q, BF16, (Q, D))
+    ps = _swd_typed("nn_distances", "set", set_, BF16, (N, D))
+    if out is None:
+        out = torch.empty(Q, N, dtype=torch.float32, device=q.device)
+    po = _swd_typed("nn_distances", "out", out, torch.float32, (Q, N))
+    check(lib().bg_nn_distances(pq, ps, Q, N, D, po, stream()))
+    return out
+
+
+def nn_topk(dist, k):
+    """The k <= 16 smallest entries of every row of dist fp32 [Q,N]: (values fp32 [Q,k], indices int32 [Q,k]), ascending,
+    ties to the lower index, (+inf, -1) past N.  Exact."""
+    if dist.dim() != 2:
+        raise RuntimeError("nn_topk: dist must be [Q,N], got %s" % (tuple(dist.shape),))
+    Q, N = dist.shape
+    k = int(k)
+    pd = _swd_typed("nn_topk", "dist", dist, torch.float32, (Q, N))
+    nb = int(lib().bg_nn_topk_workspace_bytes(Q, N, k))
+    ws = torch.empty(max(nb, 4) // 4, dtype=torch.int32, device=dist.device)
+    ov = torch.empty(Q, k, dtype=torch.float32, device=dist.device)
+    oi = torch.empty(Q, k, dtype=torch.int32, device=dist.device)
+    check(lib().bg_nn_topk(pd, Q, N, k, hip.ptr(ov), hip.ptr(oi), hip.ptr(ws), nb, stream()))
+    return ov, oi
+
+
 def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
     the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns

@@ -63,7 +63,14 @@ FLAGS = [
 #   --swd_freq N            every N iterations: the sliced Wasserstein scores of the generator (metrics.py) as scalars in
 #                           the event file and one "SWD: ..." line; 0 (default) is off.  --phase test: computed once
 #   --swd_images M          images per set, rounded down to a power of two (and to the number of dataset files)
-EXTRA_FLAGS = [("precision", T, None), ("swd_freq", I, 0), ("swd_images", I, 2048)]
+#   --nn_freq N             every N iterations: the nearest training images of the static samples in pixel space
+#                           (neighbours.py): a grid and a table next to the sample grids, scalars nn_dist_min / nn_dist_mean
+#                           and one "NN: ..." line; 0 (default) is off.  --phase test: computed once
+#   --nn_k K                neighbours per sample, 1..8
+#   --nn_size S             side of the search descriptors, a power of two >= 8; min(img_size, S) is used
+#   --nn_images M           the first M files of the listing; 0 (default): all of them (capped by BG_NN_GB, default 8 GiB)
+EXTRA_FLAGS = [("precision", T, None), ("swd_freq", I, 0), ("swd_images", I, 2048),
+               ("nn_freq", I, 0), ("nn_k", I, 3), ("nn_size", I, 64), ("nn_images", I, 0)]
 
 
 def build_parser():

@@ -177,6 +177,12 @@ class BigGAN(GANBase):
         self.swd_freq = int(getattr(args, "swd_freq", 0) or 0)
         self.swd_images = int(getattr(args, "swd_images", 2048) or 2048)
         self._swd = None                       # metrics.Swd with the kept real set, built at the first event
+        # nearest training images (extension flags --nn_freq / --nn_k / --nn_size / --nn_images; neighbours.py)
+        self.nn_freq = int(getattr(args, "nn_freq", 0) or 0)
+        self.nn_k = int(getattr(args, "nn_k", 3) or 3)
+        self.nn_size = int(getattr(args, "nn_size", 64) or 64)
+        self.nn_images = int(getattr(args, "nn_images", 0) or 0)
+        self._nn = None                        # neighbours.NearestSet with the resident training set, built at the first event
         self.recon_plan = self._recon_plan()
         self.deep = args.deep                                                          # BigGAN.py:20
         self.g_mixed_resblocks = args.g_mixed_resblocks                                # BigGAN.py:40-41
@@ -1564,6 +1570,8 @@ class BigGAN(GANBase):
                         print("SWD: " + format_scores(scores), flush=True)
                         if self._log_writer is not None:
                             self._log_writer.add_scalars(self.counter - 1, scores)
+                if self.nn_freq > 0 and self.counter % self.nn_freq == 0:
+                    self.save_neighbours(epoch, idx + 1)                               # (collective: every rank enters)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
             if self._log_writer is not None:
@@ -1889,10 +1897,122 @@ class BigGAN(GANBase):
                     out.update(m.scores(m.finish(), prefix))
         return out
 
+    # ---- nearest training images (neighbours.py) -------------------------------------------------
+    def nn_plan(self, root="./dataset"):
+        from .neighbours import NnPlan
+        files = self._swd_files(root)
+        return NnPlan(self.img_size, self.c_dim, self.batch_size, self.nn_size, self.nn_images, self.static_sample_seed,
+                      n_files=None if files is None else len(files))
+
+    def nn_set_batches(self, plan, files):
+        """The training set of the search, ``batch_size`` images at a time on the device, in listing order and unflipped:
+        decoded by a thread pool, then resized and normalised on the device where the loader would do so
+        (``data.device_input_enabled``), else by ``ImageData.image_processing``; the two are bit-identical.  The
+        ``ImageData`` is the search's own: the training loader and its flip stream are never touched.  Without a dataset
+        folder: ``neighbours.synthetic_batch``."""
+        B = self.batch_size
+        if not plan.from_files:
+            from .neighbours import synthetic_batch
+            for b in range((plan.N + B - 1) // B):
+                yield synthetic_batch(plan, b, self.device)
+            return
+        import numpy as np
+        from concurrent.futures import ThreadPoolExecutor
+        from . import data as D
+        image_data = D.ImageData(self.img_size, self.c_dim, True, False)
+        on_device = D.device_input_enabled(self.device)
+        with ThreadPoolExecutor(max_workers=8) as pool:
+            for lo in range(0, plan.N, B):
+                part = files[lo:min(lo + B, plan.N)]
+                if on_device:
+                    arrs = list(pool.map(lambda f: D.decode_file(image_data, f), part))
+                    if all(D.packable(a, self.c_dim) for a in arrs):
+                        yield D.PackedBatch(*D.pack_batch(arrs, [False] * len(arrs), self.img_size, self.c_dim,
+                                                          pin=True)).to_device(self.device)
+                        continue
+                    imgs = list(pool.map(lambda a: D.finish_on_host(a, self.img_size, False), arrs))
+                else:
+                    imgs = list(pool.map(image_data.image_processing, part))
+                yield torch.from_numpy(np.stack(imgs)).to(self.device)
+
+    def _nn_set(self, root="./dataset"):
+        """The resident training set (neighbours.NearestSet), built at the first call and kept."""
+        if self._nn is None:
+            from . import neighbours
+            plan = self.nn_plan(root)
+            files = self._swd_files(root)
+            s = neighbours.NearestSet(plan, self.device, files)
+            for batch in self.nn_set_batches(plan, files):
+                s.add(batch)
+            self._nn = s.finish()
+        return self._nn
+
+    def _nn_fetch(self, index):
+        """The full-size training image fp32 [S,S,C] (numpy) of a set index, by the host path; kept per index."""
+        s = self._nn
+        if index not in s.images:
+            if s.plan.from_files:
+                from . import data as D
+                s.images[index] = D.ImageData(self.img_size, self.c_dim, True, False).image_processing(s.files[index])
+            else:
+                from .neighbours import synthetic_batch
+                b, i = divmod(index, self.batch_size)
+                s.images[index] = synthetic_batch(s.plan, b, self.device)[i].cpu().numpy()
+        return s.images[index]
+
+    def nearest(self, images=None, ema=True, k=None, root="./dataset", _samples=None):
+        """The ``k`` (default --nn_k) nearest training images of ``images`` [Q,S,S,C] on the device, or else of the first
+        min(sample_num, batch_size) images of the static sample set (``ema``: from the moving averages), in pixel space at
+        the search side: {``dist`` [Q,k]: RMS difference per element in units of the [-1, 1] pixel scale, ``index``: rows of
+        the listing, ``mirrored``: the hit is the mirror image (searched when --random_flip is true), ``files``}.  The
+        training set's descriptors are computed at the first call and kept.  Every rank calls it (``sync_sharded_state`` is
+        collective); rank 0 computes, the others return {}.  Nothing the training run reads is changed."""
+        self.sync_sharded_state()
+        if self.rank != 0:
+            return {}
+        with torch.no_grad():
+            s = self._nn_set(root)
+            if images is None:
+                zs, cs = self.static_sample_set()
+                n = min(self.sample_num, self.batch_size)
+                images = self.generate(zs[:n], None if cs is None else cs[:n], ema=ema, _synced=True)
+            if _samples is not None:
+                _samples.append(images)
+            return s.search(images, self.nn_k if k is None else k, bool(self.args.random_flip))
+
+    def save_neighbours(self, epoch, idx, folder=None, names=None):
+        """One --nn_freq event: for the moving averages and / or the live weights, as --sample_ema says, the grid
+        ``<model>_nn_EE_IIIII.png`` (``_nn_noema_``) of the up to 8 samples closest to a training image, each followed by its
+        neighbours, the table ``.txt`` beside it, the scalars ``nn_dist_min`` / ``nn_dist_mean`` and one "NN: ..." line.
+        Collective like ``save_samples``; returns the paths written."""
+        from . import neighbours
+        from .utils import check_folder
+        paths = []
+        for prefix, ema, wanted in (("nn", True, self.generate_ema_samples), ("nn_noema", False, self.generate_noema_samples)):
+            if not wanted:
+                continue
+            first = self._nn is None
+            samples = []
+            result = self.nearest(ema=ema, _samples=samples)                           # (collective: every rank enters)
+            if self.rank != 0:
+                continue
+            folder_ = self.sample_dir if folder is None else folder
+            check_folder(folder_)
+            which = neighbours.event_names(self.model_name, epoch, idx, prefix) if names is None else names[prefix]
+            paths += neighbours.write_event(result, samples[0].float().cpu().numpy(), self._nn_fetch, folder_, which)
+            scalars = neighbours.scalars(result, prefix)
+            if first:
+                print("NN: set of " + self._nn.plan.describe(), flush=True)
+            print("NN: " + ", ".join("%s: %.4f" % kv for kv in scalars.items()), flush=True)
+            if getattr(self, "_log_writer", None) is not None:                       # (--phase test opens no log)
+                self._log_writer.add_scalars(self.counter - 1, scalars)
+        return paths
+
     def test(self):
         """--phase test (BigGAN.py:1372-1395): load the latest checkpoint and write ``test_num`` grids of
         floor(sqrt(min(sample_num, batch_size)))^2 EMA samples to ``<result_dir>/<model_dir>/``.  With --swd_freq > 0 the
-        checkpoint's quality scores are printed and written to ``swd.txt`` beside them."""
+        checkpoint's quality scores are printed and written to ``swd.txt`` beside them; with --nn_freq > 0 the nearest
+        training images of its static samples go to ``nn.png`` / ``nn.txt`` (``nn_noema.*``)."""
         import numpy as np
         from .utils import save_images, check_folder
         could_load, _ = self.load(self.checkpoint_dir)
@@ -1914,6 +2034,9 @@ class BigGAN(GANBase):
                 with open(os.path.join(result_dir, "swd.txt"), "w") as f:
                     for k, v in scores.items():
                         f.write("%s\t%.6f\n" % (k, v))
+        if self.nn_freq > 0:
+            paths += self.save_neighbours(0, 0, folder=result_dir,
+                                          names={p: {"png": p + ".png", "txt": p + ".txt"} for p in ("nn", "nn_noema")})
         return paths
 
     # ---- --phase service (BigGAN.py:1298-1369) -----------------------------------------------

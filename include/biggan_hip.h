@@ -1028,6 +1028,30 @@ int    bg_swd_l1(const float* a, const float* b, int64_t n_per_out, int n_out, d
                  void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Nearest training images of generated samples, in pixel space (csrc/nearest.hip, neighbours.py; an addition to ABI 10:
+ * new symbols only).  Every launcher is stream-ordered and allocates nothing; no float atomics anywhere, so a repeated
+ * launch is bit-identical.  BG_ERR_ARG with a message for a NULL pointer, a bad dtype or a bad size.
+ *
+ * bg_nn_pack: x [B,S,S,C] (BG_F32 / BG_BF16), C in {1, 3, 4} -> out bf16 [B, (S/f)(S/f)C], the search descriptors: the
+ *   f x f box sum in fp32 (row-major order), times 1 / f^2, rounded to nearest even.  f is a power of two (1: a plain
+ *   convert), S / f >= 8.  mirror != 0: the descriptor of the horizontally flipped image (columns reversed, channel order
+ *   kept), bit-identical to packing the flipped batch.
+ * bg_nn_distances: q bf16 [Q,D], set bf16 [N,D], both 16-byte aligned, D a multiple of 64 -> out fp32 [Q,N],
+ *   out[i][n] = sum_j (q[i][j] - set[n][j])^2.  Every term is an fp32 difference squared into an fp32 sum (one fma); the
+ *   expansion |q|^2 + |s|^2 - 2 q.s is not used, so a set row equal to a query gives 0.0f exactly.  One wave makes each sum
+ *   in a fixed order.  Relative error at most (D + 2) u / (1 - (D + 2) u), u = 2^-24.
+ * bg_nn_topk: for each of the Q rows of dist fp32 [Q,N] (finite values) the k <= 16 smallest entries as (value, index),
+ *   ascending, ties to the lower index, into out_dist fp32 [Q,k] and out_idx int32 [Q,k]; places past N hold (+inf, -1).
+ *   Exact.  ws: bg_nn_topk_workspace_bytes(Q, N, k) bytes, 4-byte aligned (0 bytes, and then ws may be NULL, for rows that
+ *   one block scans).
+ * ------------------------------------------------------------------------------------------ */
+int    bg_nn_pack(const void* x, int x_dtype, int B, int S, int C, int f, int mirror, void* out, void* stream);
+int    bg_nn_distances(const void* q, const void* set, int Q, int64_t N, int D, float* out, void* stream);
+size_t bg_nn_topk_workspace_bytes(int Q, int64_t N, int k);
+int    bg_nn_topk(const float* dist, int Q, int64_t N, int k, float* out_dist, int32_t* out_idx, void* ws, size_t ws_bytes,
+                  void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
  * (conv / deconv / gemm families) is bracketed by hipEvents on its stream.
  * bg_prof_collect synchronises the events and returns totals since the last reset.
