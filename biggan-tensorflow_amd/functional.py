@@ -345,6 +345,61 @@ def nn_topk(dist, k):
     return ov, oi
 
 
+# ---- multi-scale structural similarity of image pairs (csrc/msssim.hip; metrics.py drives them).  No autograd anywhere. ----
+def msssim_workspace(P, H, C, device):
+    """The fp64 partial sums of all levels of P pairs of side H: what ``msssim_level`` fills and ``msssim_finish`` reduces."""
+    nb = int(lib().bg_msssim_workspace_bytes(int(P), int(H), int(C)))
+    if nb == 0:
+        raise RuntimeError("msssim_workspace: P=%d H=%d C=%d (P >= 1, H a power of two >= 16, C 1, 3 or 4)" % (P, H, C))
+    return torch.zeros(nb // 8, dtype=torch.float64, device=device)
+
+
+def msssim_level(a, b, H, level, ws, pool=None):
+    """One pyramid level of P pairs.  ``b`` None: ``a`` [2P,h,h,C] holds the pairs as rows (2p, 2p + 1); otherwise ``a``
+    and ``b`` are [P,h,h,C] each.  h = H >> level; fp32 or bf16 at level 0, fp32 below.  Fills the level's rows of ``ws``
+    (``msssim_workspace(P, H, C)``) and, with ``pool`` fp32 [2,P,h/2,h/2,C] (every level but the last), the 2 x 2 means
+    of both sets: the next level's ``a = pool[0]``, ``b = pool[1]``."""
+    a = _swd_images("msssim_level", a)
+    n, h, _, C = a.shape
+    if b is None:
+        if n < 2 or n % 2:
+            raise RuntimeError("msssim_level: %d images are not pairs" % n)
+        P, stride = n // 2, 2
+        pa = hip.ptr(a)
+        pb = hip.c_void_p(a.data_ptr() + h * h * C * a.element_size())
+    else:
+        b = _swd_images("msssim_level", b)
+        if b.shape != a.shape or b.dtype != a.dtype:
+            raise RuntimeError("msssim_level: a is %s %s, b is %s %s" % (a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+        P, stride = n, 1
+        pa, pb = hip.ptr(a), hip.ptr(b)
+    if h != int(H) >> int(level):
+        raise RuntimeError("msssim_level: level %d of side %d has side %d, got %d" % (level, H, int(H) >> int(level), h))
+    pw = _swd_typed("msssim_level", "ws", ws, torch.float64, (ws.numel(),))
+    pp = (None, None)
+    if pool is not None:
+        _swd_typed("msssim_level", "pool", pool, torch.float32, (2, P, h // 2, h // 2, C))
+        pp = (hip.ptr(pool[0]), hip.ptr(pool[1]))
+    check(lib().bg_msssim_level(pa, pb, dt(a), stride, P, int(H), int(level), C, pp[0], pp[1], pw, ws.numel() * 8, stream()))
+    return pool
+
+
+def msssim_level_sums(ws, P, H, C, level):
+    """The rows of ``ws`` that level ``level`` fills, as a view [P, tiles, C, 2]: per pair, 16 x 16 tile of window
+    positions and channel the sums of cs and of ssim (the levels follow one another; level i has (H >> i >> 4)^2 tiles)."""
+    tiles = [((int(H) >> i) // 16) ** 2 for i in range(int(level) + 1)]
+    lo = sum(tiles[:-1]) * int(P) * int(C) * 2
+    return ws[lo:lo + tiles[-1] * int(P) * int(C) * 2].view(int(P), tiles[-1], int(C), 2)
+
+
+def msssim_finish(ws, P, H, C, scores, row_offset=0):
+    """``ws`` (all levels filled) -> ``scores[row_offset : row_offset + P]`` fp64, one MS-SSIM score per pair."""
+    pw = _swd_typed("msssim_finish", "ws", ws, torch.float64, (ws.numel(),))
+    ps = _swd_typed("msssim_finish", "scores", scores, torch.float64, (scores.numel(),))
+    check(lib().bg_msssim_finish(pw, ws.numel() * 8, int(P), int(H), int(C), ps, scores.numel(), int(row_offset), stream()))
+    return scores
+
+
 def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
     the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns

@@ -285,6 +285,9 @@ SIGNATURES = {
     "bg_nn_distances": (c_int, [_P, _P, c_int, c_int64, c_int, _P, _P]),
     "bg_nn_topk_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
     "bg_nn_topk": (c_int, [_P, c_int, c_int64, c_int, _P, _P, _P, c_size_t, _P]),
+    "bg_msssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bg_msssim_level": (c_int, [_P, _P, c_int, c_int64, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "bg_msssim_finish": (c_int, [_P, c_size_t, c_int, c_int, c_int, _P, c_int64, c_int64, _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

@@ -69,8 +69,15 @@ FLAGS = [
 #   --nn_k K                neighbours per sample, 1..8
 #   --nn_size S             side of the search descriptors, a power of two >= 8; min(img_size, S) is used
 #   --nn_images M           the first M files of the listing; 0 (default): all of them (capped by BG_NN_GB, default 8 GiB)
+#   --msssim_freq N         every N iterations: the diversity score of the generator, the mean MS-SSIM of generated pairs that
+#                           share a class vector (metrics.py; lower is more diverse, 1.0 is collapse), as scalars msssim /
+#                           msssim_noema in the event file and one "MS-SSIM: ..." line; the first event adds msssim_real,
+#                           the same over random pairs of dataset images (dataset-wide, not per class); 0 (default) is
+#                           off.  --phase test: computed once
+#   --msssim_pairs P        generated pairs per event
 EXTRA_FLAGS = [("precision", T, None), ("swd_freq", I, 0), ("swd_images", I, 2048),
-               ("nn_freq", I, 0), ("nn_k", I, 3), ("nn_size", I, 64), ("nn_images", I, 0)]
+               ("nn_freq", I, 0), ("nn_k", I, 3), ("nn_size", I, 64), ("nn_images", I, 0),
+               ("msssim_freq", I, 0), ("msssim_pairs", I, 1024)]
 
 
 def build_parser():

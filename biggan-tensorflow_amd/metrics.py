@@ -6,7 +6,12 @@ the definition; csrc/swd.hip holds the kernels; tests/swd_ref.py restates the me
 ``SwdPlan`` is host arithmetic only: levels, the power-of-two image count, buffer sizes, seeds and the draws.  ``Swd``
 runs a plan on the device.  The metric has random generators of its own, derived from --static_sample_seed: nothing is
 drawn from the training run's generators, the sampler's, or the loader's, and every draw is made once per run, so
-consecutive events differ by the weights alone."""
+consecutive events differ by the weights alone.
+
+In-training diversity score: the mean multi-scale structural similarity (MS-SSIM; Wang, Simoncelli and Bovik 2003) of
+pairs of generated images that share a class vector (Odena et al. 2017), as ``msssim`` (lower is more diverse, 1.0 is
+collapse).  ``MsssimPlan`` / ``Msssim`` follow the same split and the same rules for draws; csrc/msssim.hip holds the
+kernels; tests/msssim_ref.py restates the metric in float64."""
 import numpy as np
 import torch
 
@@ -168,6 +173,165 @@ class Swd:
         out = {"%s_%d" % (prefix, side): float(v) for side, v in zip(p.sides, per_level)}
         out[prefix + "_avg"] = float(np.mean(per_level))
         return out
+
+
+# ---- in-training diversity score: mean MS-SSIM of generated pairs (csrc/msssim.hip; DESIGN.md gives the definition) ----
+MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli and Bovik 2003
+MS_TAPS, MS_SIGMA, MS_MIN_SIDE = 11, 1.5, 16
+
+
+def msssim_sides(img_size):
+    """[img_size, img_size / 2, ...]: L = min(5, log2(img_size) - 3) levels, the coarsest of at least 16 px: 32 px gives 2
+    levels, 64 px 3, 128 px 4, 256 px and more 5."""
+    img_size = int(img_size)
+    if img_size < MS_MIN_SIDE or img_size & (img_size - 1):
+        raise ValueError("msssim: --img_size %d: the pyramid needs a power of two >= %d" % (img_size, MS_MIN_SIDE))
+    levels = min(len(MS_WEIGHTS), img_size.bit_length() - 1 - 3)
+    return [img_size >> i for i in range(levels)]
+
+
+def msssim_weights(levels):
+    """The first ``levels`` of the published five weights over their sum.  (With fewer than five levels the score is this
+    project's convention and not comparable with published five-level numbers.)"""
+    w = np.asarray(MS_WEIGHTS[:int(levels)], dtype=np.float64)
+    return w / w.sum()
+
+
+class MsssimPlan:
+    """What one run of the diversity score needs, from the flags alone.
+
+    n_pairs       P = --msssim_pairs generated pairs; the two images of a pair have independent latents and, with
+                  --n_labels, one class vector (a row of the label table): the intra-class diversity of AC-GAN
+    n_real_pairs  pairs of the real baseline: P random pairs of the first 2 P dataset files (fewer when the dataset has
+                  fewer than 2 P files), or P pairs of uniform noise without a dataset
+    seeds         one per draw, derived from --static_sample_seed; none is shared with SwdPlan or NnPlan"""
+
+    def __init__(self, img_size, c_dim, batch_size, msssim_pairs, static_sample_seed, n_files=None):
+        if c_dim not in (1, 3, 4):
+            raise ValueError("msssim: c_dim %d (1, 3 or 4)" % c_dim)
+        self.sides = msssim_sides(img_size)
+        self.weights = msssim_weights(len(self.sides))
+        self.img_size, self.c_dim, self.batch_size = int(img_size), int(c_dim), int(batch_size)
+        self.n_pairs = int(msssim_pairs)
+        if self.n_pairs < 1:
+            raise ValueError("msssim: no pairs to measure (%d)" % self.n_pairs)
+        self.from_files = n_files is not None
+        self.n_real_pairs = self.n_pairs if n_files is None else min(self.n_pairs, int(n_files) // 2)
+        if self.n_real_pairs < 1:
+            raise ValueError("msssim: the real baseline needs two dataset files, there are %d" % int(n_files))
+        base = int(static_sample_seed)
+        self.seeds = {name: (base + 15485863 * (i + 1)) % (1 << 32)
+                      for i, name in enumerate(("latents", "labels", "real", "real_pairs"))}
+
+    # ---- sizes in bytes -------------------------------------------------------------------------
+    @property
+    def batch_pairs(self):
+        """The most pairs one ``add`` launches: a generator batch and the image carried over from the one before."""
+        return (self.batch_size + 1) // 2
+
+    @property
+    def tiles_per_pair(self):
+        return sum((s // 16) ** 2 for s in self.sides)
+
+    @property
+    def workspace_bytes(self):
+        """The fp64 partial sums of one generator batch: (cs, ssim) per pair, 16 x 16 tile, channel and level."""
+        return self.batch_pairs * self.tiles_per_pair * self.c_dim * 2 * 8
+
+    @property
+    def pyramid_bytes(self):
+        """The pooled fp32 images of one generator batch, both sets, every level below the first."""
+        return sum(2 * self.batch_pairs * s * s * self.c_dim * 4 for s in self.sides[1:])
+
+    @property
+    def score_bytes(self):
+        return self.n_pairs * 8
+
+    @property
+    def peak_bytes(self):
+        """All that exists during an event besides the generator's own batch: nothing of size P x S^2."""
+        return self.workspace_bytes + self.pyramid_bytes + self.score_bytes
+
+    # ---- draws -------------------------------------------------------------------------------------
+    def draw_latents(self, z_dim, trunc):
+        """fp32 [2 P, 1, 1, z_dim] (sampling.draw_z): rows 2 p and 2 p + 1 are pair p, drawn independently."""
+        g = torch.Generator(device="cpu")
+        g.manual_seed(self.seeds["latents"])
+        return Sp.draw_z(2 * self.n_pairs, z_dim, g, trunc)
+
+    def draw_labels(self, label_table):
+        """fp32 [2 P, n_labels]: one row of the label table per pair, drawn with replacement, for both of its images."""
+        rows = Sp.draw_n_tags(label_table, self.n_pairs, np.random.RandomState(self.seeds["labels"]))
+        return np.repeat(rows, 2, axis=0)
+
+    def draw_real_pairs(self):
+        """int64 [n_real_pairs, 2]: a random perfect matching of the first 2 n_real_pairs dataset files."""
+        perm = np.random.RandomState(self.seeds["real_pairs"]).permutation(2 * self.n_real_pairs)
+        return perm.reshape(self.n_real_pairs, 2).astype(np.int64)
+
+
+class Msssim:
+    """A plan on the device.  ``begin`` / ``add`` / ``finish``: images arrive a generator batch at a time, rows 2 p and
+    2 p + 1 of the stream being pair p.  A batch may hold an odd number of images, so the last image of one batch can be
+    the first of a pair that the next batch completes: it is carried.  Per batch one workspace and one pooled pyramid
+    exist; what stays is the fp64 score of every pair.  ``ops``: the launch wrappers (functional.py)."""
+
+    def __init__(self, plan, device, ops=None):
+        self.plan, self.device = plan, torch.device(device)
+        self.ops = Fn if ops is None else ops
+        self.fake_inputs = None                # (latents, class vectors or None), drawn once by the model
+        self.real = None                       # the real baseline, computed at the first event
+
+    def begin(self, n_pairs=None):
+        self._n = self.plan.n_pairs if n_pairs is None else int(n_pairs)
+        self._scores = torch.zeros(self._n, dtype=torch.float64, device=self.device)
+        self._images, self._pairs, self._carry = 0, 0, None
+
+    def _launch(self, x):
+        """x [2 p, S, S, C]: p pairs as consecutive rows -> their scores at rows ``self._pairs`` on."""
+        p, ops = self.plan, self.ops
+        n = int(x.shape[0]) // 2
+        ws = ops.msssim_workspace(n, p.img_size, p.c_dim, self.device)
+        a, b = x, None
+        for i, side in enumerate(p.sides):
+            pool = None
+            if i + 1 < len(p.sides):
+                pool = torch.empty(2, n, side // 2, side // 2, p.c_dim, dtype=torch.float32, device=self.device)
+            ops.msssim_level(a, b, p.img_size, i, ws, pool)
+            if pool is not None:
+                a, b = pool[0], pool[1]
+        ops.msssim_finish(ws, n, p.img_size, p.c_dim, self._scores, self._pairs)
+        self._pairs += n
+
+    def add(self, img):
+        """Images [b, S, S, C] (fp32 or bf16); those past 2 n_pairs (the padding of a last generator batch) are dropped."""
+        p = self.plan
+        b = min(int(img.shape[0]), 2 * self._n - self._images)
+        if b <= 0:
+            return
+        g = img[:b]
+        if tuple(g.shape[1:]) != (p.img_size, p.img_size, p.c_dim):
+            raise ValueError("msssim: images of %s, the plan is for %s" % (tuple(g.shape[1:]), (p.img_size, p.img_size, p.c_dim)))
+        self._images += b
+        if self._carry is not None:                        # the pair that straddles two batches
+            self._launch(torch.cat([self._carry.to(g.dtype), g[:1]]))
+            self._carry, g = None, g[1:]
+        even = (int(g.shape[0]) // 2) * 2
+        if even:
+            self._launch(g[:even])
+        if int(g.shape[0]) > even:
+            self._carry = g[even:].clone()
+
+    def finish(self):
+        """The mean of the pairs' scores, the doubles added on the host in index order."""
+        if self._images != 2 * self._n or self._pairs != self._n:
+            raise RuntimeError("msssim: %d of %d images arrived" % (self._images, 2 * self._n))
+        per_pair = self._scores.cpu().numpy()
+        self.per_pair, self._scores = per_pair, None
+        total = 0.0
+        for v in per_pair:
+            total += float(v)
+        return total / self._n
 
 
 def format_scores(scores):

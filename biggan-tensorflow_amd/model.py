@@ -183,6 +183,10 @@ class BigGAN(GANBase):
         self.nn_size = int(getattr(args, "nn_size", 64) or 64)
         self.nn_images = int(getattr(args, "nn_images", 0) or 0)
         self._nn = None                        # neighbours.NearestSet with the resident training set, built at the first event
+        # in-training diversity score (extension flags --msssim_freq / --msssim_pairs; metrics.py)
+        self.msssim_freq = int(getattr(args, "msssim_freq", 0) or 0)
+        self.msssim_pairs = int(getattr(args, "msssim_pairs", 1024) or 1024)
+        self._msssim = None                    # metrics.Msssim with the draws of the run, built at the first event
         self.recon_plan = self._recon_plan()
         self.deep = args.deep                                                          # BigGAN.py:20
         self.g_mixed_resblocks = args.g_mixed_resblocks                                # BigGAN.py:40-41
@@ -1572,6 +1576,13 @@ class BigGAN(GANBase):
                             self._log_writer.add_scalars(self.counter - 1, scores)
                 if self.nn_freq > 0 and self.counter % self.nn_freq == 0:
                     self.save_neighbours(epoch, idx + 1)                               # (collective: every rank enters)
+                if self.msssim_freq > 0 and self.counter % self.msssim_freq == 0:
+                    scores = self.msssim()                                             # (collective: every rank enters)
+                    if self.rank == 0:
+                        from .metrics import format_scores
+                        print("MS-SSIM: " + format_scores(scores), flush=True)
+                        if self._log_writer is not None:
+                            self._log_writer.add_scalars(self.counter - 1, scores)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
             if self._log_writer is not None:
@@ -1897,6 +1908,76 @@ class BigGAN(GANBase):
                     out.update(m.scores(m.finish(), prefix))
         return out
 
+    # ---- in-training diversity score (metrics.py) ------------------------------------------------
+    def msssim_plan(self, root="./dataset"):
+        from .metrics import MsssimPlan
+        files = self._swd_files(root)
+        return MsssimPlan(self.img_size, self.c_dim, self.batch_size, self.msssim_pairs, self.static_sample_seed,
+                          n_files=None if files is None else len(files))
+
+    def msssim_fake_inputs(self, plan):
+        """(latents [2P,1,1,z_dim], class vectors [2P,n_labels] or None): rows 2p and 2p + 1 are pair p - independent
+        latents with --z_trunc_train's truncation, one row of the label table for both - the same at every event."""
+        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
+        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
+
+    def msssim_real_batches(self, plan, root="./dataset"):
+        """The pairs of the real baseline as consecutive rows, at most ``batch_size`` images at a time on the device: with
+        a dataset folder a random matching of the first 2 ``plan.n_real_pairs`` files of the listing (the plan's draw),
+        decoded and resized by the host path without flips (never taken from the training loader); without one, uniform
+        noise from a generator of the metric's own."""
+        B, M = self.batch_size, 2 * plan.n_real_pairs
+        if plan.from_files:
+            import numpy as np
+            from . import data as D
+            image_data = D.ImageData(self.img_size, self.c_dim, True, False)
+            files = self._swd_files(root)
+            order = [files[i] for i in plan.draw_real_pairs().reshape(-1)]
+            for lo in range(0, M, B):
+                yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in order[lo:lo + B]])).to(self.device)
+        else:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(plan.seeds["real"])
+            for lo in range(0, M, B):
+                yield torch.rand(min(B, M - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
+                                 generator=gen) * 2.0 - 1.0
+
+    def msssim(self, root="./dataset"):
+        """The diversity score of the current weights: {``msssim``: the mean MS-SSIM of --msssim_pairs generated pairs} for
+        the moving averages and / or ``msssim_noema`` for the live weights, as --sample_ema says; lower is more diverse,
+        1.0 means that every pair is identical.  The first call adds ``msssim_real``, the same number over random pairs
+        of dataset images (dataset-wide, not per class).  The pairs are regenerated through ``generate`` a batch at a
+        time from latents and class vectors drawn once.  Every rank calls it (``sync_sharded_state`` is collective);
+        rank 0 computes, the others return {}.  Nothing the training run reads is changed."""
+        from . import metrics
+        self.sync_sharded_state()
+        if self.rank != 0:
+            return {}
+        with torch.no_grad():
+            out = {}
+            if self._msssim is None:
+                plan = self.msssim_plan(root)
+                m = metrics.Msssim(plan, self.device)
+                m.begin(plan.n_real_pairs)
+                for batch in self.msssim_real_batches(plan, root):
+                    m.add(batch)
+                m.real = m.finish()
+                m.fake_inputs = self.msssim_fake_inputs(plan)
+                self._msssim = m
+                real = m.real
+            else:
+                real = None
+            m = self._msssim
+            for name, ema, wanted in (("msssim", True, self.generate_ema_samples),
+                                      ("msssim_noema", False, self.generate_noema_samples)):
+                if wanted:
+                    m.begin()
+                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
+                    out[name] = m.finish()
+            if real is not None:
+                out["msssim_real"] = real
+        return out
+
     # ---- nearest training images (neighbours.py) -------------------------------------------------
     def nn_plan(self, root="./dataset"):
         from .neighbours import NnPlan
@@ -2012,7 +2093,8 @@ class BigGAN(GANBase):
         """--phase test (BigGAN.py:1372-1395): load the latest checkpoint and write ``test_num`` grids of
         floor(sqrt(min(sample_num, batch_size)))^2 EMA samples to ``<result_dir>/<model_dir>/``.  With --swd_freq > 0 the
         checkpoint's quality scores are printed and written to ``swd.txt`` beside them; with --nn_freq > 0 the nearest
-        training images of its static samples go to ``nn.png`` / ``nn.txt`` (``nn_noema.*``)."""
+        training images of its static samples go to ``nn.png`` / ``nn.txt`` (``nn_noema.*``); with --msssim_freq > 0 its
+        diversity scores are printed and written to ``msssim.txt``."""
         import numpy as np
         from .utils import save_images, check_folder
         could_load, _ = self.load(self.checkpoint_dir)
@@ -2037,6 +2119,14 @@ class BigGAN(GANBase):
         if self.nn_freq > 0:
             paths += self.save_neighbours(0, 0, folder=result_dir,
                                           names={p: {"png": p + ".png", "txt": p + ".txt"} for p in ("nn", "nn_noema")})
+        if self.msssim_freq > 0:
+            from .metrics import format_scores
+            scores = self.msssim()
+            if self.rank == 0:
+                print("MS-SSIM: " + format_scores(scores), flush=True)
+                with open(os.path.join(result_dir, "msssim.txt"), "w") as f:
+                    for k, v in scores.items():
+                        f.write("%s\t%.6f\n" % (k, v))
         return paths
 
     # ---- --phase service (BigGAN.py:1298-1369) -----------------------------------------------

@@ -1052,6 +1052,35 @@ int    bg_nn_topk(const float* dist, int Q, int64_t N, int k, float* out_dist, i
                   void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Multi-scale structural similarity of image pairs (Wang, Simoncelli and Bovik 2003; csrc/msssim.hip, metrics.py; an
+ * addition to ABI 10: new symbols only).  NHWC images in [-1, 1] with H = W a power of two >= 16, C in {1, 3, 4}; the
+ * arithmetic runs on u = (x + 1) / 2 with C1 = 0.01^2, C2 = 0.03^2, an 11-tap Gaussian window (sigma 1.5, no padding) and
+ * L = min(5, log2(H) - 3) levels, level i of side H >> i, weighted by the first L of (0.0448, 0.2856, 0.3001, 0.2363,
+ * 0.1333) over their sum.  Every launcher is stream-ordered and allocates nothing; every sum goes through partial rows
+ * added in index order (no float atomics), so a repeated launch is bit-identical.  BG_ERR_ARG with a message for a NULL
+ * pointer, a bad dtype or a bad size.
+ *
+ * bg_msssim_workspace_bytes: bytes of the fp64 partial sums of all L levels of P pairs of side H (0 for sizes that the
+ *   launches reject); level and finish of one batch of pairs share one such workspace, 8-byte aligned.  It holds, level
+ *   after level, fp64 [P][tiles][C][2] = (sum of cs, sum of ssim), tiles = ((H >> level) / 16)^2 in row-major tile order.
+ * bg_msssim_level: level `level` (0 .. L-1) of P pairs.  a, b: the level's images [*, h, h, C], h = H >> level, BG_F32 or
+ *   BG_BF16 at level 0 and BG_F32 below; pair p is image p * pair_stride of a and of b (pair_stride 1: two buffers of P
+ *   images; pair_stride 2 with b = a + one image: rows 2p and 2p + 1 of one batch).  Each image is read once.  Written:
+ *   the level's rows of ws, per (pair, 16 x 16 tile of window positions, channel) the sums of cs and of ssim = l * cs over
+ *   the tile's positions, each position evaluated in fp32 (separable window, horizontal pass first) and added in fp64;
+ *   and, unless the level is the last, pool_a and pool_b fp32 [P, h/2, h/2, C], the 2 x 2 means of the images,
+ *   ((p00 + p01) + (p10 + p11)) * 0.25 in fp32.  At the last level pool_a and pool_b are not written and may be NULL.
+ * bg_msssim_finish: scores[row_offset + p] for p < P, fp64: per channel the product over levels of
+ *   max(mean cs_i, 0)^w_i (the last level: mean ssim), means over the (h - 10)^2 positions, then the mean over channels.
+ *   scores holds n_scores doubles; row_offset + P <= n_scores.
+ * ------------------------------------------------------------------------------------------ */
+size_t bg_msssim_workspace_bytes(int P, int H, int C);
+int    bg_msssim_level(const void* a, const void* b, int dtype, int64_t pair_stride, int P, int H, int level, int C,
+                       float* pool_a, float* pool_b, double* ws, size_t ws_bytes, void* stream);
+int    bg_msssim_finish(const double* ws, size_t ws_bytes, int P, int H, int C, double* scores, int64_t n_scores,
+                        int64_t row_offset, void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
  * (conv / deconv / gemm families) is bracketed by hipEvents on its stream.
  * bg_prof_collect synchronises the events and returns totals since the last reset.
