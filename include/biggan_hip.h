@@ -396,8 +396,9 @@ int bg_spectral_norm_batch_bwd(const BgSnItem* items_dev, int n_items, const uin
 
 /* Forward-mode tangent of TRAINING-mode batch norm and its backward: the gradient penalty (BigGAN.py:717-742) through a
  * discriminator with --bn_in_d (ops.py:546-561).  x, xd, s are [rows, C] fp32.
- *   bg_chan_dots3            sums[0:C] = sum p, [C:2C] = sum p q, [2C:3C] = sum p r (r may be NULL) in fp64 (the caller
- *                            all-reduces them under data parallelism)
+ *   bg_chan_dots3            sums[0:C] = sum p, [C:2C] = sum p q, [2C:3C] = sum p r (r may be NULL: zeros) in fp64; the
+ *                            call zeroes sums itself and overwrites all 3C entries (the caller all-reduces them under
+ *                            data parallelism)
  *   bg_bn_tangent_fwd_coefs  from sums(p = xd, q = x): coefs[3C] with yd = coefs[0] xd + coefs[1] x + coefs[2] and m12[2C] =
  *                            (mean(xd) | mean(xd xhat)), kept for the backward
  *   bg_bn_tangent_bwd_coefs  from sums(p = s, q = x, r = xd), s = dL/dyd: coefs_dxd[3C] (d_xd = . s + . x + .), coefs_dx[4C]
@@ -496,7 +497,8 @@ int bg_maxpool2_bwd(const float* x, const float* dy, float* dx, int N, int H, in
 int bg_box2_down(const float* x, float* y, int N, int H, int W, int C, float scale, void* stream);
 int bg_box2_up(const float* x, float* y, int N, int H, int W, int C, float scale, void* stream);
 
-/* tf.nn.softmax over the last axis (ops.py:483): rows x cols, in place allowed; bwd: ds = p*(dp - sum(dp*p)) */
+/* tf.nn.softmax over the last axis (ops.py:483): rows x cols, cols <= 1024 (more: BG_ERR_UNSUPPORTED, nothing is launched;
+ * the same holds for bg_softmax_tangent_bwd), in place allowed (p == s); bwd: ds = p*(dp - sum(dp*p)) */
 int bg_softmax_fwd(const float* s, float* p, int64_t rows, int cols, void* stream);
 int bg_softmax_bwd(const float* p, const float* dp, float* ds, int64_t rows, int cols, void* stream);
 
@@ -612,10 +614,10 @@ int bg_diffaugment_bwd(const float* dy, float* dx, const float* u_s, const float
 
 /* --------------------------------------------------------------------------------------------
  * Hinge losses with flood (ops.py:788-797, 832-840, 847-848).
- *   sums: device float[2] accumulators (caller zeroes; all-reduced across ranks for DP):
- *     D: sums[0] += sum relu(1-real), sums[1] += sum relu(1+fake);   G: sums[0] += sum fake
+ *   sums: device float accumulators (caller zeroes; all-reduced across ranks for DP):
+ *     D (float[2]): sums[0] += sum relu(1-real), sums[1] += sum relu(1+fake);   G (float[1]): sums[0] += sum fake
  *   grad kernels read the (global) sums, n_global = global batch, and write the flooded loss
- *   (loss_out[0]) and d(loss)/d(logit).
+ *   (loss_out[0], nullable) and d(loss)/d(logit); where the loss equals flood exactly the gradient is +-0.
  * ------------------------------------------------------------------------------------------ */
 int bg_hinge_d_sums(const float* real, const float* fake, float* sums, int n, void* stream);
 int bg_hinge_d_grad(const float* real, const float* fake, const float* sums, double n_global, float flood,
@@ -626,10 +628,12 @@ int bg_hinge_g_grad(const float* sums, double n_global, float flood, float* d_fa
 
 /* General GAN losses (ops.py:753-840): kind 0 hinge, 1 lsgan, 2 gan (also 'dragan'), 3 ra-lsgan, 4 ra-gan (also
  * 'ra-dragan'), 5 ra-hinge, 6 wgan (wgan-gp / wgan-lp); generator = 0 for discriminator_loss, 1 for generator_loss.  Three steps so that data-parallel
- * ranks can exchange the sums in between:  bg_gan_loss_means -> sums = {sum real, sum fake};
+ * ranks can exchange the sums in between:  bg_gan_loss_means -> sums = {sum real, sum fake} (OVERWRITTEN - the hinge
+ * pair above accumulates, this one does not; sum real = 0 for nr = 0; tsums below is overwritten as well);
  * bg_gan_loss_terms (given the GLOBAL sums / counts) -> tsums = {sum phi_r, sum phi_f, sum phi_r', sum phi_f'};
  * bg_gan_loss_grad (given the GLOBAL tsums) -> loss (flooded), d_real, d_fake (incl. the coupling through the
- * batch means of the relativistic kinds).  real may be NULL with nr = 0 (non-relativistic generator losses). */
+ * batch means of the relativistic kinds).  real may be NULL with nr = 0 (non-relativistic generator losses; d_real is
+ * then not written).  loss_out may be NULL. */
 int bg_gan_loss_means(const float* real, const float* fake, float* sums, int nr, int nf, void* stream);
 int bg_gan_loss_terms(int kind, int generator, const float* real, const float* fake, const float* sums,
                       double n_real_global, double n_fake_global, float* tsums, int nr, int nf, void* stream);
@@ -648,11 +652,13 @@ int bg_gan_loss_grad(int kind, int generator, const float* real, const float* fa
  *                    x^ = real + alpha_n * 0.5 * std(real) * other (sums = {sum real, sum real^2} in fp64 from
  *                         bg_bn_stats with C = 1, count = numel: BigGAN.py:719-724, other = eps ~ U[0,1))
  * bg_gp_penalty: g [N, per] -> *loss = ld * sum_n phi(||g_n||) / count_global (this rank's share of the mean),
- *                v = the direction above; ws: 2*N doubles of scratch; lp = 1 selects wgan-lp.
+ *                v = the direction above (a row of norm 0 gets v = 0); ws: 2*N doubles, zeroed by the call: on return
+ *                ws[0:N] = ||g_n||^2 and ws[N:2N] = the factor of g_n in v_n; lp = 1 selects wgan-lp.
  * bg_maxpool2_gather: tangent of the 2x2 max pool, y = t at the first maximum of x's window (its transpose is
  *                bg_maxpool2_bwd).
  * bg_prelu_tangent_dalpha: the PReLU tangent is ydot = xdot * prelu'(x) (computed by bg_prelu_bwd with dy := xdot);
- *                its derivative w.r.t. alpha is dalpha[c] = sum_rows dy * xdot * [x < 0]  (1/2 at x == 0).
+ *                its derivative w.r.t. alpha is dalpha[c] = sum_rows dy * xdot * [x < 0]  (1/2 at x == 0); dalpha is
+ *                overwritten (the call zeroes it; bg_prelu_bwd_t's dalpha accumulates).
  * bg_softmax_tangent_bwd: the softmax tangent is pdot = p * (sdot - sum p sdot) (computed by bg_softmax_bwd with
  *                dp := sdot); given g = dL/dpdot:  dsdot = p * (g - u), dp = g * (sdot - t) - u * sdot,
  *                t = sum p sdot, u = sum g p (row sums).
