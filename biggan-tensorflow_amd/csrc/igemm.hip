@@ -17,6 +17,9 @@
 #include "igemm_dev.h"
 #include "igemm_bf16.h"
 #include "igemm16.h"
+#include "igemm16_plan.h"
+#include <stdio.h>
+#include <string.h>
 
 
 namespace bg {
@@ -631,7 +634,8 @@ static inline bool route_ring(Route r) { return r == BF16_RING || r == BF16_THIN
 
 // Everything about a call that follows from its descriptor alone: the route and the parameter block the route launches
 // (nn / nn16 / tn / tn16, tensor pointers null; the others stay zero).  The entry point binds the pointers and the
-// pointer-dependent vec flag; the query returns plan_workspace_bytes.
+// pointer-dependent vec flag; the query returns plan_workspace_bytes.  For the bf16 routes plan_launch16 adds the launch
+// plans (igemm16_plan.h: kernel, form, tiles, split-K, grid) once the workspace the caller hands is known.
 struct ConvPlan {
     Route route;
     NNParams nn;            // F32_* routes; the BF16_* routes derive nn16 from it
@@ -645,6 +649,11 @@ struct ConvPlan {
     int zdim, niter_min;    // grid z (stride phases or batch), fewest K iterations of a block
     int64_t out_elems;      // elements of the launch's output (= of one split-K slab)
     size_t grid_bytes;      // *_PADDED_FOLD: 256-byte-aligned size of the padded grid at the head of the workspace, else 0
+    Tune16 tune;            // bf16 routes: the switches, read once when the plan function of the pass chose the route
+    bool planned16;         // plan_launch16 has filled the three below
+    NN16Launch l16;         // BF16_* routes: the plain (or thin depth-to-space) launch
+    NN16Launch ring16;      // route_ring: the mirrored-tap launch that follows it
+    TN16Launch lt16;        // TN_BF16
 };
 
 struct NNPlan {
@@ -1088,6 +1097,7 @@ static ConvPlan plan_nn_pass(const BgConvDesc* d, bool deconv, bool grad) {
 // the bf16-resident form of pl.nn; out_f32 from the dtype of the tensor the pass writes
 static void plan_resident(ConvPlan& pl, Route route, int out_dtype) {
     pl.route = route;
+    pl.tune = tune16();
     nn16_from(pl.nn, pl.nn16);
     pl.nn16.out_f32 = out_dtype == BG_F32;
 }
@@ -1111,7 +1121,8 @@ static void plan_padded_grid(const BgConvDesc* d, ConvPlan& pl, size_t elem_byte
 }
 
 // d2s_block = 2 (bg_conv2d_fwd_d2s): the same launch with the depth-to-space store (NN16Params::d2s_c) where d describes
-// one; d2s_c stays 0 where it does not.  Whether the kernel form the launch takes has that store is nn16_d2s_ok's answer.
+// one; d2s_c stays 0 where it does not.  Whether the kernel form the launch takes has that store is its plan's answer
+// (NN16Launch::d2s_store).
 static ConvPlan plan_conv_fwd(const BgConvDesc* d, int d2s_block = 0) {
     ConvPlan pl = plan_nn_pass(d, false, false);
     if (!resident_fwd(d)) return pl;
@@ -1132,7 +1143,7 @@ static ConvPlan plan_conv_dgrad(const BgConvDesc* d) {
         if (padded) plan_padded_grid(d, pl, d->x_dtype == BG_F32 ? 4 : 2);
         plan_resident(pl, padded ? BF16_PADDED_FOLD : (ring ? BF16_RING : BF16_PLAIN), d->x_dtype);
         // 8-channel image layers, stride 2: one 2 x 2-window launch (igemm16.hip) in place of the tap / halo-tile one
-        if (!padded && nn16h_d2s_ok(pl.nn16)) pl.route = ring ? BF16_THIN_D2S_RING : BF16_THIN_D2S;
+        if (!padded && nn16h_d2s_ok(pl.tune, pl.nn16)) pl.route = ring ? BF16_THIN_D2S_RING : BF16_THIN_D2S;
         return pl;
     }
     // The ONE pass that plans for uneven phases.  The fp32 transposed-conv forward has the same uneven k3 s2 phases and
@@ -1175,6 +1186,7 @@ static ConvPlan plan_wgrad(const BgConvDesc* d, bool deconv) {
     };
     if (resident_wgrad(d)) {
         pl.route = TN_BF16;
+        pl.tune = tune16();
         fill(pl.tn16);
     } else {
         pl.route = TN_F32;
@@ -1223,6 +1235,7 @@ static ConvPlan plan_gemm(const BgGemmDesc* d) {
 static ConvPlan plan_gram16(int rows, int cols, int ld) {
     ConvPlan pl{};
     pl.route = TN_BF16;
+    pl.tune = tune16();
     pl.mode = GATHER_PLAIN;
     TN16Params& p = pl.tn16;
     p.g.ld = ld; p.b_ld = ld;
@@ -1230,18 +1243,35 @@ static ConvPlan plan_gram16(int rows, int cols, int ld) {
     return pl;
 }
 
+static inline bool route_thin(Route r) { return r == BF16_THIN_D2S || r == BF16_THIN_D2S_RING; }
+
+// The launch plans of a bf16 route for the workspace a caller hands.  have_ws: a non-null pointer (behind the padded grid
+// of a *_PADDED_FOLD route); (true, (size_t)-1) is the plan the workspace query reads.
+static void plan_launch16(ConvPlan& pl, bool have_ws, size_t ws_bytes) {
+    pl.planned16 = true;
+    if (pl.route == TN_BF16) {
+        pl.lt16 = plan_tn16_launch(pl.tune, pl.tn16, pl.mode, have_ws, ws_bytes);
+    } else if (pl.route != TN_F32 && !route_f32(pl.route)) {
+        pl.l16 = route_thin(pl.route) ? plan_nn16h_d2s_launch(pl.nn16)
+                                      : plan_nn16_launch(pl.tune, pl.nn16, pl.mode, pl.zdim, pl.out_elems, have_ws, ws_bytes);
+        if (route_ring(pl.route)) pl.ring16 = plan_nn16_ring_launch(pl.tune, pl.nn16, pl.nn16.g.stride == 1 ? 2 : 1);
+    }
+}
+
 static size_t plan_workspace_bytes(const ConvPlan& pl) {
     if (pl.route == TN_F32) return tn_workspace_bytes(pl.tn.Mf, pl.tn.Cb, pl.tn.batch, pl.tn.M);
-    if (pl.route == TN_BF16) return tn16_workspace_bytes(pl.tn16);
-    const size_t slabs = route_f32(pl.route) ? nn_workspace_bytes(pl)
-                                             : nn16_workspace_bytes(pl.nn16, pl.mode, pl.zdim, pl.out_elems);
+    if (pl.route == TN_BF16) return plan_tn16_launch(pl.tune, pl.tn16, pl.mode, true, (size_t)-1).ws_bytes;
+    // (a thin depth-to-space route answers the plain launch's slabs too: callers have always sized by them)
+    const size_t slabs = route_f32(pl.route)
+                             ? nn_workspace_bytes(pl)
+                             : plan_nn16_launch(pl.tune, pl.nn16, pl.mode, pl.zdim, pl.out_elems, true, (size_t)-1).ws_bytes;
     return pl.grid_bytes ? align256(slabs) + pl.grid_bytes : slabs;
 }
 
-// bytes of the partial batch-norm sums a deconv forward with fused statistics writes (0: no such launch)
+// bytes of the partial batch-norm sums a deconv forward with fused statistics writes (0: no such launch); pl: planned
 static size_t plan_stats_bytes(const BgConvDesc* d, const ConvPlan& pl) {
     if (pl.route != BF16_PLAIN || d->y_dtype != BG_BF16) return 0;
-    return (size_t)nn16_stats_rows(pl.nn16, pl.mode, pl.zdim) * 2 * (size_t)d->Cout * sizeof(float);
+    return (size_t)pl.l16.stats_rows * 2 * (size_t)d->Cout * sizeof(float);
 }
 
 // ---- running a plan ----
@@ -1273,16 +1303,17 @@ static int run_nn(ConvPlan& pl, const BgConvDesc* d, const char* op, bool deconv
     } else {
         NN16Params& r = pl.nn16;
         r.A = src; r.B = w; r.bias = bias; r.alpha = alpha_dev; r.out = target; r.accumulate = acc;
-        NN16Params q = r;                       // (the launch fills in its tiling: the ring launch starts from the plain block)
-        if (pl.route == BF16_THIN_D2S || pl.route == BF16_THIN_D2S_RING)
-            rc = launch_nn16h_d2s(r, s);
+        if (!pl.planned16) plan_launch16(pl, ws != nullptr, ws_bytes);
+        NN16Params q = r;                       // (the ring launch starts from the plain block)
+        if (route_thin(pl.route))
+            rc = launch_nn16h_d2s(r, pl.l16, s);
         else
-            rc = launch_nn16(r, pl.mode, pl.zdim, pl.out_elems, ws, ws_bytes, s);
+            rc = launch_nn16(r, pl.l16, pl.out_elems, ws, s);
         if (!rc && route_ring(pl.route)) {
             q.ring = 1;
             q.ring_lines = d->stride == 1 ? 2 : 1;
             q.accumulate = 1;
-            rc = launch_nn16_ring(q, s);
+            rc = launch_nn16_ring(q, pl.ring16, s);
         }
     }
     if (rc || !pl.grid_bytes) return rc;
@@ -1297,7 +1328,8 @@ static int run_tn(ConvPlan& pl, const BgConvDesc* d, const char* op, bool deconv
     ProfScope prof(as_stream(stream), conv_flops(d, deconv), tag.s, tag.bytes);
     if (pl.route == TN_BF16) {
         pl.tn16.A = a; pl.tn16.Bv = b;
-        return launch_tn16(pl.tn16, pl.mode, dw, ws, ws_bytes, as_stream(stream));
+        plan_launch16(pl, ws != nullptr, ws_bytes);
+        return launch_tn16(pl.tn16, pl.lt16, dw, ws, as_stream(stream));
     }
     pl.tn.A = (const float*)a; pl.tn.Bv = (const float*)b;
     const bool vec = (d->Cin % 4 == 0) && (d->Cout % 4 == 0) && aligned16(a) && aligned16(b);
@@ -1316,7 +1348,12 @@ size_t bg_conv2d_wgrad_workspace_bytes(const BgConvDesc* d) { return d ? plan_wo
 size_t bg_deconv2d_fwd_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_deconv_fwd(d)) : 0; }
 size_t bg_deconv2d_dgrad_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_deconv_dgrad(d)) : 0; }
 size_t bg_deconv2d_wgrad_workspace_bytes(const BgConvDesc* d) { return d ? plan_workspace_bytes(plan_deconv_wgrad(d)) : 0; }
-size_t bg_deconv2d_fwd_stats_workspace_bytes(const BgConvDesc* d) { return d ? plan_stats_bytes(d, plan_deconv_fwd(d)) : 0; }
+size_t bg_deconv2d_fwd_stats_workspace_bytes(const BgConvDesc* d) {
+    if (!d) return 0;
+    ConvPlan pl = plan_deconv_fwd(d);
+    plan_launch16(pl, true, (size_t)-1);
+    return plan_stats_bytes(d, pl);
+}
 size_t bg_gemm_workspace_bytes(const BgGemmDesc* d) { return d ? plan_workspace_bytes(plan_gemm(d)) : 0; }
 size_t bg_gram16_workspace_bytes(int rows, int cols) {
     return rows > 0 && cols > 0 ? plan_workspace_bytes(plan_gram16(rows, cols, cols)) : 0;
@@ -1337,9 +1374,10 @@ int bg_conv2d_fwd(const BgConvDesc* d, const void* x, const void* w, const float
 
 int bg_conv2d_fwd_d2s_supported(const BgConvDesc* d, int block) {
     if (!d) return 0;
-    const ConvPlan pl = plan_conv_fwd(d, block);
+    ConvPlan pl = plan_conv_fwd(d, block);
     if (!pl.nn16.d2s_c || check_conv(d) != BG_OK) return 0;
-    return nn16_d2s_ok(pl.nn16, pl.mode, pl.zdim) ? 1 : 0;
+    plan_launch16(pl, false, 0);               // (the fused launch is handed no workspace)
+    return pl.l16.d2s_store ? 1 : 0;
 }
 
 int bg_conv2d_fwd_d2s(const BgConvDesc* d, const void* x, const void* w, const float* bias, const float* alpha_dev,
@@ -1348,7 +1386,8 @@ int bg_conv2d_fwd_d2s(const BgConvDesc* d, const void* x, const void* w, const f
     if (rc) return rc;
     BG_REQUIRE(x && w && y, "bg_conv2d_fwd_d2s: null tensor pointer");
     ConvPlan pl = plan_conv_fwd(d, block);
-    BG_REQUIRE(pl.nn16.d2s_c && nn16_d2s_ok(pl.nn16, pl.mode, pl.zdim),
+    if (pl.nn16.d2s_c) plan_launch16(pl, false, 0);
+    BG_REQUIRE(pl.nn16.d2s_c && pl.l16.d2s_store,
                "bg_conv2d_fwd_d2s: this launch has no fused depth-to-space store (query bg_conv2d_fwd_d2s_supported)");
     (void)ws; (void)ws_bytes;                  // supported launches never split K
     return run_nn(pl, d, "conv2d_fwd_d2s", false, x, w, bias, alpha_dev, y, 0, nullptr, 0, stream);
@@ -1397,6 +1436,7 @@ int bg_deconv2d_fwd_stats(const BgConvDesc* d, const void* x, const void* w, con
     if (rc) return rc;
     BG_REQUIRE(x && w && y && sums && stats_ws, "bg_deconv2d_fwd_stats: null tensor pointer");
     ConvPlan pl = plan_deconv_fwd(d);
+    plan_launch16(pl, ws != nullptr, ws_bytes);
     const size_t need = plan_stats_bytes(d, pl);
     BG_REQUIRE(need > 0 && d->w_packed, "bg_deconv2d_fwd_stats: this launch has no fused statistics (query the workspace)");
     BG_REQUIRE(stats_ws_bytes >= need && (reinterpret_cast<uintptr_t>(stats_ws) & 15) == 0,
@@ -1428,6 +1468,74 @@ int bg_deconv2d_wgrad(const BgConvDesc* d, const void* x, const void* dy, float*
     if (pl.route == TN_F32)
         BG_REQUIRE(d->x_dtype == BG_F32 && d->y_dtype == BG_F32, "bg_deconv2d_wgrad: x and dy must both be fp32 or both bf16");
     return run_tn(pl, d, "deconv2d_wgrad", true, dy, x, dw, ws, ws_bytes, stream);
+}
+
+int bg_conv_plan_describe(const BgConvDesc* d, int pass, size_t ws_bytes, char* buf, size_t buf_bytes) {
+    BG_REQUIRE(d && buf && buf_bytes > 0, "bg_conv_plan_describe: null descriptor or buffer");
+    BG_REQUIRE(pass >= BG_PASS_CONV_FWD && pass <= BG_PASS_CONV_FWD_D2S, "bg_conv_plan_describe: unknown pass %d", pass);
+    const bool deconv = pass >= BG_PASS_DECONV_FWD && pass <= BG_PASS_DECONV_WGRAD;
+    if (const int rc = deconv ? check_deconv(d) : check_conv(d)) return rc;
+    ConvPlan pl = pass == BG_PASS_CONV_FWD        ? plan_conv_fwd(d)
+                  : pass == BG_PASS_CONV_DGRAD    ? plan_conv_dgrad(d)
+                  : pass == BG_PASS_CONV_WGRAD    ? plan_conv_wgrad(d)
+                  : pass == BG_PASS_DECONV_FWD    ? plan_deconv_fwd(d)
+                  : pass == BG_PASS_DECONV_DGRAD  ? plan_deconv_dgrad(d)
+                  : pass == BG_PASS_DECONV_WGRAD  ? plan_deconv_wgrad(d)
+                                                  : plan_conv_fwd(d, 2);
+    static const char* const routes[] = {"F32_TAP", "F32_MIRROR", "F32_PADDED_FOLD", "BF16_PLAIN", "BF16_RING",
+                                         "BF16_PADDED_FOLD", "BF16_THIN_D2S", "BF16_THIN_D2S_RING", "TN_F32", "TN_BF16"};
+    static const char* const forms[] = {"two", "ring", "wide", "phased"};
+    const bool query = ws_bytes == (size_t)-1;
+    const size_t asked = plan_workspace_bytes(pl);
+    if (query) ws_bytes = asked;
+    if (pass == BG_PASS_CONV_FWD_D2S) ws_bytes = 0;        // (bg_conv2d_fwd_d2s hands its launch no workspace)
+    BG_REQUIRE(ws_bytes >= pl.grid_bytes, "bg_conv_plan_describe: workspace too small for the padded gradient");
+    ws_bytes -= pl.grid_bytes;
+    char line[1024];
+    int n = snprintf(line, sizeof(line), "route=%s", routes[pl.route]);
+    auto add = [&](const char* fmt, auto... v) {
+        if (n < (int)sizeof(line)) n += snprintf(line + n, sizeof(line) - n, fmt, v...);
+    };
+    char name[48];
+    size_t used = pl.grid_bytes;
+    auto launch = [&](long long gx, int gz, int block, int lds, int rows, int cols, const char* form, int splitk, int pm,
+                      int mf, int zf, long long stats, int d2s) {      // the fields every bf16 route has
+        add("; kernel=%s; grid=%lld*1*%d; block=%d; lds=%d; tile=%dx%d; form=%s; splitk=%d; posmajor=%d; mfast=%d; zfold=%d; "
+            "stats_rows=%lld; d2s=%d", name, gx, gz, block, lds, rows, cols, form, splitk, pm, mf, zf, stats, d2s);
+    };
+    if (pl.route == TN_BF16) {
+        plan_launch16(pl, ws_bytes > 0, ws_bytes);
+        const TN16Launch& l = pl.lt16;
+        tn16_launch_name(l, name, sizeof(name));
+        launch(l.grid_x, 1, l.block, tn16_launch_lds(l), l.kernel == TN16_NARROW ? 128 : 256,
+               l.kernel == TN16_PHASED ? l.bn : (l.kernel == TN16_WIDE ? 128 * l.nbi : 128),
+               l.kernel == TN16_PHASED ? "phased" : (l.kernel == TN16_WIDE ? "wide" : "narrow"), l.splitk, 0, 0, 0, 0, 0);
+        add("; rows_per_split=%d", l.rows_per_split);
+        used = l.ws_bytes;
+    } else if (pl.route != TN_F32 && !route_f32(pl.route)) {
+        plan_launch16(pl, ws_bytes > 0, ws_bytes);
+        const NN16Launch& l = pl.l16;
+        nn16_launch_name(l, name, sizeof(name));
+        const bool halo = l.family == NN16_HALO || l.family == NN16_HALO_D2S;
+        launch(l.grid_x, l.grid_z, l.block, nn16_launch_lds(l), l.block == 512 ? 256 : 128, 32 * l.tn,
+               halo ? "halo" : forms[l.form], l.splitk, l.posmajor, l.mfast, l.zfold, l.stats_rows, l.d2s_store);
+        if (halo) add("; nt=%d; nf=%d", l.nt, l.nf);
+        if (route_ring(pl.route)) {
+            const NN16Launch& r = pl.ring16;
+            nn16_launch_name(r, name, sizeof(name));
+            add("; ring_kernel=%s; ring_grid=%lld*1*1; ring_tile=128x%d; ring_form=%s; ring_lds=%d", name,
+                (long long)r.grid_x, 32 * r.tn, forms[r.form], nn16_launch_lds(r));
+        }
+        if (pl.grid_bytes) add("; fold_grid_bytes=%zu; fold_grid=%dx%d", pl.grid_bytes, pl.nn.g.Ho, pl.nn.g.Wo);
+        used += route_thin(pl.route) ? 0 : l.ws_bytes;
+    } else {
+        used = asked;                                      // (fp32 routes: the route and the query's answer only)
+    }
+    add("; ws=%zu", query ? asked : used);
+    BG_REQUIRE(n < (int)sizeof(line) && (size_t)n < buf_bytes, "bg_conv_plan_describe: buffer of %zu bytes too small",
+               buf_bytes);
+    memcpy(buf, line, (size_t)n + 1);
+    return BG_OK;
 }
 
 int bg_gemm(const BgGemmDesc* d, const float* A, const float* B, const float* bias, const float* alpha_dev,
@@ -1462,9 +1570,10 @@ int bg_gram16(const void* a, int rows, int cols, int ld, float* out, void* ws, s
     BG_REQUIRE(cols % 8 == 0 && ld % 8 == 0, "bg_gram16: cols and ld must be multiples of 8");
     ConvPlan pl = plan_gram16(rows, cols, ld);
     pl.tn16.A = a; pl.tn16.Bv = a;
+    plan_launch16(pl, ws != nullptr, ws_bytes);
     Tag tag("gram16", cols, cols, rows);
     ProfScope prof(as_stream(stream), 2.0 * rows * (double)cols * cols, tag.s);
-    return launch_tn16(pl.tn16, pl.mode, out, ws, ws_bytes, as_stream(stream));
+    return launch_tn16(pl.tn16, pl.lt16, out, ws, as_stream(stream));
 }
 
 }  // extern "C"

@@ -44,7 +44,7 @@ struct NN16Params {
     int32_t ring_lines;     // 2: both borders mirror (stride 1); 1: only the low border does (stride 2, even maps)
     int32_t d2s_c;          // > 0 (stride-1 forward gathers, N = 4 d2s_c, d2s_c % 8 == 0): the epilogue stores depth-to-space -
                             // out is [Nb, 2 Ho, 2 Wo, d2s_c] and column (2 i + j) d2s_c + c of pixel (ho, wo) goes to channel c
-                            // of pixel (2 ho + i, 2 wo + j) (ops.py:23-27 subpixel_conv); launches that pass nn16_d2s_ok only
+                            // of pixel (2 ho + i, 2 wo + j) (ops.py:23-27 subpixel_conv); launches whose plan has NN16Launch::d2s_store only
 };
 
 struct TN16Params {
@@ -64,21 +64,22 @@ struct TN16Params {
     int32_t wq_shift, hq_shift;
 };
 
-// conv-family entry points of the bf16-resident path (called from igemm.hip's extern "C" functions)
-size_t nn16_workspace_bytes(const NN16Params& p, int mode, int zdim, int64_t out_elems);
-int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, size_t ws_bytes, hipStream_t s);
-// rows of NN16Params::stats_part a launch would write (0: the launch does not take the halo-tile form - no fused statistics)
-int64_t nn16_stats_rows(const NN16Params& p, int mode, int zdim);
+// Launchers of the bf16-resident path (called from igemm.hip's extern "C" functions).  Each runs a plan of igemm16_plan.h,
+// which is also what the workspace / statistics / depth-to-space queries read: a launcher decides nothing.
+struct NN16Launch;
+struct TN16Launch;
+// the plain launch of a forward pass / input gradient (plan_nn16_launch); ws: the split-K slabs or null
+int launch_nn16(NN16Params& p, const NN16Launch& l, int64_t out_elems, void* ws, hipStream_t s);
 // the mirrored-tap launch of a reflect-padded convolution's input gradient (p.ring = 1, p.ring_lines, p.g of the plain
-// launch, accumulate = 1): see NN16Params::ring
-int launch_nn16_ring(NN16Params& p, hipStream_t s);
-// whether a forward gather with p.d2s_c set takes a kernel form whose epilogue has the depth-to-space store: the halo-tile
-// form, or the tap kernel with image-major rows and no split-K
-bool nn16_d2s_ok(const NN16Params& p, int mode, int zdim);
-bool nn16h_d2s_ok(const NN16Params& p);                    // 8-channel stride-2 input gradients: depth-to-space halo form
-int launch_nn16h_d2s(const NN16Params& plain, hipStream_t s);
-size_t tn16_workspace_bytes(const TN16Params& p);
-int launch_tn16(TN16Params& p, int mode, float* final_out, void* ws, size_t ws_bytes, hipStream_t s);
+// launch, accumulate = 1; plan_nn16_ring_launch): see NN16Params::ring
+int launch_nn16_ring(NN16Params& p, const NN16Launch& l, hipStream_t s);
+// 8-channel stride-2 input gradients: the depth-to-space halo form (plan_nn16h_d2s_launch)
+int launch_nn16h_d2s(const NN16Params& plain, const NN16Launch& l, hipStream_t s);
+// weight gradients and Gram matrices (plan_tn16_launch); ws: the split-K slabs or null
+int launch_tn16(TN16Params& p, const TN16Launch& l, float* final_out, void* ws, hipStream_t s);
+// dynamic LDS bytes of the instantiation a plan names (the kernels' own constexpr sizes)
+int nn16_launch_lds(const NN16Launch& l);
+int tn16_launch_lds(const TN16Launch& l);
 // dx[b,h,w,:] (+)= sum of the padded-grid gradient dxp[b,i,j,:] over the padded positions (i,j) that tf.pad(REFLECT)
 // filled from pixel (h,w) (the transpose of ops.py:82's padding); f32: both tensors fp32, else both bf16
 int launch_reflect_fold(const void* dxp, void* dx, int f32, int N, int H, int W, int C, int Hp, int Wp, int pad_lo,

@@ -39,6 +39,7 @@
 #include "common.h"
 #include "igemm.h"
 #include "igemm16.h"
+#include "igemm16_plan.h"
 #include <type_traits>
 #include "igemm_dev.h"
 
@@ -2009,405 +2010,95 @@ int launch_reflect_fold(const void* dxp, void* dx, int f32, int N, int H, int W,
 }
 
 // ------------------------------------------------------------------------------------------
-// host side
+// host side: the launchers run the plans of igemm16_plan.h
 // ------------------------------------------------------------------------------------------
-struct NN16Plan {
-    int tn, splitk;
-};
+static_assert(P16_BM == NN16_BM && P16_HALO_T == NH_T && P16_TN_BK == TN16_BK, "igemm16_plan.h counts with other tiles");
 
-static int nn16_steps_min(const NN16Params& p, int mode) {
-    int per_axis = p.g.k;
-    if (mode == GATHER_TCONV && p.g.pstep > 1) per_axis = max(1, p.g.k / p.g.stride);
-    return (per_axis * per_axis * (p.C >> 3) + 7) >> 3;
+// An instantiation: the kernel and its dynamic LDS bytes.
+struct NN16Inst { void (*fn)(NN16Params); int lds; };
+struct TN16Inst { void (*fn)(TN16Params); int lds; };
+
+// nn16_kernel<TN, MODE, PM, RING, SLOTS, WM> by pipeline form.  RING: a mirrored-tap launch (position-major, two stages or
+// the 128-row ring); the wide form has image-major rows only (nn16_form).
+template <int TN, int MODE, bool PM, bool RING>
+static NN16Inst nn16_inst_form(int form) {
+    constexpr int TAPS = RING ? NN16_RING_TAPS : NN16_TAPS;
+    if (form == NN16_FORM_RING) return {&nn16_kernel<TN, MODE, PM, RING, 3, 2>, nn16_pipe_lds_bytes(TN, 2, TAPS)};
+    if constexpr (!PM)
+        if (form == NN16_FORM_WIDE) return {&nn16_kernel<TN, MODE, PM, false, 3, 4>, nn16_pipe_lds_bytes(TN, 4)};
+    return {&nn16_kernel<TN, MODE, PM, RING, 2, 2>, nn16_lds_bytes(TN, TAPS)};
 }
 
-// Fraction of the (row, tap) pairs of a launch that have a source pixel: 1 for reflect-padded forward gathers, 16 / 36
-// for the input gradient of a 3 x 3 convolution on the padded 6 x 6 grid of a 4 x 4 map.  Separable per axis.
-static double nn16_axis_fraction(const Gather& g, int mode, int nq, int n_src) {
-    int64_t valid = 0, slots = 0;
-    for (int ph = 0; ph < (mode == GATHER_TCONV ? g.pstep : 1); ++ph) {
-        int k0 = 0, kstep = 1, nk = g.k;
-        if (mode == GATHER_TCONV && g.pstep > 1) {
-            kstep = g.stride;
-            k0 = (ph + g.pad) % g.stride;
-            nk = (g.k - k0 + g.stride - 1) / g.stride;
-        }
-        for (int q = 0; q < nq; ++q) {
-            const int o = q * g.pstep + ph;
-            for (int i = 0; i < nk; ++i) {
-                const int kk = k0 + i * kstep;
-                bool ok;
-                if (mode == GATHER_CONV) {
-                    const int src = o * g.stride + kk - g.pad;
-                    ok = g.reflect || (src >= 0 && src < n_src);
-                } else {
-                    const int hn = o + g.pad - kk;
-                    ok = hn >= 0 && hn % g.stride == 0 && hn / g.stride < n_src;
-                }
-                valid += ok;
-            }
-            slots += nk;
-        }
+template <int MODE, bool PM, bool RING = false>
+static NN16Inst nn16_inst_tn(const NN16Launch& l) {
+    if constexpr (!RING)
+        if (l.form == NN16_FORM_PHASED)                // (tn: the form's own column tile, 4, 6 or 8)
+            return l.tn == 8   ? NN16Inst{&nn16_kernel<8, MODE, PM, false, 2, 4>, nn16x_lds_bytes(8)}
+                   : l.tn == 6 ? NN16Inst{&nn16_kernel<6, MODE, PM, false, 2, 4>, nn16x_lds_bytes(6)}
+                               : NN16Inst{&nn16_kernel<4, MODE, PM, false, 2, 4>, nn16x_lds_bytes(4)};
+    switch (l.tn) {
+        case 1: return nn16_inst_form<1, MODE, PM, RING>(l.form);
+        case 2: return nn16_inst_form<2, MODE, PM, RING>(l.form);
+        case 3: return nn16_inst_form<3, MODE, PM, RING>(l.form);
+        default: return nn16_inst_form<4, MODE, PM, RING>(l.form);
     }
-    return slots ? (double)valid / (double)slots : 1.0;
-}
-
-// Position-major rows (NN16Params::posmajor) when at least a tenth of the tap walk would run on the zero page and a
-// 128-row tile covers few positions (BG_NN16_POSMAJOR=0 switches it off; read per call so that a test can compare).
-static double nn16_posmajor_fraction(const NN16Params& p, int mode) {
-    const char* e = getenv("BG_NN16_POSMAJOR");
-    if (e && atoi(e) == 0) return 1.0;
-    const Gather& g = p.g;
-    if (g.k <= 1 || g.Nb < 16 || g.Hq <= 0 || g.Wq <= 0 || (int64_t)g.Hq * g.Wq > 40 * 40) return 1.0;
-    const double f = nn16_axis_fraction(g, mode, g.Hq, g.Hs) * nn16_axis_fraction(g, mode, g.Wq, g.Ws);
-    return f < 0.9 ? f : 1.0;
-}
-
-// Tile width and split-K by a round model: the grid runs in rounds of `slots` co-resident blocks (2 per CU); a block's
-// time is its K steps x (A-side work + one unit per 32 output columns).  Fewer, wider tiles waste padded columns and
-// can leave the last round (or the only one) mostly empty; narrow ones re-read the A tile more often.
-static NN16Plan plan_nn16(const NN16Params& p, int mode, int zdim, bool allow_split) {
-    static const int slots = getenv("BG_NN16_SLOTS") ? atoi(getenv("BG_NN16_SLOTS")) : 512;
-    const int64_t tm = (p.M + NN16_BM - 1) / NN16_BM;
-    int steps = nn16_steps_min(p, mode);
-    const double pm = nn16_posmajor_fraction(p, mode);
-    if (pm < 1.0) steps = max(1, (int)(steps * pm + 0.5));       // taps without sources are not walked
-    NN16Plan best{4, 1};
-    double best_cost = 1e30;
-    for (int tn = 4; tn >= 1; --tn) {
-        const int bn = 32 * tn;
-        const int64_t tiles = tm * ((p.N + bn - 1) / bn) * zdim;
-        const double unit = 1.5 + tn;
-        const int max_sk = allow_split ? (steps / 4 < 16 ? (steps / 4 < 1 ? 1 : steps / 4) : 16) : 1;
-        for (int sk = 1; sk <= max_sk; ++sk) {
-            const int64_t rounds = (tiles * sk + slots - 1) / slots;
-            double cost = (double)rounds * ((steps + sk - 1) / sk + 2.0) * unit;     // + prologue / epilogue per block
-            if (sk > 1) cost += 6.0 * unit + 0.02 * sk * (double)tiles / slots * bn; // reduce launch + slab traffic
-            if (cost < best_cost - 1e-9) {
-                best_cost = cost;
-                best = NN16Plan{tn, sk};
-            }
-        }
-    }
-    return best;
-}
-
-size_t nn16_workspace_bytes(const NN16Params& p, int mode, int zdim, int64_t out_elems) {
-    const NN16Plan pl = plan_nn16(p, mode, zdim, true);
-    return pl.splitk > 1 ? (size_t)pl.splitk * out_elems * sizeof(float) : 0;
-}
-
-static int nn16_mfast(const NN16Params& p, int tiles_m, int tiles_n);
-
-// Which pipeline form of nn16_kernel a launch takes (see the kernel's header).  The forms give bit-identical results, so
-// this is a matter of speed alone; the plan (tile width, split-K) does not depend on it.
-//   tn: the plan's tile width; row_blocks: 256-row tiles x stride phases x K splits of the launch; even_phases: every
-//   stride phase walks the same number of taps; mirrored: a mirrored-tap launch (NN16Params::ring), which has no 8-wave
-//   instantiation; *xtn: the phased form's own column tile BN / 32 (the plan's tn is for the 128-row tile).
-// BG_NN16_PIPE (read per call: tests/test_gpu_nn16_pipe.py and test_gpu_nn16_phased.py compare the forms) = 0: two stages
-// everywhere, 1: the ring form at the 128-row block wherever it applies, 2: the wide form wherever it applies, 3: the phased
-// form wherever it applies; unset: the rule below.  BG_NN16X_BN = 128 | 192 | 256 (read per call; the tests and
-// tools/kbench.py only) overrides the phased form's column tile.
-//
-// The rule, from the per-layer tables of profiles/nn16_pipe_ab.txt (config 3 at 256 and at 32 images, forward / input
-// gradient, ms, two stages -> wide form):
-//   C <= 192 per tap, image-major rows, a grid of at least one round of blocks (2 per CU) - the wide form:
-//       conv 96 -> 192 k3 s2 at 64^2 0.33 / 0.45 -> 0.27 / 0.39, 192 -> 384 k3 s2 at 32^2 0.20 / 0.27 -> 0.18 / 0.25, input
-//       gradients of the k4 s2 transposed convs 192 -> 96 at 64^2 0.93 -> 0.81 and 384 -> 192 at 32^2 0.65 -> 0.62, the 1 x 1
-//       convs 192 -> 96 0.14 / 0.23 -> 0.13 / 0.19, 96 -> 192 0.22 / 0.14 -> 0.19 / 0.13, 192 -> 24 input gradient 0.20 -> 0.14.
-//       These layers re-read activations, not weights: the 256-row tile halves the weight-tile traffic per row and its
-//       ring keeps two tiles in flight per block.
-//   32-column tiles (192 -> 24 forward: 0.091 -> 0.097), the ring forms at C >= 384 (within +-0.01 of the two-stage form at
-//       256 images, up to 20 % slower at 32, where the 256-row grid falls under one round) and position-major rows: two stages.
-//   C >= 384 per tap, image-major rows or position-major rows with Nb % 256 == 0, a grid of WHOLE rounds of one block per CU -
-//       the phased form (profiles/nn16x_phase_ab.txt; config 3 at 256 images, ms per call, two stages -> BN 128 / 192 / 256,
-//       forward ; input gradient; blocks at BN 128 / 192 / 256):
-//         deconv 4^2 1536 -> 1536 k4 s2    0.341 -> 0.318 / 0.300 / 0.333 ; 0.348 -> 0.333 / 0.318 / 0.343   (768 / 512 / 384)
-//         deconv 8^2 1536 -> 1536 k3       0.617 -> 0.627 / 0.566 / 0.678 ; 0.605 -> 0.600 / 0.548 / 0.651   (768 / 512 / 384)
-//         deconv 8^2 1536 -> 768 k4 s2     0.639 -> 0.559 / 0.493 / 0.466 (1536 / 1024 / 768) ; 0.539 -> 0.531 / 0.482 / 0.574
-//         deconv 16^2 768 -> 384 k4 s2     (forward: halo kernel) ; 0.586 -> 0.607 / 0.559 / 0.515   (1536 / 1024 / 768)
-//         deconv 32^2 384 -> 192 k4 s2     (forward: halo kernel) ; 0.644 -> 0.660 / 0.583 / 0.702   (3072 / 2048 / 2048)
-//         conv 16^2 384 -> 768 k3 s2       0.159 -> 0.170 / 0.152 / 0.176 ; 0.224 -> 0.243 / 0.218 / 0.246
-//         conv 8^2 768 -> 768 k3           0.298 -> 0.311 / 0.275 / 0.329 ; 0.408 -> 0.419 / 0.384 / 0.441   (768 / 512 / 384)
-//         conv 8^2 768 -> 1536 k3 s2       0.186 -> 0.193 / 0.178 / 0.208 ; 0.260 -> 0.261 / 0.248 / 0.255
-//         conv 4^2 1536 -> 1536 k3         0.323 -> 0.334 / 0.298 / 0.350 ; 0.552 -> 0.552 / 0.534 / 0.560   (768 / 512 / 384)
-//       (repeat spread of a layer: 0.001 - 0.006).  The form runs ONE block per CU, so what decides is whether the grid comes
-//       out in whole rounds of 256 blocks: BN = 256 wins only where it does (768 blocks: 1330 TF/s on 1536 -> 768 k4 s2) and
-//       loses at 384 blocks = 1.5 rounds; BN = 128 fills the rounds but fetches 3/4 of the two-stage form's L2 -> LDS bytes
-//       per FLOP and ties it.  1536, 768 and 384 output channels are whole multiples of 192, and 192-column tiles bring every
-//       one of these launches to 512, 1024 or 2048 blocks.  Hence: BN = 256 when N % 256 == 0, the grid is whole rounds at
-//       256 columns and the stride phases are even (k3 s2 phases walk 1 / 2 / 2 / 4 taps: 768 -> 1536 k3 s2 input gradient,
-//       1536 blocks at BN 256, is slower there than at 192); otherwise BN = 192 when 192-column tiles pad N to no more columns
-//       than the plan's own tiles do (N % 192 == 0 here; at N = 256, 512 or 1024 they would add 12 - 50 % of MFMA work, at
-//       N <= 64 many times the plan's - none of those measured, all left on two stages), the grid leaves at most 1/16 of the
-//       256 slots of its last round empty, however many rounds there are (a round half empty costs BN = 256 the 8 - 10 %
-//       the form gains) and, with uneven phases, has at least two rounds (768 -> 1536 k3 s2 input gradient at 256 images, ONE round of 256 blocks: 0.195 -> 0.215 per call in the
-//       step, the CUs that drew a 1-tap phase idle while the 4-tap blocks finish; at 512 images, two rounds, 0.259 -> 0.251);
-//       otherwise two stages.  At 32 images the rule leaves most of these launches on two stages and every C >= 384 layer is
-//       within the repeat spread (0.002 - 0.008 ms) of BG_NN16_PIPE=0.  Grids of partly filled rounds other than the 1.5
-//       above: not measured.
-//   The ring at the 128-row block is the default nowhere: where it gains (the C <= 192 layers above) the wide form gains
-//       more, and on the C >= 768 maps of 4^2 ... 8^2 it LOSES 25 - 40 % (1536 -> 1536 k3 at 8^2: 0.62 -> 0.87): those launches
-//       stream 10 - 40 MB of weights through L2 and a 32-channel stage reads only half of every 128-byte line per
-//       LDS-DMA, so each line is requested twice, one step apart - with three blocks per CU streaming 48 KB per step
-//       through the CU's 32 KB vector cache in between.  It stays behind the switch for the comparison.
-enum { NN16_FORM_TWO = 0, NN16_FORM_RING = 1, NN16_FORM_WIDE = 2, NN16_FORM_PHASED = 3 };
-constexpr int NN16X_CUS = 256;                // one phased block per CU (plan_nn16 counts 512 slots of two blocks per CU)
-static int nn16_form(const NN16Params& p, int tn, int64_t row_blocks, bool even_phases, bool mirrored, int* xtn) {
-    // The 256-row forms on position-major rows: a position-major tile walks the taps that ITS rows have sources under, so a
-    // 256-row tile would walk other taps (and split K elsewhere) than the two 128-row tiles it replaces - other sums -
-    // unless it lies inside one position, as both of those tiles then do: Nb % 256 == 0.  The wide form has no
-    // position-major instantiation at all.
-    const bool wide_ok = !mirrored && !p.posmajor && p.g.Ws < (1 << 15);   // (the ring forms keep source columns as int16)
-    const bool phased_ok = !mirrored && (!p.posmajor || p.g.Nb % 256 == 0);
-    const int64_t wide_blocks = row_blocks * ((p.N + 32 * tn - 1) / (32 * tn));
-    // BN of the phased form by the rule (0: the rule leaves the launch on two stages)
-    const int64_t nb256 = row_blocks * ((p.N + 255) / 256), nb192 = row_blocks * ((p.N + 191) / 192);
-    const int64_t last192 = (nb192 + NN16X_CUS - 1) / NN16X_CUS * NN16X_CUS - nb192;      // empty slots of the last round
-    // columns the 192-wide tiles pad N to, against the plan's own tiles: never more MFMA work than the plan's
-    const int pad192 = (p.N + 191) / 192 * 192, pad_plan = (p.N + 32 * tn - 1) / (32 * tn) * (32 * tn);
-    int bn = 0;
-    if (phased_ok && p.C >= 384) {
-        if (p.N % 256 == 0 && nb256 % NN16X_CUS == 0 && even_phases) bn = 256;
-        else if (pad192 <= pad_plan && nb192 >= (even_phases ? 1 : 2) * NN16X_CUS && last192 * 16 <= NN16X_CUS) bn = 192;
-    }
-    const int rule_bn = bn;
-    if (bn == 0) bn = p.N <= 128 ? 128 : (p.N <= 192 ? 192 : 256);       // (forced by the switch)
-    if (const char* e = getenv("BG_NN16X_BN")) {
-        const int v = atoi(e);
-        if (v == 128 || v == 192 || v == 256) bn = v;
-    }
-    *xtn = bn / 32;
-    if (const char* e = getenv("BG_NN16_PIPE")) {
-        const int v = atoi(e);
-        if (v == 3) return phased_ok ? NN16_FORM_PHASED : NN16_FORM_TWO;
-        if (v == 2) return wide_ok ? NN16_FORM_WIDE : NN16_FORM_TWO;
-        return (v == 1 && p.g.Ws < (1 << 15)) ? NN16_FORM_RING : NN16_FORM_TWO;
-    }
-    if (rule_bn) return NN16_FORM_PHASED;
-    return (wide_ok && p.C <= 192 && tn >= 2 && wide_blocks >= 512) ? NN16_FORM_WIDE : NN16_FORM_TWO;
-}
-
-// ring launches (NN16Params::ring): mirrored taps of the gradient of tf.pad(REFLECT), accumulated into dx
-template <int TN, int SLOTS = 2>
-static int launch_nn16_ring_inst(const NN16Params& p, dim3 grid, hipStream_t s) {
-    constexpr int lds = SLOTS == 3 ? nn16_pipe_lds_bytes(TN, 2, NN16_RING_TAPS) : nn16_lds_bytes(TN, NN16_RING_TAPS);
-    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16_kernel<TN, GATHER_TCONV, true, true, SLOTS>), lds)) return BG_ERR_LAUNCH;
-    hipLaunchKernelGGL((nn16_kernel<TN, GATHER_TCONV, true, true, SLOTS>), grid, dim3(256), lds, s, p);
-    return BG_OK;
-}
-template <int TN>
-static int launch_nn16_ring_tn(const NN16Params& p, int form, dim3 grid, hipStream_t s) {
-    return form == NN16_FORM_RING ? launch_nn16_ring_inst<TN, 3>(p, grid, s) : launch_nn16_ring_inst<TN>(p, grid, s);
-}
-
-int launch_nn16_ring(NN16Params& p, hipStream_t s) {
-    BG_REQUIRE(p.ring == 1 && (p.ring_lines == 1 || p.ring_lines == 2), "nn16 ring launch: ring = 1, ring_lines 1 or 2");
-    BG_REQUIRE(p.g.k >= 1 && p.g.k <= NN16_RING_TAPS / 2 && p.g.Ho >= 4 && p.g.Wo >= 4 && p.accumulate == 1,
-               "nn16 ring launch: kernel size %d / map %d x %d not supported", p.g.k, p.g.Ho, p.g.Wo);
-    BG_REQUIRE(p.C % 8 == 0 && p.N % 8 == 0 && p.g.ld % 8 == 0 && p.out_ld % 8 == 0, "nn16 ring launch: channels %% 8");
-    const int npos = p.ring_lines * p.g.Wo + p.ring_lines * (p.g.Ho - p.ring_lines);
-    p.g.pstep = 1;
-    p.g.Hq = 1;
-    p.g.Wq = npos;
-    p.M = p.g.Nb * npos;
-    p.posmajor = 1;
-    p.splitk = 1;                       // (slabs live in output coordinates: a ring launch touches a few lines of them)
-    p.slabs = nullptr;
-    p.zfold = 0;
-    p.pow2 = 0;
-    int tn = 4, best = 1 << 30;
-    for (int c = 4; c >= 1; --c) {      // least padded output channels; ties: the wider tile
-        const int padded = (p.N + 32 * c - 1) / (32 * c) * (32 * c);
-        if (padded < best) { best = padded; tn = c; }
-    }
-    p.tiles_m = (p.M + NN16_BM - 1) / NN16_BM;
-    p.tiles_n = (p.N + 32 * tn - 1) / (32 * tn);
-    p.mfast = nn16_mfast(p, p.tiles_m, p.tiles_n);
-    dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
-    int xtn;
-    const int form = nn16_form(p, tn, 0, true, true, &xtn);
-    int rc;
-    switch (tn) {
-        case 1: rc = launch_nn16_ring_tn<1>(p, form, grid, s); break;
-        case 2: rc = launch_nn16_ring_tn<2>(p, form, grid, s); break;
-        case 3: rc = launch_nn16_ring_tn<3>(p, form, grid, s); break;
-        default: rc = launch_nn16_ring_tn<4>(p, form, grid, s); break;
-    }
-    if (rc) return rc;
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-template <int TN, int MODE, bool PM, int SLOTS = 2, int WM = 2>
-static int launch_nn16_inst(const NN16Params& p, dim3 grid, hipStream_t s) {
-    constexpr int lds = SLOTS == 3 ? nn16_pipe_lds_bytes(TN, WM) : (WM == 4 ? nn16x_lds_bytes(TN) : nn16_lds_bytes(TN));
-    // > 48 KB of dynamic LDS needs the opt-in once per kernel and device
-    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16_kernel<TN, MODE, PM, false, SLOTS, WM>), lds)) return BG_ERR_LAUNCH;
-    if (SLOTS == 2 && WM == 2) prof_kernel("nn16_kernel<%d, %d, %s>", TN, MODE, PM ? "true" : "false");
-    else prof_kernel("nn16_kernel<%d, %d, %s, false, %d, %d>", TN, MODE, PM ? "true" : "false", SLOTS, WM);
-    hipLaunchKernelGGL((nn16_kernel<TN, MODE, PM, false, SLOTS, WM>), grid, dim3(128 * WM), lds, s, p);
-    return BG_OK;
-}
-
-template <int TN, int MODE, bool PM>
-static int launch_nn16_tn(const NN16Params& p, int form, dim3 grid, hipStream_t s) {
-    if (form == NN16_FORM_RING) return launch_nn16_inst<TN, MODE, PM, 3, 2>(p, grid, s);
-    if constexpr (!PM)                             // (nn16_form: image-major rows only)
-        if (form == NN16_FORM_WIDE) return launch_nn16_inst<TN, MODE, PM, 3, 4>(p, grid, s);
-    return launch_nn16_inst<TN, MODE, PM>(p, grid, s);
-}
-
-template <int MODE, bool PM>
-static int launch_nn16_pm(const NN16Params& p, int tn, int form, dim3 grid, hipStream_t s) {
-    if (form == NN16_FORM_PHASED)                  // (tn: the form's own column tile, 4, 6 or 8)
-        return tn == 8   ? launch_nn16_inst<8, MODE, PM, 2, 4>(p, grid, s)
-               : tn == 6 ? launch_nn16_inst<6, MODE, PM, 2, 4>(p, grid, s)
-                         : launch_nn16_inst<4, MODE, PM, 2, 4>(p, grid, s);
-    switch (tn) {
-        case 1: return launch_nn16_tn<1, MODE, PM>(p, form, grid, s);
-        case 2: return launch_nn16_tn<2, MODE, PM>(p, form, grid, s);
-        case 3: return launch_nn16_tn<3, MODE, PM>(p, form, grid, s);
-        default: return launch_nn16_tn<4, MODE, PM>(p, form, grid, s);
-    }
-}
-
-template <int MODE>
-static int launch_nn16_mode(const NN16Params& p, int tn, int form, dim3 grid, hipStream_t s) {
-    return p.posmajor ? launch_nn16_pm<MODE, true>(p, tn, form, grid, s) : launch_nn16_pm<MODE, false>(p, tn, form, grid, s);
-}
-
-// ---- halo-tile form: which launches take it ----
-static int nn16h_taps(const NN16Params& p, int mode, int zdim) {
-    // On by default (BG_NN16_HALO=0 switches it off; read per call so that a test can compare both forms).  Measured r02,
-    // config 3 at batch 256: forward sum over the 22 layer shapes 10.62 -> 9.18 ms, input gradients 12.31 -> 11.65 ms;
-    // transposed conv 96 -> 96 at 128^2: 600 -> 825 TF/s, 768 -> 768 at 16^2: 1083 -> 1198 (forward), 1276 (input gradient).
-    const char* e = getenv("BG_NN16_HALO");
-    const int use = e ? atoi(e) : 1;
-    static const int cmax = getenv("BG_NN16_HALO_CMAX") ? atoi(getenv("BG_NN16_HALO_CMAX")) : 4096;
-    const Gather& g = p.g;
-    if (!use || p.C > cmax || p.C % 32 || p.N % 8 || g.Hq < NH_T || g.Wq < NH_T || g.Hq % NH_T || g.Wq % NH_T) return 0;
-    if (mode == GATHER_CONV) return (g.stride == 1 && g.k == 3 && g.pstep == 1 && zdim == 1) ? 3 : 0;
-    if (g.reflect) return 0;
-    if (g.stride == 1 && g.k == 3 && g.pstep == 1 && zdim == 1) return 3;
-    if (g.stride == 2 && g.k == 4 && g.pstep == 2 && zdim == 4) return 2;
-    // r03: the stride phases of a 3 x 3 stride-2 transposed gather (input gradients of the discriminator's down-sampling
-    // convolutions): windows of 1 x 1, 1 x 2, 2 x 1 and 2 x 2 taps inside the 2 x 2 halo.  OFF by default (BG_NN16_HALO_K3S2=1
-    // turns it on): measured on config 3 at batch 256, tap kernel -> this form: 64^2 96 <- 192: 0.435 -> 0.402 ms per call,
-    // 32^2 192 <- 384: 0.29 -> 0.37 - a block of the 1-tap phase loads a 17 x 17 halo and stores a full patch for a
-    // quarter of the MFMA work, so the halo's saving in L2 -> LDS bytes does not pay.
-    if (g.stride == 2 && g.k == 3 && g.pad == 1 && g.pstep == 2 && zdim == 4) {
-        const char* e3 = getenv("BG_NN16_HALO_K3S2");
-        return (e3 && atoi(e3) == 1) ? 2 : 0;
-    }
-    return 0;
-}
-
-template <int NT, int NF, int MODE, int THIN = 0>
-static int launch_nn16h_inst(const NN16Params& p, int blocks, hipStream_t s) {
-    constexpr int lds = nn16h_lds_bytes<NT, NF>();
-    if (!lds_opt_in(reinterpret_cast<const void*>(&nn16h_kernel<NT, NF, MODE, THIN>), lds)) return BG_ERR_LAUNCH;
-    if (THIN) prof_kernel("nn16h_kernel<%d, %d, %d, d2s>", NT, NF, MODE);
-    else prof_kernel("nn16h_kernel<%d, %d, %d>", NT, NF, MODE);
-    hipLaunchKernelGGL((nn16h_kernel<NT, NF, MODE, THIN>), dim3(blocks), dim3(512), lds, s, p);
-    return BG_OK;
 }
 
 template <int NT, int MODE>
-static int launch_nn16h_nf(const NN16Params& p, int nf, int blocks, hipStream_t s) {
+static NN16Inst nn16h_inst_nf(int nf) {
     switch (nf) {
-        case 1: return launch_nn16h_inst<NT, 1, MODE>(p, blocks, s);
-        case 2: return launch_nn16h_inst<NT, 2, MODE>(p, blocks, s);
-        case 3: return launch_nn16h_inst<NT, 3, MODE>(p, blocks, s);
-        default: return launch_nn16h_inst<NT, 4, MODE>(p, blocks, s);
+        case 1: return {&nn16h_kernel<NT, 1, MODE>, nn16h_lds_bytes<NT, 1>()};
+        case 2: return {&nn16h_kernel<NT, 2, MODE>, nn16h_lds_bytes<NT, 2>()};
+        case 3: return {&nn16h_kernel<NT, 3, MODE>, nn16h_lds_bytes<NT, 3>()};
+        default: return {&nn16h_kernel<NT, 4, MODE>, nn16h_lds_bytes<NT, 4>()};
     }
 }
 
-// The THIN = 1 form of nn16h_kernel (see there): p describes the plain transposed gather (A = dy [Nb, Hs, Ws, C], B = the
-// packed [9][8][C] kernel, out = dx [Nb, 2 Hs, 2 Ws, 8]).
-bool nn16h_d2s_ok(const NN16Params& p) {
-    const char* e = getenv("BG_THIN_D2S");              // (read per call: a test compares both forms)
-    const int use = e ? atoi(e) : 1;
-    const Gather& g = p.g;
-    return use && p.N == 8 && p.out_ld == 8 && g.k == 3 && g.stride == 2 && g.pad == 1 && !g.reflect && p.C % 32 == 0 &&
-           g.Hs % NH_T == 0 && g.Ws % NH_T == 0 && g.Ho == 2 * g.Hs && g.Wo == 2 * g.Ws && !p.bias && !p.stats_part;
-}
-int launch_nn16h_d2s(const NN16Params& plain, hipStream_t s) {
-    BG_REQUIRE(nn16h_d2s_ok(plain), "nn16h depth-to-space form: unsupported geometry");
-    NN16Params p = plain;
-    Gather& g = p.g;
-    g.Hq = g.Hs; g.Wq = g.Ws; g.pstep = 1; g.pad = 0; g.stride = 1;
-    p.N = 32;
-    p.splitk = 1; p.mfast = 0; p.ring = 0;
-    const int64_t blocks = (int64_t)g.Nb * (g.Hq / NH_T) * (g.Wq / NH_T);
-    BG_REQUIRE(blocks > 0 && blocks < (int64_t(1) << 31), "nn16h: grid out of range");
-    if (const int rc = launch_nn16h_inst<2, 1, GATHER_CONV, 1>(p, (int)blocks, s)) return rc;
-    BG_LAUNCH_CHECK();
-    return BG_OK;
-}
-
-// Which operand should stay in an XCD's L2 (4 MB) while the other streams: estimated fabric bytes of the two tile orders.
-// OFF by default: measured r03 (config 3, batch 256, same box): N-tiles fastest 100.9 ms / iteration, this rule 102.0, M-tiles
-// fastest everywhere 103.7 - the weight slabs the N-fastest order re-fetches once per M-tile (round 2's FETCH_SIZE counters:
-// 1.9 GB per launch on the 4 x 4 ... 16 x 16 layers) come out of the 256 MB Infinity Cache, not out of HBM, and cost no time,
-// while M-fastest makes every co-resident block miss on its own gathered rows.  BG_NN16_MFAST=auto applies the rule, =1
-// forces M-fastest (for counter runs).
-static int nn16_mfast(const NN16Params& p, int tiles_m, int tiles_n) {
-    const char* e = getenv("BG_NN16_MFAST");
-    if (!e) return 0;
-    if (strcmp(e, "auto") != 0) return atoi(e) != 0;
-    const double l2 = 3.0e6;
-    const double a_bytes = 2.0 * p.g.Nb * (double)p.g.Hs * p.g.Ws * p.g.ld;
-    const double w_bytes = 2.0 * p.g.k * p.g.k * (double)p.N * p.C;
-    const double nfast = a_bytes + (w_bytes > l2 ? w_bytes * tiles_m : w_bytes);
-    const double mfast = w_bytes + (a_bytes > l2 ? a_bytes * tiles_n : a_bytes);
-    return mfast < nfast;
-}
-
-static int launch_nn16h(NN16Params& p, int mode, int ntaps, hipStream_t s) {
-    int nf = 4, best = 1 << 30;
-    // (c = 1, a 32-column tile, r03: the generator's 96 -> 3 (8) image layer - a quarter of the padded MFMA work of the
-    //  64-column tile and the input read once instead of once per tap by the tap kernel)
-    // Least padded output channels; ties: the wider tile.  N = 384 / 768 pad alike at 128 and 96 columns; measured on
-    // config 3 at batch 256 (profiles/halo_ring_ab.txt; NF = 4 against NF = 3, forward / input gradient, ms):
-    // 16^2 768 -> 384 k4s2 0.53 against 0.59, 32^2 384 -> 384 k3 0.55 / 0.55 against 0.61 / 0.60, 16^2 768 -> 768 k3 0.53 / 0.53
-    // against 0.58 / 0.56 - the narrower tile loads the halo 4/3 times as often.
-    for (int c = 4; c >= 1; --c) {
-        const int padded = (p.N + 32 * c - 1) / (32 * c) * (32 * c);
-        if (padded < best) { best = padded; nf = c; }
+// THE dispatch of the forward / input-gradient launches: plan fields -> instantiation
+static NN16Inst nn16_inst(const NN16Launch& l) {
+    switch (l.family) {
+        case NN16_HALO_D2S: return {&nn16h_kernel<2, 1, GATHER_CONV, 1>, nn16h_lds_bytes<2, 1>()};
+        case NN16_HALO:
+            if (l.mode == GATHER_CONV) return nn16h_inst_nf<3, GATHER_CONV>(l.nf);
+            return l.nt == 3 ? nn16h_inst_nf<3, GATHER_TCONV>(l.nf) : nn16h_inst_nf<2, GATHER_TCONV>(l.nf);
+        case NN16_MIRROR_RING: return nn16_inst_tn<GATHER_TCONV, true, true>(l);
+        default:
+            if (l.mode == GATHER_CONV)
+                return l.posmajor ? nn16_inst_tn<GATHER_CONV, true>(l) : nn16_inst_tn<GATHER_CONV, false>(l);
+            return l.posmajor ? nn16_inst_tn<GATHER_TCONV, true>(l) : nn16_inst_tn<GATHER_TCONV, false>(l);
     }
-    const Gather& g = p.g;
-    const int64_t blocks = (int64_t)g.Nb * (g.Hq / NH_T) * (g.Wq / NH_T) * ((p.N + 32 * nf - 1) / (32 * nf)) *
-                           (g.pstep * g.pstep);
-    BG_REQUIRE(blocks > 0 && blocks < (int64_t(1) << 31), "nn16h: grid out of range");
-    p.splitk = 1;
-    p.mfast = nn16_mfast(p, g.Nb * (g.Hq / NH_T) * (g.Wq / NH_T), (p.N + 32 * nf - 1) / (32 * nf));
-    int rc;
-    if (mode == GATHER_CONV) rc = launch_nn16h_nf<3, GATHER_CONV>(p, nf, (int)blocks, s);
-    else if (ntaps == 3) rc = launch_nn16h_nf<3, GATHER_TCONV>(p, nf, (int)blocks, s);
-    else rc = launch_nn16h_nf<2, GATHER_TCONV>(p, nf, (int)blocks, s);
-    if (rc) return rc;
+}
+int nn16_launch_lds(const NN16Launch& l) { return nn16_inst(l).lds; }
+
+// The shared tail: the plan's fields into the parameter block, the launch, its check, the slab reduce of a split launch.
+// record: name the instantiation for bg_prof (the mirrored-tap launch leaves the plain launch's name in place).
+static int nn16_run(NN16Params& p, const NN16Launch& l, bool record, hipStream_t s) {
+    BG_REQUIRE(l.grid_x > 0 && l.grid_x < (int64_t(1) << 31), "bf16-resident conv: grid out of range");
+    p.splitk = l.splitk; p.posmajor = l.posmajor; p.mfast = l.mfast; p.zfold = l.zfold;
+    p.pow2 = l.pow2; p.wq_shift = l.wq_shift; p.hq_shift = l.hq_shift;
+    p.tiles_m = l.tiles_m; p.tiles_n = l.tiles_n;
+    const NN16Inst k = nn16_inst(l);
+    // > 48 KB of dynamic LDS needs the opt-in once per kernel and device
+    if (!lds_opt_in(reinterpret_cast<const void*>(k.fn), k.lds)) return BG_ERR_LAUNCH;
+    if (record && prof_on()) {
+        char name[48];
+        nn16_launch_name(l, name, sizeof(name));
+        prof_kernel("%s", name);
+    }
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)l.grid_x, 1, l.grid_z), dim3(l.block), k.lds, s, p);
     BG_LAUNCH_CHECK();
+    if (l.splitk > 1) {
+        const int64_t n8 = p.slab_stride / 8;
+        int blocks = (int)((n8 + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(nn16_slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, p.slabs, p.out, p.bias, p.alpha, n8,
+                           p.N, l.splitk, p.slab_stride, p.accumulate, p.out_f32);
+        BG_LAUNCH_CHECK();
+    }
     return BG_OK;
 }
 
-bool nn16_d2s_ok(const NN16Params& p, int mode, int zdim) {
-    const Gather& g = p.g;
-    if (p.d2s_c <= 0 || p.d2s_c % 8 || p.N != 4 * p.d2s_c || p.C % 8 || mode != GATHER_CONV || zdim != 1 || g.stride != 1 ||
-        g.pstep != 1 || g.Hq != g.Ho || g.Wq != g.Wo || p.stats_part || p.ring)
-        return false;
-    if ((int64_t)g.Nb * g.Ho * g.Wo * 4 >= (int64_t(1) << 31)) return false;
-    if (nn16h_taps(p, mode, zdim)) return true;
-    if (nn16_posmajor_fraction(p, mode) < 1.0) return false;
-    return plan_nn16(p, mode, zdim, true).splitk == 1;     // (the plan the unfused launch of the same shape would take)
-}
-
-int64_t nn16_stats_rows(const NN16Params& p, int mode, int zdim) {
-    if (p.C % 8 || p.N % 8 || !nn16h_taps(p, mode, zdim)) return 0;
-    return 2 * (int64_t)p.g.Nb * (p.g.Hq / NH_T) * (p.g.Wq / NH_T) * (p.g.pstep * p.g.pstep);     // one per half patch
-}
-
-int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, size_t ws_bytes, hipStream_t s) {
+int launch_nn16(NN16Params& p, const NN16Launch& l, int64_t out_elems, void* ws, hipStream_t s) {
     BG_REQUIRE(p.C % 8 == 0 && p.N % 8 == 0 && p.g.ld % 8 == 0 && p.out_ld % 8 == 0,
                "bf16-resident conv: channel counts must be multiples of 8 (C=%d N=%d)", p.C, p.N);
     BG_REQUIRE((reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.B) & 15) == 0 &&
@@ -2417,288 +2108,83 @@ int launch_nn16(NN16Params& p, int mode, int zdim, int64_t out_elems, void* ws, 
                "bf16-resident conv: kernel size %d / stride %d / %d channels not supported", p.g.k, p.g.stride, p.C);
     BG_REQUIRE((int64_t)p.g.Nb * p.g.Hs * p.g.Ws < (int64_t(1) << 30) && (int64_t)p.g.Nb * p.g.Ho * p.g.Wo < (int64_t(1) << 31),
                "bf16-resident conv: more than 2^30 source / 2^31 output pixels");
-    BG_REQUIRE(p.d2s_c == 0 || (nn16_d2s_ok(p, mode, zdim) && ws == nullptr),
+    BG_REQUIRE(p.d2s_c == 0 || (l.d2s_store && ws == nullptr),
                "bf16-resident conv: this launch has no depth-to-space store (bg_conv2d_fwd_d2s_supported)");
-    if (const int ntaps = nn16h_taps(p, mode, zdim)) return launch_nn16h(p, mode, ntaps, s);
-    BG_REQUIRE(p.stats_part == nullptr, "bf16-resident conv: fused statistics need the halo-tile form (nn16_stats_rows)");
-    NN16Plan pl = plan_nn16(p, mode, zdim, ws != nullptr);
-    if (pl.splitk > 1 && ws_bytes < (size_t)pl.splitk * out_elems * sizeof(float)) pl.splitk = 1;
-    p.splitk = pl.splitk;
+    BG_REQUIRE(l.family == NN16_HALO || p.stats_part == nullptr,
+               "bf16-resident conv: fused statistics need the halo-tile form (bg_deconv2d_fwd_stats_workspace_bytes)");
+    BG_REQUIRE((l.family == NN16_HALO || l.family == NN16_TAP) && (l.splitk == 1 || ws != nullptr),
+               "bf16-resident conv: not a plan of this launch");
     p.slabs = reinterpret_cast<float*>(ws);
     p.slab_stride = out_elems;
-    p.posmajor = nn16_posmajor_fraction(p, mode) < 1.0;
-    // the pipeline form: by the grid the 256-row tile would leave; the phased form brings its own column tile
-    int xtn;
-    const int form = nn16_form(p, pl.tn, (int64_t)((p.M + 255) / 256) * zdim * pl.splitk,
-                               zdim == 1 || p.g.k % p.g.stride == 0, false, &xtn);
-    const int ltn = form == NN16_FORM_PHASED ? xtn : pl.tn;
-    const int bn = 32 * ltn;
-    p.tiles_n = (p.N + bn - 1) / bn;
-    const int bm = (form == NN16_FORM_WIDE || form == NN16_FORM_PHASED) ? 256 : NN16_BM;
-    p.tiles_m = (p.M + bm - 1) / bm;
-    p.pow2 = 0;
-    if (p.g.Wq > 0 && p.g.Hq > 0 && (p.g.Wq & (p.g.Wq - 1)) == 0 && (p.g.Hq & (p.g.Hq - 1)) == 0) {
-        p.pow2 = 1;
-        p.wq_shift = __builtin_ctz(p.g.Wq);
-        p.hq_shift = __builtin_ctz(p.g.Hq);
+    return nn16_run(p, l, true, s);
+}
+
+int launch_nn16_ring(NN16Params& p, const NN16Launch& l, hipStream_t s) {
+    BG_REQUIRE(p.ring == 1 && (p.ring_lines == 1 || p.ring_lines == 2), "nn16 ring launch: ring = 1, ring_lines 1 or 2");
+    BG_REQUIRE(l.family == NN16_MIRROR_RING && p.g.k >= 1 && p.g.k <= NN16_RING_TAPS / 2 && p.g.Ho >= 4 && p.g.Wo >= 4 &&
+                   p.accumulate == 1,
+               "nn16 ring launch: kernel size %d / map %d x %d not supported", p.g.k, p.g.Ho, p.g.Wo);
+    BG_REQUIRE(p.C % 8 == 0 && p.N % 8 == 0 && p.g.ld % 8 == 0 && p.out_ld % 8 == 0, "nn16 ring launch: channels %% 8");
+    const int npos = p.ring_lines * p.g.Wo + p.ring_lines * (p.g.Ho - p.ring_lines);
+    p.g.pstep = 1;
+    p.g.Hq = 1;
+    p.g.Wq = npos;
+    p.M = p.g.Nb * npos;
+    p.slabs = nullptr;
+    return nn16_run(p, l, false, s);
+}
+
+// The THIN = 1 form of nn16h_kernel (see there): plain describes the plain transposed gather (nn16h_d2s_ok).
+int launch_nn16h_d2s(const NN16Params& plain, const NN16Launch& l, hipStream_t s) {
+    BG_REQUIRE(l.family == NN16_HALO_D2S, "nn16h depth-to-space form: not a plan of this launch");
+    NN16Params p = plain;
+    Gather& g = p.g;
+    g.Hq = g.Hs; g.Wq = g.Ws; g.pstep = 1; g.pad = 0; g.stride = 1;
+    p.N = 32;
+    p.ring = 0;
+    return nn16_run(p, l, true, s);
+}
+
+// THE dispatch of the weight-gradient launches
+static TN16Inst tn16_inst(const TN16Launch& l) {
+    const bool conv = l.mode == GATHER_CONV;
+    if (l.kernel == TN16_PHASED) {                     // (gathered operands only: tn16x_phased_bn)
+        const int lds = tn16xp_lds_bytes(l.nkb);
+        if (l.bn == 256)
+            return {l.nkb == 8 ? &tn16x_phased_kernel<GATHER_CONV, 256, 8> : &tn16x_phased_kernel<GATHER_CONV, 256, 6>, lds};
+        return {l.nkb == 8 ? &tn16x_phased_kernel<GATHER_CONV, 192, 8> : &tn16x_phased_kernel<GATHER_CONV, 192, 6>, lds};
     }
-    p.mfast = nn16_mfast(p, p.tiles_m, p.tiles_n);
-    dim3 grid(p.tiles_m * p.tiles_n, 1, zdim * p.splitk);
-    p.zfold = 0;
-    if (mode == GATHER_TCONV && zdim > 1 && p.splitk == 1 && p.g.k % p.g.stride == 0) {
-        p.zfold = zdim;                     // the phases of one M tile gather the same input rows: same XCD
-        grid = dim3(p.tiles_m * p.tiles_n * zdim, 1, 1);
-    }
-    int rc;
-    if (mode == GATHER_CONV)
-        rc = launch_nn16_mode<GATHER_CONV>(p, ltn, form, grid, s);
-    else
-        rc = launch_nn16_mode<GATHER_TCONV>(p, ltn, form, grid, s);
-    if (rc) return rc;
-    BG_LAUNCH_CHECK();
-    if (pl.splitk > 1) {
-        const int64_t n8 = out_elems / 8;
-        int blocks = (int)((n8 + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(nn16_slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, p.slabs, p.out, p.bias, p.alpha, n8,
-                           p.N, pl.splitk, out_elems, p.accumulate, p.out_f32);
-        BG_LAUNCH_CHECK();
-    }
-    return BG_OK;
+    if (l.kernel == TN16_NARROW) return {conv ? &tn16_kernel<GATHER_CONV> : &tn16_kernel<GATHER_PLAIN>, 4 * TN16_TILE};
+    if (l.nbi == 2) return {conv ? &tn16x_kernel<GATHER_CONV, 32, 2> : &tn16x_kernel<GATHER_PLAIN, 32, 2>, 3 * 4 * 32 * 256};
+    if (l.bk == 64) return {conv ? &tn16x_kernel<GATHER_CONV, 64> : &tn16x_kernel<GATHER_PLAIN, 64>, 3 * 3 * l.bk * 256};
+    return {conv ? &tn16x_kernel<GATHER_CONV, 32> : &tn16x_kernel<GATHER_PLAIN, 32>, 3 * 3 * l.bk * 256};
 }
+int tn16_launch_lds(const TN16Launch& l) { return tn16_inst(l).lds; }
 
-static void plan_tn16(TN16Params& p) {
-    const int64_t tiles = (int64_t)((p.Mf + 127) / 128) * ((p.Cb + 127) / 128);
-    static const int want = getenv("BG_TN16_WANT") ? atoi(getenv("BG_TN16_WANT")) : 1024;
-    int sk = (int)(want / tiles);          // (floor: tiles * sk <= want = a whole number of rounds of 512 co-resident blocks)
-    const int max_sk = (p.M + 4 * TN16_BK - 1) / (4 * TN16_BK);      // at least 256 pixels per split
-    if (sk > max_sk) sk = max_sk;
-    if (sk < 1) sk = 1;
-    if (sk > 512) sk = 512;
-    int rps = (p.M + sk - 1) / sk;
-    rps = (rps + TN16_BK - 1) / TN16_BK * TN16_BK;
-    p.splitk = (p.M + rps - 1) / rps;
-    p.rows_per_split = rps;
-}
-
-// wide form (tn16x_kernel): used when there are at least two 128-row tiles of output and the reduction fills the ring;
-// split so that the grid is a whole number of rounds of 256 co-resident blocks (one per CU)
-// 256-wide output tiles (tn16x_kernel<.., 2>) where they divide the output channels: C = 512, 768, 1536.  OFF by default:
-// measured r03 (config 3, same box): 102.7 ms / iteration with it, 102.9 without at batch 256, 25.6 / 25.6 at batch 32 -
-// the third fewer L2 -> LDS bytes and LDS operand reads buy nothing once only one block (2 waves per SIMD) fits a CU.
-// BG_TN16X_NBI=2 switches it on (tests/test_gpu_bf16.py keeps it exact).
-static int tn16x_nbi(const TN16Params& p) {
-    const char* e = getenv("BG_TN16X_NBI");
-    if (!e || atoi(e) != 2) return 1;
-    return (p.Cb >= 512 && p.Cb % 256 == 0 && p.Mf >= 256) ? 2 : 1;
-}
-
-// Column tile of the phased form (tn16x_phased_kernel) for a launch that plan_tn16x accepts; 0: the launch keeps
-// tn16x_kernel<.., 32>.  The K partition is plan_tn16x's for 128-column tiles whatever the tile (same sums, same workspace):
-// tm: 256-row tiles, sk: K splits of that plan, so the phased grid is tm * ceil(Cb / BN) * sk blocks.
-// Switches, read per call (tests/test_gpu_tn16x_phased.py, tools/kbench.py): BG_TN16X_PHASED = 0: never, 1: every launch
-// the wide form accepts (gathered operands only: the regulariser's Gram keeps the ring form - not measured); unset: the
-// rule.  BG_TN16X_PHASED_BN = 192 / 256 sets the column tile of a launch that takes the form.  With BG_TN16X_NBI=2 set, the
-// launches that switch applies to go where it sends them.  (BG_TN16X_PHASED_RING=8: the 128 KB ring, for A/B.)
-//
-// The rule, from the per-layer table of profiles/tn16x_phase_ab.txt (config 3 at 256 images, tools/kbench.py wgrad column,
-// ms per call: tn16x_kernel<0, 32> -> BN 192 / BN 256 ; Cb ; blocks at 128 / 192 / 256 columns; repeat spread 0.001 - 0.010):
-//   deconv 64^2 192 -> 96 k4 s2      0.889 -> 0.694 / 0.780   Cb  192   504 / 252 / 252
-//   deconv 64^2 192 -> 192 k3        0.976 -> 0.781 / 0.870   Cb  192   504 / 252 / 252
-//   conv 64^2 96 -> 192 k3 s2        0.290 -> 0.221 / 0.246   Cb  192   512 / 256 / 256
-//   conv 32^2 192 -> 192 k3          0.502 -> 0.385 / 0.419   Cb  192   504 / 252 / 252
-//   deconv 32^2 384 -> 192 k4 s2     0.693 -> 0.866 / 0.952   Cb  384   504 / 336 / 336
-//   deconv 32^2 384 -> 384 k3        0.769 -> 1.000 / 1.163   Cb  384   504 / 336 / 336
-//   conv 32^2 192 -> 384 k3 s2       0.210 -> 0.283 / 0.307   Cb  384   504 / 336 / 336
-//   conv 16^2 384 -> 384 k3          0.359 -> 0.506 / 0.566   Cb  384   504 / 336 / 336
-//   deconv 16^2 768 -> 384 k4 s2     0.742 -> 0.994 / 0.635   Cb  768   432 / 288 / 216
-//   deconv 16^2 768 -> 768 k3        0.684 -> 0.989 / 0.588   Cb  768   486 / 324 / 243
-//   conv 16^2 384 -> 768 k3 s2       0.205 -> 0.279 / 0.184   Cb  768   504 / 336 / 252
-//   conv 8^2 768 -> 768 k3           0.385 -> 0.525 / 0.349   Cb  768   486 / 324 / 243
-//   deconv 8^2 1536 -> 768 k4 s2     0.777 -> 0.749 / 0.802   Cb 1536   576 / 384 / 288
-//   deconv 8^2 1536 -> 1536 k3       0.821 -> 0.796 / 0.842   Cb 1536   648 / 432 / 324
-//   deconv 4^2 1536 -> 1536 k4 s2    0.370 -> 0.338 / 0.355   Cb 1536  1152 / 768 / 576
-//   conv 8^2 768 -> 1536 k3 s2       0.259 -> 0.195 / 0.224   Cb 1536   324 / 216 / 162
-//   conv 4^2 1536 -> 1536 k3         0.414 -> 0.401 / 0.446   Cb 1536   648 / 432 / 324
-//   (forced onto Cb = 96 and 24 the form loses 8 - 60 %: one partly filled tile.)
-// The form runs ONE block per CU under a split that was planned for 512 slots of 128 columns, and the split stays (the sums
-// depend on it).  What decides is therefore how the grid falls into rounds of 256 blocks.  With whole 192-column tiles the
-// Cb = 192 layers come out at 252 - 256 blocks without the parent's half-empty second tile (-20 ... -24 %), 768 -> 1536 k3 s2
-// at 216 (-25 %) and 1536 -> 1536 k4 s2 at three whole rounds (-9 %).  At Cb = 768 three 256-column tiles make 216 - 252
-// blocks (-9 ... -14 %) where four 192-column tiles make 1.1 - 1.3 rounds (+35 ... 45 %).  Cb = 384 has no tile that fills
-// its rounds (336 blocks: +25 ... 40 %).  The Cb = 1536 launches of 1.5 - 1.7 rounds gain 3 - 4 % at 192 (their parent grids,
-// 576 - 648 blocks on 512 slots, do not fill their rounds either) and lose at 256.  Hence: BN = 192 where Cb % 192 == 0,
-// else BN = 256 where Cb % 256 == 0, each only if the last round of its grid is at least half full (measured: 0 - 128 empty
-// slots gain, 176 and more lose; grids under half a round and Cb % 256 == 0 with Cb % 192 != 0: not measured) - otherwise the
-// parent form: Cb = 96, 24, 8, every tail, every grid that does not fill its rounds.
-constexpr int TN16XP_CUS = 256;
-static int tn16x_phased_bn(const TN16Params& p, int mode, int tm, int sk) {
-    if (mode != GATHER_CONV || tn16x_nbi(p) != 1) return 0;
-    int bn = 0;
-    for (int c = 192; c <= 256 && bn == 0; c += 64) {
-        const int64_t blocks = (int64_t)tm * (p.Cb / c) * sk;
-        const int64_t last = (blocks + TN16XP_CUS - 1) / TN16XP_CUS * TN16XP_CUS - blocks;      // empty slots of the last round
-        if (p.Cb % c == 0 && last * 2 <= TN16XP_CUS) bn = c;
-    }
-    if (const char* e = getenv("BG_TN16X_PHASED")) {
-        if (atoi(e) == 0) return 0;
-        if (bn == 0) bn = (p.Cb > 192 && p.Cb % 256 == 0) ? 256 : 192;       // (forced by the switch)
-    }
-    if (bn == 0) return 0;
-    if (const char* e = getenv("BG_TN16X_PHASED_BN")) {
-        const int v = atoi(e);
-        if (v == 192 || v == 256) bn = v;
-    }
-    return bn;
-}
-
-template <int BN, int NKB>
-static int launch_tn16x_phased(const TN16Params& p, dim3 grid, hipStream_t s) {
-    constexpr int lds = tn16xp_lds_bytes(NKB);
-    if (!lds_opt_in(reinterpret_cast<const void*>(&tn16x_phased_kernel<GATHER_CONV, BN, NKB>), lds)) return BG_ERR_LAUNCH;
-    prof_kernel("tn16x_phased_kernel<%d, %d, %d>", (int)GATHER_CONV, BN, NKB);
-    hipLaunchKernelGGL((tn16x_phased_kernel<GATHER_CONV, BN, NKB>), grid, dim3(512), lds, s, p);
-    return BG_OK;
-}
-
-static bool plan_tn16x(const TN16Params& p, int* sk_out, int* rps_out) {
-    static const int use_wide = getenv("BG_TN16_WIDE") ? atoi(getenv("BG_TN16_WIDE")) : 1;
-    if (!use_wide || p.Mf <= 128 || p.M < 8 * TN16_BK) return false;
-    // the kernel walks a power-of-two pixel grid by shifts (every BigGAN resolution is one); others take tn16_kernel
-    if (p.g.k > 0 && (p.g.Wq <= 0 || p.g.Hq <= 0 || (p.g.Wq & (p.g.Wq - 1)) || (p.g.Hq & (p.g.Hq - 1)))) return false;
-    // (g.k == 0: plain rows, no pixel walk)
-    const int nbi = tn16x_nbi(p);
-    const int tm = (p.Mf + 255) / 256, tn = (p.Cb + 128 * nbi - 1) / (128 * nbi);
-    static const int wantx0 = getenv("BG_TN16X_WANT") ? atoi(getenv("BG_TN16X_WANT")) : 512;
-    const int wantx = nbi == 2 ? wantx0 / 2 : wantx0;           // (one block per CU with the 96 KB ring)
-    int sk = wantx / (tm * tn);
-    const int max_sk = (p.M + 4 * TN16_BK - 1) / (4 * TN16_BK);
-    if (sk > max_sk) sk = max_sk;
-    if (sk < 1) sk = 1;
-    if (sk > 512) sk = 512;
-    int rps = (p.M + sk - 1) / sk;
-    rps = (rps + TN16_BK - 1) / TN16_BK * TN16_BK;
-    *sk_out = (p.M + rps - 1) / rps;
-    *rps_out = rps;
-    return true;
-}
-
-size_t tn16_workspace_bytes(const TN16Params& p0) {
-    TN16Params p = p0;
-    plan_tn16(p);
-    int sk = p.splitk, skx = 1, rps = 0;
-    if (plan_tn16x(p0, &skx, &rps) && skx > sk) sk = skx;
-    return sk > 1 ? (size_t)sk * p.Mf * p.Cb * sizeof(float) : 0;
-}
-
-int launch_tn16(TN16Params& p, int mode, float* final_out, void* ws, size_t ws_bytes, hipStream_t s) {
+int launch_tn16(TN16Params& p, const TN16Launch& l, float* final_out, void* ws, hipStream_t s) {
     BG_REQUIRE(p.Ca % 8 == 0 && p.Cb % 8 == 0 && p.g.ld % 8 == 0 && p.b_ld % 8 == 0,
                "bf16-resident wgrad: channel counts must be multiples of 8 (Ca=%d Cb=%d)", p.Ca, p.Cb);
     BG_REQUIRE((reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.Bv) & 15) == 0,
                "bf16-resident wgrad: tensors must be 16-byte aligned");
-    plan_tn16(p);
+    BG_REQUIRE(l.splitk == 1 || ws != nullptr, "bf16-resident wgrad: not a plan of this launch");
+    BG_REQUIRE(l.grid_x > 0 && l.grid_x < (int64_t(1) << 31), "bf16-resident wgrad: grid out of range");
     const int64_t total = (int64_t)p.Mf * p.Cb;
-    if (p.splitk > 1 && (ws == nullptr || ws_bytes < (size_t)p.splitk * total * sizeof(float) || p.out_ld != p.Cb)) {
-        p.splitk = 1;
-        p.rows_per_split = (p.M + TN16_BK - 1) / TN16_BK * TN16_BK;
+    p.splitk = l.splitk; p.rows_per_split = l.rows_per_split;
+    p.out = l.splitk > 1 ? reinterpret_cast<float*>(ws) : final_out;
+    p.slab_stride = l.splitk > 1 ? total : 0;
+    p.tiles_m = l.tiles_m; p.tiles_n = l.tiles_n;
+    p.pow2 = l.pow2; p.wq_shift = l.wq_shift; p.hq_shift = l.hq_shift;
+    const TN16Inst k = tn16_inst(l);
+    if (!lds_opt_in(reinterpret_cast<const void*>(k.fn), k.lds)) return BG_ERR_LAUNCH;
+    if (prof_on()) {
+        char name[48];
+        tn16_launch_name(l, name, sizeof(name));
+        prof_kernel("%s", name);
     }
-    if (p.splitk > 1) {
-        p.out = reinterpret_cast<float*>(ws);
-        p.slab_stride = total;
-    } else {
-        p.out = final_out;
-        p.slab_stride = 0;
-    }
-    p.tiles_m = (p.Mf + 127) / 128;
-    p.tiles_n = (p.Cb + 127) / 128;
-    p.pow2 = 0;
-    if (mode != GATHER_PLAIN && (p.g.Wq & (p.g.Wq - 1)) == 0 && (p.g.Hq & (p.g.Hq - 1)) == 0) {
-        p.pow2 = 1;
-        p.wq_shift = __builtin_ctz(p.g.Wq);
-        p.hq_shift = __builtin_ctz(p.g.Hq);
-    }
-    int sk = 1, rps = 0;
-    if (plan_tn16x(p, &sk, &rps)) {
-        const int nbi = tn16x_nbi(p);
-        const int tm = (p.Mf + 255) / 256, tn = (p.Cb + 128 * nbi - 1) / (128 * nbi);
-        const bool can_split = ws != nullptr && ws_bytes >= (size_t)sk * total * sizeof(float) && p.out_ld == p.Cb;
-        if (sk == 1 || can_split) {
-            p.splitk = sk;
-            p.rows_per_split = rps;
-            p.out = sk > 1 ? reinterpret_cast<float*>(ws) : final_out;
-            p.slab_stride = sk > 1 ? total : 0;
-            p.tiles_m = tm;
-            p.tiles_n = tn;
-            static const int bk = getenv("BG_TN16X_BK") ? atoi(getenv("BG_TN16X_BK")) : 32;
-            if (const int pbn = tn16x_phased_bn(p, mode, tm, sk)) {
-                const char* ring = getenv("BG_TN16X_PHASED_RING");     // K blocks of the ring: 6 (96 KB), 8 (128 KB, for A/B)
-                const int nkb = ring ? atoi(ring) : 6;
-                p.tiles_n = (p.Cb + pbn - 1) / pbn;
-                dim3 gridp(tm * p.tiles_n * sk, 1, 1);
-                int rc;
-                if (pbn == 256) rc = nkb == 8 ? launch_tn16x_phased<256, 8>(p, gridp, s) : launch_tn16x_phased<256, 6>(p, gridp, s);
-                else rc = nkb == 8 ? launch_tn16x_phased<192, 8>(p, gridp, s) : launch_tn16x_phased<192, 6>(p, gridp, s);
-                if (rc) return rc;
-                BG_LAUNCH_CHECK();
-                if (sk > 1) {
-                    launch_slab_reduce(reinterpret_cast<const float*>(ws), final_out, total, sk, total, s);
-                    BG_LAUNCH_CHECK();
-                }
-                return BG_OK;
-            }
-            if (nbi == 2) {
-                constexpr int ldsw = 3 * 4 * 32 * 256;
-                const void* fw = mode == GATHER_CONV ? reinterpret_cast<const void*>(&tn16x_kernel<GATHER_CONV, 32, 2>)
-                                                     : reinterpret_cast<const void*>(&tn16x_kernel<GATHER_PLAIN, 32, 2>);
-                if (!lds_opt_in(fw, ldsw)) return BG_ERR_LAUNCH;
-                prof_kernel("tn16x_kernel<%d, 32, 2>", mode == GATHER_CONV ? GATHER_CONV : GATHER_PLAIN);
-                dim3 gridw(tm * tn * sk, 1, 1);
-                if (mode == GATHER_CONV) hipLaunchKernelGGL((tn16x_kernel<GATHER_CONV, 32, 2>), gridw, dim3(512), ldsw, s, p);
-                else hipLaunchKernelGGL((tn16x_kernel<GATHER_PLAIN, 32, 2>), gridw, dim3(512), ldsw, s, p);
-                BG_LAUNCH_CHECK();
-                if (sk > 1) {
-                    launch_slab_reduce(reinterpret_cast<const float*>(ws), final_out, total, sk, total, s);
-                    BG_LAUNCH_CHECK();
-                }
-                return BG_OK;
-            }
-            const int ldsx = 3 * 3 * bk * 256;
-            const void* fx = mode == GATHER_CONV
-                                 ? (bk == 64 ? reinterpret_cast<const void*>(&tn16x_kernel<GATHER_CONV, 64>)
-                                             : reinterpret_cast<const void*>(&tn16x_kernel<GATHER_CONV, 32>))
-                                 : (bk == 64 ? reinterpret_cast<const void*>(&tn16x_kernel<GATHER_PLAIN, 64>)
-                                             : reinterpret_cast<const void*>(&tn16x_kernel<GATHER_PLAIN, 32>));
-            if (!lds_opt_in(fx, ldsx)) return BG_ERR_LAUNCH;
-            prof_kernel("tn16x_kernel<%d, %d>", mode == GATHER_CONV ? GATHER_CONV : GATHER_PLAIN, bk == 64 ? 64 : 32);
-            dim3 gridx(tm * tn * sk, 1, 1);
-            if (mode == GATHER_CONV) {
-                if (bk == 64) hipLaunchKernelGGL((tn16x_kernel<GATHER_CONV, 64>), gridx, dim3(512), ldsx, s, p);
-                else hipLaunchKernelGGL((tn16x_kernel<GATHER_CONV, 32>), gridx, dim3(512), ldsx, s, p);
-            } else {
-                if (bk == 64) hipLaunchKernelGGL((tn16x_kernel<GATHER_PLAIN, 64>), gridx, dim3(512), ldsx, s, p);
-                else hipLaunchKernelGGL((tn16x_kernel<GATHER_PLAIN, 32>), gridx, dim3(512), ldsx, s, p);
-            }
-            BG_LAUNCH_CHECK();
-            if (sk > 1) {
-                launch_slab_reduce(reinterpret_cast<const float*>(ws), final_out, total, sk, total, s);
-                BG_LAUNCH_CHECK();
-            }
-            return BG_OK;
-        }
-    }
-    dim3 grid(p.tiles_m * p.tiles_n * p.splitk, 1, 1);
-    constexpr int lds = 4 * TN16_TILE;
-    if (!lds_opt_in(mode == GATHER_CONV ? reinterpret_cast<const void*>(&tn16_kernel<GATHER_CONV>)
-                                        : reinterpret_cast<const void*>(&tn16_kernel<GATHER_PLAIN>), lds))
-        return BG_ERR_LAUNCH;
-    prof_kernel("tn16_kernel<%d>", mode == GATHER_CONV ? GATHER_CONV : GATHER_PLAIN);
-    if (mode == GATHER_CONV)
-        hipLaunchKernelGGL((tn16_kernel<GATHER_CONV>), grid, dim3(256), lds, s, p);
-    else
-        hipLaunchKernelGGL((tn16_kernel<GATHER_PLAIN>), grid, dim3(256), lds, s, p);
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)l.grid_x), dim3(l.block), k.lds, s, p);
     BG_LAUNCH_CHECK();
-    if (p.splitk > 1) {
-        launch_slab_reduce(reinterpret_cast<const float*>(ws), final_out, total, p.splitk, total, s);
+    if (l.splitk > 1) {
+        launch_slab_reduce(reinterpret_cast<const float*>(ws), final_out, total, l.splitk, total, s);
         BG_LAUNCH_CHECK();
     }
     return BG_OK;

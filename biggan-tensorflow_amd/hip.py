@@ -111,6 +111,7 @@ SIGNATURES = {
     "bg_conv2d_fwd_workspace_bytes": (c_size_t, [_CD]),
     "bg_conv2d_fwd": (c_int, [_CD, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_conv2d_fwd_d2s_supported": (c_int, [_CD, c_int]),
+    "bg_conv_plan_describe": (c_int, [_CD, c_int, c_size_t, c_char_p, c_size_t]),
     "bg_conv2d_fwd_d2s": (c_int, [_CD, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "bg_conv2d_dgrad_workspace_bytes": (c_size_t, [_CD]),
     "bg_conv2d_dgrad": (c_int, [_CD, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
@@ -375,6 +376,18 @@ def stream():
 def conv_desc(N, H, W, Cin, Ho, Wo, Cout, k, stride, pad_lo, pad_mode, compute=COMPUTE_F32, x_dtype=F32, y_dtype=F32,
               w_packed=0):
     return BgConvDesc(N, H, W, Cin, Ho, Wo, Cout, k, stride, pad_lo, pad_mode, compute, x_dtype, y_dtype, w_packed)
+
+
+PASSES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "deconv2d_fwd", "deconv2d_dgrad", "deconv2d_wgrad", "conv2d_fwd_d2s")
+
+
+def plan_describe(desc, pass_name, ws_bytes=None):
+    """bg_conv_plan_describe as a dict of strings: what the call `bg_<pass_name>` would launch for `desc` when handed
+    ws_bytes of workspace (None: what its workspace query returns).  Host only."""
+    buf = ctypes.create_string_buffer(1024)
+    check(lib().bg_conv_plan_describe(desc, PASSES.index(pass_name), c_size_t(-1).value if ws_bytes is None else ws_bytes,
+                                      buf, len(buf)))
+    return dict(kv.split("=", 1) for kv in buf.value.decode().split("; "))
 
 
 def workspace(nbytes, device):

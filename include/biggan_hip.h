@@ -167,6 +167,24 @@ size_t bg_deconv2d_wgrad_workspace_bytes(const BgConvDesc*);
 int bg_deconv2d_wgrad(const BgConvDesc*, const void* x, const void* dy, float* dw,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* What a conv / transposed-conv call would launch, as text, without launching it (no GPU needed): one line of
+ * "key=value" pairs separated by "; " in buf.  pass: BG_PASS_* - the six passes above and the forward with the fused
+ * depth-to-space store (block 2).  ws_bytes: the workspace the caller would hand the call ((size_t)-1: what the pass's
+ * *_workspace_bytes returns; 0: a null pointer).  The line is made from the same plan the call and its queries read:
+ *   every route     route (the form of the call: F32_TAP ... TN_BF16), ws (bytes of workspace: with ws_bytes = -1 the
+ *                   query's answer, else what the launches use of ws_bytes)
+ *   bf16 routes     kernel (the instantiation, as bg_prof_dump names it), grid (x * y * z), block, lds (dynamic bytes),
+ *                   tile (rows x columns), form (two | ring | wide | phased; halo; narrow | wide | phased for weight
+ *                   gradients), splitk, posmajor, mfast, zfold, stats_rows, d2s (the launch stores depth-to-space)
+ *   halo-tile       nt, nf            weight gradients   rows_per_split
+ *   ring routes     ring_kernel, ring_grid, ring_tile, ring_form, ring_lds (the mirrored-tap launch)
+ *   padded grid     fold_grid_bytes (the padded gradient at the head of the workspace), fold_grid (Hp x Wp)
+ * BG_ERR_ARG (nothing written) for a null descriptor or buffer, a buffer too small for the line, an unknown pass, a
+ * descriptor the pass rejects, or a ws_bytes smaller than the padded grid of a call that needs one. */
+enum { BG_PASS_CONV_FWD = 0, BG_PASS_CONV_DGRAD = 1, BG_PASS_CONV_WGRAD = 2, BG_PASS_DECONV_FWD = 3,
+       BG_PASS_DECONV_DGRAD = 4, BG_PASS_DECONV_WGRAD = 5, BG_PASS_CONV_FWD_D2S = 6 };
+int bg_conv_plan_describe(const BgConvDesc* d, int pass, size_t ws_bytes, char* buf, size_t buf_bytes);
+
 /* Direct (vector-ALU, HBM-bound) path for k x k stride-1 convolutions with <= 3 output channels:
  * the generator's RGB head G_logit (BigGAN.py:570 -> ops.py:49-113).  Same arithmetic as
  * bg_conv2d_*; bg_rgbconv_supported tells whether a geometry qualifies.

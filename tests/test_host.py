@@ -609,7 +609,7 @@ def test_pmc_summary_classifies_the_kernel_names_of_this_build():
 
 def test_workspace_queries_run_the_bf16_planner_on_the_host():
     """The workspace queries of the bf16-resident convolutions are pure host code and run the same tile / split-K planner
-    as the launch (igemm16.hip plan_nn16, incl. the position-major decision for small maps).  Default form of the
+    as the launch (igemm16_plan.hip plan_nn16, incl. the position-major decision for small maps).  Default form of the
     reflect-padded input gradient (plain transposed gather + mirrored-tap launches): whole fp32 split-K slabs of the
     H x W gradient, nothing else; BG_DGRAD_RING=0 (round 2's form): at least the gradient on the reflect-padded grid,
     plus whole slabs of it - with either setting of BG_NN16_POSMAJOR."""
@@ -639,3 +639,263 @@ def test_workspace_queries_run_the_bf16_planner_on_the_host():
     finally:
         os.environ.pop("BG_NN16_POSMAJOR", None)
         os.environ.pop("BG_DGRAD_RING", None)
+
+
+# ------------------------------------------------------------------------------------------
+# bf16 launch plans (csrc/igemm16_plan.hip through bg_conv_plan_describe): no GPU needed
+# ------------------------------------------------------------------------------------------
+_PLAN_SWITCHES = ("BG_NN16_POSMAJOR", "BG_NN16_PIPE", "BG_NN16X_BN", "BG_NN16_HALO", "BG_NN16_HALO_K3S2", "BG_THIN_D2S",
+                  "BG_NN16_MFAST", "BG_TN16X_NBI", "BG_TN16X_PHASED", "BG_TN16X_PHASED_BN", "BG_TN16X_PHASED_RING",
+                  "BG_DGRAD_RING")
+
+
+def _bf16_desc(N, H, Cin, Ho, Cout, k, s, lo, mode=hip.PAD_ZERO):
+    return hip.conv_desc(N, H, H, Cin, Ho, Ho, Cout, k, s, lo, mode, hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
+
+
+def _plan(d, pass_name, ws_bytes=None, **env):
+    """hip.plan_describe under the given switches (restored afterwards)."""
+    try:
+        for k, v in env.items():
+            os.environ[k] = str(v)
+        return hip.plan_describe(d, pass_name, ws_bytes)
+    finally:
+        for k in env:
+            os.environ.pop(k, None)
+
+
+def _changed(a, b):
+    return {k for k in set(a) | set(b) if a.get(k) != b.get(k)}
+
+
+def test_bf16_plans_match_the_recorded_launches():
+    """tests/golden/bf16_launch_plans.json: every unique conv / deconv call of config 3 in bf16 at batch 256 and 32 and of
+    the bf16 geometry sweep, with the kernel bg_prof_dump named and the workspace query's answer, recorded on an MI355X
+    BEFORE the launch decisions moved into igemm16_plan.hip.  The plan names the same kernel when handed the workspace the
+    call was handed, and asks for the same workspace, under default switches (a sweep row carries the BG_DGRAD_RING its
+    case sets: that switch selects the route, not the launch)."""
+    root = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(root, "golden", "bf16_launch_plans.json")) as fh:
+        rows = json.load(fh)
+    assert len(rows) > 1000 and not any(os.environ.get(k) for k in _PLAN_SWITCHES)
+    L = hip.lib()
+    resident = 0
+    for r in rows:
+        d = hip.BgConvDesc(*r["desc"])
+        entry = r["entry"][3:].replace("_stats", "")
+        try:
+            os.environ.update(r["env"])
+            asked = hip.plan_describe(d, entry)
+            given = hip.plan_describe(d, entry, r["ws_passed"])
+            query = int(getattr(L, "bg_%s_workspace_bytes" % entry)(d))
+            stats = int(L.bg_deconv2d_fwd_stats_workspace_bytes(d)) if "stats_bytes" in r else None
+        finally:
+            for k in r["env"]:
+                os.environ.pop(k, None)
+        assert int(asked["ws"]) == r["ws_query"] == query, (r, asked)
+        if asked["route"].startswith(("BF16_", "TN_BF16")):
+            resident += 1
+            assert given["kernel"] == r["kernel"], (r, given)
+            assert int(given["ws"]) <= r["ws_passed"], (r, given)
+        else:
+            assert not r["kernel"].startswith(("nn16", "tn16")), (r, asked)
+        if stats is not None:
+            assert stats == r["stats_bytes"] == int(asked["stats_rows"]) * 2 * d.Cout * 4, (r, asked)
+    assert resident > 900
+
+
+def test_bf16_plan_rule_boundaries():
+    """One layer on each side of every boundary that the rule tables of nn16_form and tn16x_phased_bn
+    (csrc/igemm16_plan.hip) state; the expected form is the table's (the column that measured fastest), the layers are
+    config 3's at 256 images (the discriminator sees 512: real + fake)."""
+    fwd = lambda *a: _plan(_bf16_desc(*a), "conv2d_fwd")                      # noqa: E731
+    # C <= 192 per tap: the wide form; C >= 384: the phased form (conv 192 -> 384 k3 s2 at 32^2 0.20 -> 0.18 wide; conv 16^2
+    # 384 -> 768 k3 s2 0.159 -> 0.170 / 0.152 / 0.176: BN 192)
+    p = fwd(512, 32, 192, 16, 384, 3, 2, 1, hip.PAD_REFLECT)
+    assert (p["form"], p["tile"].split("x")[0]) == ("wide", "256"), p
+    p = fwd(512, 16, 384, 8, 768, 3, 2, 1, hip.PAD_REFLECT)
+    assert (p["form"], p["tile"]) == ("phased", "256x192"), p
+    # N % 256 == 0 with whole rounds at 256 columns: BN 256 (deconv 8^2 1536 -> 768 k4 s2, 768 blocks: 0.639 -> 0.466);
+    # N = 384, no multiple of 256: BN 192 (conv 16^2 384 -> 768 k3 s2 input gradient 0.224 -> 0.243 / 0.218 / 0.246)
+    p = _plan(_bf16_desc(256, 8, 1536, 16, 768, 4, 2, 1), "deconv2d_fwd")
+    assert (p["form"], p["tile"], p["grid"]) == ("phased", "256x256", "768*1*1"), p
+    p = _plan(_bf16_desc(512, 16, 384, 8, 768, 3, 2, 1, hip.PAD_REFLECT), "conv2d_dgrad", BG_DGRAD_RING=1)
+    assert (p["form"], p["tile"]) == ("phased", "256x192"), p
+    # whole rounds against 1.5 rounds: conv 8^2 768 -> 768 k3 has 512 blocks at BN 192 and 384 at BN 256 (0.275 against
+    # 0.329); deconv 4^2 1536 -> 1536 k4 s2 likewise (0.300 against 0.333)
+    p = fwd(512, 8, 768, 8, 768, 3, 1, 1, hip.PAD_REFLECT)
+    assert (p["form"], p["tile"], p["grid"]) == ("phased", "256x192", "512*1*1"), p
+    p = _plan(_bf16_desc(256, 4, 1536, 8, 1536, 4, 2, 1), "deconv2d_fwd")
+    assert (p["form"], p["tile"]) == ("phased", "256x192"), p
+    # uneven phases (k3 s2: 1 / 2 / 2 / 4 taps): one round of 256 blocks stays on two stages (768 -> 1536 k3 s2 input gradient
+    # at 256 images 0.195 -> 0.215), two rounds take BN 192 (at 512 images 0.259 -> 0.251)
+    p = _plan(_bf16_desc(256, 8, 768, 4, 1536, 3, 2, 1, hip.PAD_REFLECT), "conv2d_dgrad", BG_DGRAD_RING=1)
+    assert p["form"] == "two" and p["tile"].startswith("128x"), p
+    p = _plan(_bf16_desc(512, 8, 768, 4, 1536, 3, 2, 1, hip.PAD_REFLECT), "conv2d_dgrad", BG_DGRAD_RING=1)
+    assert (p["form"], p["tile"]) == ("phased", "256x192"), p
+    # tn16x_phased_bn, the table's rows at 512 images: Cb = 192 -> BN 192, Cb = 384 -> the ring form, Cb = 768 -> BN 256,
+    # Cb = 1536 -> BN 192
+    for (H, Cin, Ho, Cout, s), kernel in [((32, 192, 32, 192, 1), "tn16x_phased_kernel<0, 192, 6>"),
+                                          ((16, 384, 16, 384, 1), "tn16x_kernel<0, 32>"),
+                                          ((8, 768, 8, 768, 1), "tn16x_phased_kernel<0, 256, 6>"),
+                                          ((16, 384, 8, 768, 2), "tn16x_phased_kernel<0, 256, 6>"),
+                                          ((4, 1536, 4, 1536, 1), "tn16x_phased_kernel<0, 192, 6>"),
+                                          ((8, 768, 4, 1536, 2), "tn16x_phased_kernel<0, 192, 6>")]:
+        p = _plan(_bf16_desc(512, H, Cin, Ho, Cout, 3, s, 1, hip.PAD_REFLECT), "conv2d_wgrad")
+        assert p["kernel"] == kernel, (H, Cin, Cout, p)
+
+
+def test_bf16_plan_switches_act_only_where_documented():
+    """Each per-call switch of Tune16 (csrc/igemm16_plan.h), at each documented value, on one small descriptor: the fields
+    it documents change, no other field does.  (The six switches read once per process: the next test.)"""
+    launch = {"kernel", "grid", "block", "lds", "tile", "form"}
+    tap = _bf16_desc(2, 8, 16, 4, 32, 3, 2, 1)                      # conv k3 s2: the tap kernel, image-major
+    base = _plan(tap, "conv2d_fwd")
+    assert (base["kernel"], base["form"], base["posmajor"]) == ("nn16_kernel<1, 0, false>", "two", "0"), base
+    assert _plan(tap, "conv2d_fwd", BG_NN16_PIPE=0) == base
+    for v, form, kernel in ((1, "ring", "nn16_kernel<1, 0, false, false, 3, 2>"),
+                            (2, "wide", "nn16_kernel<1, 0, false, false, 3, 4>"),
+                            (3, "phased", "nn16_kernel<4, 0, false, false, 2, 4>")):
+        p = _plan(tap, "conv2d_fwd", BG_NN16_PIPE=v)
+        assert (p["form"], p["kernel"]) == (form, kernel) and _changed(p, base) <= launch, (v, p)
+    ruled = _bf16_desc(512, 32, 192, 16, 384, 3, 2, 1, hip.PAD_REFLECT)         # the rule picks the wide form here
+    assert _plan(ruled, "conv2d_fwd")["form"] == "wide"
+    for v in (0, -1, 7):                                            # set to anything but 1, 2, 3: two stages everywhere
+        assert _plan(ruled, "conv2d_fwd", BG_NN16_PIPE=v)["form"] == "two", v
+    for bn in (128, 192, 256):
+        assert _plan(tap, "conv2d_fwd", BG_NN16X_BN=bn) == base     # (only a launch that takes the phased form reads it)
+        p = _plan(tap, "conv2d_fwd", BG_NN16_PIPE=3, BG_NN16X_BN=bn)
+        assert p["tile"] == "256x%d" % bn and _changed(p, base) <= launch, (bn, p)
+    for v in (1, "auto"):
+        p = _plan(tap, "conv2d_fwd", BG_NN16_MFAST=v)
+        assert _changed(p, base) <= {"mfast"} and (v == "auto" or p["mfast"] == "1"), (v, p)
+    assert _plan(tap, "conv2d_fwd", BG_NN16_MFAST=0) == base
+
+    halo = _bf16_desc(1, 16, 32, 16, 32, 3, 1, 1)                   # conv k3 s1 on 16 x 16: the halo-tile kernel
+    hb = _plan(halo, "conv2d_fwd")
+    assert (hb["kernel"], hb["form"], hb["nt"], hb["nf"]) == ("nn16h_kernel<3, 1, 0>", "halo", "3", "1"), hb
+    assert _plan(halo, "conv2d_fwd", BG_NN16_HALO=1) == hb
+    p = _plan(halo, "conv2d_fwd", BG_NN16_HALO=0)
+    assert p["kernel"].startswith("nn16_kernel<") and p["stats_rows"] == "0" and "nt" not in p, p
+    assert _changed(p, hb) <= launch | {"nt", "nf", "stats_rows", "posmajor", "splitk"} and p["route"] == hb["route"], p
+
+    pm = _bf16_desc(16, 4, 16, 4, 16, 3, 1, 1)                      # deconv k3 s1 on 4 x 4 at 16 images: position-major
+    pb = _plan(pm, "deconv2d_fwd")
+    assert (pb["posmajor"], pb["kernel"]) == ("1", "nn16_kernel<1, 1, true>"), pb
+    assert _plan(pm, "deconv2d_fwd", BG_NN16_POSMAJOR=1) == pb
+    p = _plan(pm, "deconv2d_fwd", BG_NN16_POSMAJOR=0)
+    assert p["posmajor"] == "0" and _changed(p, pb) <= launch | {"posmajor", "splitk", "ws"}, p
+
+    k3s2 = _bf16_desc(1, 32, 32, 16, 32, 3, 2, 1)                   # input gradient of conv k3 s2, 16 x 16 per phase
+    kb = _plan(k3s2, "conv2d_dgrad")
+    assert kb["kernel"].startswith("nn16_kernel<") and _plan(k3s2, "conv2d_dgrad", BG_NN16_HALO_K3S2=0) == kb
+    p = _plan(k3s2, "conv2d_dgrad", BG_NN16_HALO_K3S2=1)
+    assert (p["form"], p["nt"]) == ("halo", "2") and p["route"] == kb["route"], p
+
+    thin = _bf16_desc(2, 64, 8, 32, 96, 3, 2, 1)                    # 8-channel image layer (tests/test_gpu_bf16.py)
+    tb = _plan(thin, "conv2d_dgrad")
+    assert (tb["route"], tb["kernel"], tb["d2s"]) == ("BF16_THIN_D2S", "nn16h_kernel<2, 1, 0, d2s>", "1"), tb
+    assert _plan(thin, "conv2d_dgrad", BG_THIN_D2S=1) == tb
+    p = _plan(thin, "conv2d_dgrad", BG_THIN_D2S=0)
+    assert p["route"] == "BF16_PLAIN" and p["d2s"] == "0" and p["ws"] == tb["ws"], p
+
+    wg = _bf16_desc(2, 16, 32, 16, 192, 3, 1, 1)                    # weight gradient k3 32 -> 192: the ring form by rule
+    wb = _plan(wg, "conv2d_wgrad")
+    assert (wb["kernel"], wb["form"]) == ("tn16x_kernel<0, 32>", "wide"), wb
+    assert _plan(wg, "conv2d_wgrad", BG_TN16X_PHASED=0) == wb
+    assert _plan(wg, "conv2d_wgrad", BG_TN16X_PHASED_BN=256) == wb and _plan(wg, "conv2d_wgrad", BG_TN16X_PHASED_RING=8) == wb
+    wlaunch = {"kernel", "grid", "lds", "tile", "form"}             # (the K partition stays: same sums, same workspace)
+    for env, kernel, tile in ((dict(BG_TN16X_PHASED=1), "tn16x_phased_kernel<0, 192, 6>", "256x192"),
+                              (dict(BG_TN16X_PHASED=1, BG_TN16X_PHASED_BN=256), "tn16x_phased_kernel<0, 256, 6>", "256x256"),
+                              (dict(BG_TN16X_PHASED=1, BG_TN16X_PHASED_RING=8), "tn16x_phased_kernel<0, 192, 8>", "256x192")):
+        p = _plan(wg, "conv2d_wgrad", **env)
+        assert (p["kernel"], p["tile"], p["form"]) == (kernel, tile, "phased") and _changed(p, wb) <= wlaunch, (env, p)
+    nbi = _bf16_desc(2, 16, 256, 16, 512, 1, 1, 0)                  # 512 output channels: 256-wide tiles divide them
+    nb = _plan(nbi, "conv2d_wgrad")
+    assert nb["kernel"] == "tn16x_kernel<0, 32>" and _plan(nbi, "conv2d_wgrad", BG_TN16X_NBI=1) == nb, nb
+    p = _plan(nbi, "conv2d_wgrad", BG_TN16X_NBI=2)
+    assert (p["kernel"], p["tile"]) == ("tn16x_kernel<0, 32, 2>", "256x256"), p
+    assert _changed(p, nb) <= wlaunch | {"splitk", "rows_per_split", "ws"}, p
+    assert _plan(wg, "conv2d_wgrad", BG_TN16X_NBI=2) == wb          # (192 channels: the switch does not apply)
+
+
+def test_bf16_plan_once_switches_act_only_where_documented():
+    """The six switches of Tune16 that are read once per process, each in a child process of its own (started together;
+    bg_conv_plan_describe needs no GPU) that sets the switch before its first plan."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    child = ("import json, sys; sys.path.insert(0, %r); import biggan_tensorflow_amd; from biggan_tensorflow_amd import hip; "
+             "print(json.dumps([hip.plan_describe(hip.BgConvDesc(*d), p) for d, p in json.loads(sys.argv[1])]))" % root)
+    fields = lambda d: [getattr(d, f[0]) for f in d._fields_]                    # noqa: E731
+    wg = _bf16_desc(2, 16, 32, 16, 192, 3, 1, 1)                    # weight gradient on the wide kernel, split 2
+    narrow = _bf16_desc(8, 12, 32, 12, 32, 3, 1, 1)                 # 12 x 12 map: no power of two, the narrow kernel
+    halo = _bf16_desc(1, 16, 32, 16, 32, 3, 1, 1)
+    deep = _bf16_desc(32, 4, 1536, 4, 1536, 3, 1, 1, hip.PAD_REFLECT)           # splits K: the round model decides how far
+    jobs = [("BG_TN16_WIDE", 0, wg, "conv2d_wgrad"), ("BG_TN16X_BK", 64, wg, "conv2d_wgrad"),
+            ("BG_TN16X_WANT", 1, wg, "conv2d_wgrad"), ("BG_TN16_WANT", 1, narrow, "conv2d_wgrad"),
+            ("BG_NN16_HALO_CMAX", 32, halo, "conv2d_fwd"), ("BG_NN16_HALO_CMAX", 16, halo, "conv2d_fwd"),
+            ("BG_NN16_SLOTS", 1 << 20, deep, "conv2d_fwd")]
+    procs = [subprocess.Popen([sys.executable, "-c", child, json.dumps([[fields(d), pn]])], stdout=subprocess.PIPE,
+                              env=dict(os.environ, **{name: str(value)})) for name, value, d, pn in jobs]
+    plans = []
+    for pr in procs:
+        out, _ = pr.communicate(timeout=120)
+        assert pr.returncode == 0
+        plans.append(json.loads(out.decode().strip().splitlines()[-1])[0])
+    wide0, bk64, want1, nwant1, cmax32, cmax16, slots = plans
+
+    split = {"splitk", "rows_per_split", "grid", "ws"}
+    wb = _plan(wg, "conv2d_wgrad")
+    assert (wb["kernel"], wb["lds"]) == ("tn16x_kernel<0, 32>", str(3 * 3 * 32 * 256)) and int(wb["splitk"]) > 1, wb
+    assert (wide0["kernel"], wide0["form"], wide0["tile"]) == ("tn16_kernel<0>", "narrow", "128x128"), wide0
+    assert (bk64["kernel"], bk64["lds"]) == ("tn16x_kernel<0, 64>", str(3 * 3 * 64 * 256)), bk64
+    assert _changed(bk64, wb) == {"kernel", "lds"}, bk64
+    assert want1["splitk"] == "1" and _changed(want1, wb) <= split - {"ws"}, want1      # (the query: still the narrow plan's slabs)
+    nb = _plan(narrow, "conv2d_wgrad")
+    assert nb["kernel"] == "tn16_kernel<0>" and int(nb["splitk"]) > 1, nb
+    assert nwant1["splitk"] == "1" and nwant1["ws"] == "0" and _changed(nwant1, nb) <= split, nwant1
+    assert cmax32 == _plan(halo, "conv2d_fwd")                                        # 32 channels per tap still fit
+    assert cmax16 == _plan(halo, "conv2d_fwd", BG_NN16_HALO=0) and cmax16["kernel"].startswith("nn16_kernel<"), cmax16
+    db = _plan(deep, "conv2d_fwd")
+    assert int(slots["splitk"]) >= int(db["splitk"]) > 1, (slots, db)                 # every grid is one round: split all the way
+    # (tile and split; the pipeline form follows the grid they leave, the block size and LDS follow the form)
+    assert _changed(slots, db) <= {"kernel", "grid", "block", "lds", "tile", "form", "splitk", "ws"}, (slots, db)
+
+
+def test_bf16_plan_without_workspace_runs_unsplit():
+    """A plan that would split K runs unsplit, and uses no workspace, when the caller hands none: an nn16 layer (conv
+    4^2 1536 -> 1536 at 32 images) and a tn16 layer (weight gradient of conv 8^2 768 -> 768 at 64 images)."""
+    for d, entry in ((_bf16_desc(32, 4, 1536, 4, 1536, 3, 1, 1, hip.PAD_REFLECT), "conv2d_fwd"),
+                     (_bf16_desc(64, 8, 768, 8, 768, 3, 1, 1, hip.PAD_REFLECT), "conv2d_wgrad")):
+        asked = _plan(d, entry)
+        assert int(asked["splitk"]) > 1 and int(asked["ws"]) > 0, asked
+        assert _plan(d, entry, int(asked["ws"])) == asked
+        none = _plan(d, entry, 0)
+        assert (none["splitk"], none["ws"]) == ("1", "0"), none
+        short = _plan(d, entry, int(asked["ws"]) - 1)               # slabs that do not fit: unsplit as well
+        assert (short["splitk"], short["ws"]) == ("1", "0"), short
+        if entry == "conv2d_fwd":       # nn16: the plan made with splitting allowed keeps its tile (no re-plan) ...
+            assert (short["tile"], short["kernel"]) == (asked["tile"], asked["kernel"]), (short, asked)
+            assert _changed(short, asked) == {"splitk", "grid", "ws"}, (short, asked)
+            assert none["tile"] != asked["tile"]                    # ... which the plan for no workspace at all need not share
+        else:                           # tn16: neither the wide plan's slabs nor the narrow plan's (3 splits each) fit
+            assert short == none and short["kernel"] == "tn16_kernel<0>", (short, none)
+
+
+def test_depth_to_space_query_agrees_with_the_plan():
+    """bg_conv2d_fwd_d2s_supported is the plan's d2s field, on the shapes of tests/test_subpixel.py and on launches without the
+    store: fp32 tensors, position-major rows (4 x 4 maps at 256 images) and a plan that splits K."""
+    L = hip.lib()
+    shapes = [(256, 32, 384, 192, 3, 1), (256, 64, 192, 96, 3, 1), (256, 32, 384, 192, 2, 0), (256, 64, 192, 96, 2, 0),
+              (256, 4, 64, 16, 3, 1), (2, 4, 1536, 384, 3, 1), (2, 16, 32, 8, 3, 1), (2, 8, 32, 8, 3, 1)]
+    seen = set()
+    for N, h, cin, c, k, lo in shapes:
+        d = hip.conv_desc(N, h, h, cin, h, h, 4 * c, k, 1, lo, 0, hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
+        p = hip.plan_describe(d, "conv2d_fwd_d2s")
+        assert int(p["d2s"]) == L.bg_conv2d_fwd_d2s_supported(d, 2), (N, h, cin, c, k, p)
+        assert p["d2s"] == "0" or (p["splitk"], p["ws"]) == ("1", "0"), p
+        seen.add(p["d2s"])
+    assert seen == {"0", "1"}
+    f32 = hip.conv_desc(256, 32, 32, 384, 32, 32, 768, 3, 1, 1, 0)
+    assert "d2s" not in hip.plan_describe(f32, "conv2d_fwd_d2s") and L.bg_conv2d_fwd_d2s_supported(f32, 2) == 0
