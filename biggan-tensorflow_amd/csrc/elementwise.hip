@@ -1240,8 +1240,8 @@ struct PreluTangentDalphaFn {
 // ------------------------------------------------------------------------------------------
 // small elementwise family
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(EW_BLOCK) void axpby_kernel(const float* __restrict__ x, float a, float* __restrict__ y,
-                                                          float b, int64_t n) {
+// x may be y itself (y = (a + b) y: the averaging and loss-scaling calls), a of add_kernel may be y (a += b)
+__global__ __launch_bounds__(EW_BLOCK) void axpby_kernel(const float* x, float a, float* y, float b, int64_t n) {
     const int64_t n4 = n / 4;
     for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += (int64_t)gridDim.x * EW_BLOCK) {
         float4 xv = ldg4(x + i * 4), yv;
@@ -1257,15 +1257,22 @@ __global__ __launch_bounds__(EW_BLOCK) void axpby_kernel(const float* __restrict
         y[i] = b != 0.f ? a * x[i] + b * y[i] : a * x[i];
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void add_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                        float* __restrict__ y, int64_t n) {
-    const int64_t n4 = n / 4;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += (int64_t)gridDim.x * EW_BLOCK) {
+__global__ __launch_bounds__(EW_BLOCK) void add_kernel(const float* a, const float* __restrict__ b, float* y, int64_t n) {
+    const int64_t n4 = n / 4, step = (int64_t)gridDim.x * EW_BLOCK;
+    int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x;
+    // two items per trip, both loaded before either is stored: without __restrict__ on a / y the compiler may not move a
+    // load across a store, so the order is written out (a thread only ever rewrites what it has read itself)
+    for (; i + step < n4; i += 2 * step) {
+        const int64_t j = i + step;
+        const float4 a0 = ldg4(a + i * 4), b0 = ldg4(b + i * 4), a1 = ldg4(a + j * 4), b1 = ldg4(b + j * 4);
+        stg4(y + i * 4, make_float4(a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w));
+        stg4(y + j * 4, make_float4(a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w));
+    }
+    if (i < n4) {
         const float4 av = ldg4(a + i * 4), bv = ldg4(b + i * 4);
         stg4(y + i * 4, make_float4(av.x + bv.x, av.y + bv.y, av.z + bv.z, av.w + bv.w));
     }
-    for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EW_BLOCK)
-        y[i] = a[i] + b[i];
+    for (i = n4 * 4 + (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += step) y[i] = a[i] + b[i];
 }
 
 __global__ __launch_bounds__(EW_BLOCK) void scale_add_kernel(const float* __restrict__ o,
@@ -1282,11 +1289,18 @@ __global__ __launch_bounds__(EW_BLOCK) void scale_add_kernel(const float* __rest
         y[i] = g * o[i] + x[i];
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void scale_dev_kernel(const float* __restrict__ x, const float* __restrict__ sp,
-                                                              float* __restrict__ y, int64_t n) {
+// x and y may be the same tensor (the Gram-side regulariser rescales in place): no __restrict__ on the pair
+__global__ __launch_bounds__(EW_BLOCK) void scale_dev_kernel(const float* x, const float* __restrict__ sp, float* y,
+                                                              int64_t n) {
     const float s = *sp;
-    for (int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EW_BLOCK)
-        y[i] = s * x[i];
+    const int64_t step = (int64_t)gridDim.x * EW_BLOCK;
+    int64_t i = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x;
+    for (; i + step < n; i += 2 * step) {            // both loads before either store, as in add_kernel
+        const float x0 = x[i], x1 = x[i + step];
+        y[i] = s * x0;
+        y[i + step] = s * x1;
+    }
+    if (i < n) y[i] = s * x[i];
 }
 
 // y = sa * a + sb * b (sa, sb: host scalars or device scalars when the pointers are non-null), n % 4 == 0
@@ -2112,6 +2126,8 @@ int bg_bn_bwd_finalize(const float* part, const float* gamma, int per_sample, do
 
 int bg_box2_down(const float* x, float* y, int N, int H, int W, int C, float scale, void* stream) {
     BG_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0, "bg_box2_down: bad argument");
+    BG_REQUIRE(C % 4 != 0 || (((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0),
+               "bg_box2_down: pointers must be 16-byte aligned when C %% 4 == 0");
     const int64_t total = (int64_t)N * (H / 2) * (W / 2) * C;
     if (C % 4 == 0)
         hipLaunchKernelGGL((box2_down_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0, as_stream(stream), x, y,
@@ -2125,6 +2141,8 @@ int bg_box2_down(const float* x, float* y, int N, int H, int W, int C, float sca
 
 int bg_box2_up(const float* x, float* y, int N, int H, int W, int C, float scale, void* stream) {
     BG_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0, "bg_box2_up: bad argument");
+    BG_REQUIRE(C % 4 != 0 || (((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0),
+               "bg_box2_up: pointers must be 16-byte aligned when C %% 4 == 0");
     const int64_t total = (int64_t)N * H * W * C;
     if (C % 4 == 0)
         hipLaunchKernelGGL((box2_up_kernel<4>), dim3(ew_grid(total / 4)), dim3(EW_BLOCK), 0, as_stream(stream), x, y, N,

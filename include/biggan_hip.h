@@ -449,6 +449,10 @@ int bg_gram16(const void* a, int rows, int cols, int ld, float* out, void* ws, s
  *   forms with BG_F32 - see "bf16-resident data path".
  * ------------------------------------------------------------------------------------------ */
 int bg_bn_stats(const float* x, double* sums, int64_t rows, int C, void* stream);
+/* mean = sums[0:C] / count and var = sums[C:2C] / count - mean^2 are formed in fp64 (a negative var is clamped to 0),
+ *   rstd = 1/sqrt((float) var + eps).  moving_mean / moving_var are nullable, each on its own: a non-NULL one moves to
+ *   moving * momentum + new * (1 - momentum), new = mean | var (times count / (count - 1) when unbiased_moving_var and
+ *   count > 1). */
 int bg_bn_finalize(const double* sums, double count, float eps, float momentum, int unbiased_moving_var,
                    float* mean, float* rstd, float* moving_mean, float* moving_var, int C, void* stream);
 /* inference (ops.py:640-643): mean = pop_mean, rstd = 1/sqrt(pop_var + eps) for the apply kernel below */
@@ -470,8 +474,9 @@ int bg_bn_apply_act_bwd_dx(const float* x, const float* dy, const float* mean, c
                            const float* gamma, const float* beta, int per_sample,
                            const float* alpha, const float* cm, float* dx,
                            int N, int HW, int C, void* stream);
-/* reduce part[3,N,C] -> dgamma/dbeta (per sample: copies; per channel: sums over N), dalpha[C],
- *   cm[2C] = (sum_n gamma_n * part0_n, sum_n gamma_n * part1_n) / count */
+/* reduce part[3,N,C] -> dgamma/dbeta (per sample: [N,C] copies of part1 / part0; per channel: [C] sums over N),
+ *   dalpha[C] = sum_n part2_n (nullable: plane 2 is then not summed into anything),
+ *   cm[2C] = (sum_n gamma_n * part0_n, sum_n gamma_n * part1_n) / count; sums in fp64, rounded once */
 int bg_bn_bwd_finalize(const float* part, const float* gamma, int per_sample, double count,
                        float* dgamma, float* dbeta, float* dalpha, float* cm, int N, int C, void* stream);
 
@@ -512,6 +517,7 @@ int bg_maxpool2_bwd(const float* x, const float* dy, float* dx, int N, int H, in
  * block (avg_pooling forward with scale 1/4, ops.py:512-514; up_sample backward with scale 1);
  * bg_box2_up: y[N,2H,2W,C] = scale * x replicated 2x2 (up_sample = resize_nearest_neighbor x2 forward with
  * scale 1, ops.py:516-519; avg_pooling backward with scale 1/4). */
+/* C % 4 == 0 takes 16-byte accesses: x and y must then be 16-byte aligned (BG_ERR_ARG otherwise; any other C: 4). */
 int bg_box2_down(const float* x, float* y, int N, int H, int W, int C, float scale, void* stream);
 int bg_box2_up(const float* x, float* y, int N, int H, int W, int C, float scale, void* stream);
 
@@ -524,12 +530,15 @@ int bg_softmax_bwd(const float* p, const float* dp, float* ds, int64_t rows, int
 int bg_sum_pool_fwd(const float* x, float* y, int N, int HW, int C, void* stream);
 int bg_sum_pool_bwd(const float* dy, float* dx, int N, int HW, int C, void* stream);
 
-/* y = a*x + b*y elementwise family used by residual adds, gamma*o + x (ops.py:490), tanh (ops.py:539) */
+/* y = a*x + b*y elementwise family used by residual adds, gamma*o + x (ops.py:490), tanh (ops.py:539).
+ * bg_axpby reads y only when b != 0; in place allowed: x == y of bg_axpby (y = (a + b) y), a == y of bg_add, y == x
+ * of bg_scale_dev.  Every other pair of arguments must not overlap.  bg_axpby / bg_add / bg_scale_add take 16-byte
+ * aligned pointers (BG_ERR_ARG otherwise). */
 int bg_axpby(const float* x, float a, float* y, float b, int64_t n, void* stream);
 int bg_add(const float* a, const float* b, float* y, int64_t n, void* stream);            /* y = a + b */
 int bg_scale_add(const float* o, const float* gamma_dev, const float* x, float* y, int64_t n, void* stream);
 int bg_dot(const float* a, const float* b, float* out_accum, int64_t n, void* stream);   /* out += <a,b> */
-int bg_scale_dev(const float* x, const float* s_dev, float* y, int64_t n, void* stream);  /* y = s*x, s a device scalar */
+int bg_scale_dev(const float* x, const float* s_dev, float* y, int64_t n, void* stream);  /* y = s*x, s a device scalar; in place allowed (y == x) */
 int bg_tanh_fwd(const float* x, float* y, int64_t n, void* stream);
 int bg_tanh_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream);
 int bg_bias_grad(const float* dy, float* db, int64_t rows, int C, void* stream);         /* db[c] = sum_rows dy */
