@@ -42,6 +42,15 @@ class BgSnItem(Structure):
                 ("pack_p", c_void_p), ("pack_t", c_void_p), ("taps", c_int32), ("pack_p_ld", c_int32)]
 
 
+class BgSvItem(Structure):
+    """One weight of bg_sv_batch (q [cols, SV_BLOCK] in/out; sv, resid [SV_BLOCK] out); the table lives on the device."""
+    _fields_ = [("w", c_void_p), ("q", c_void_p), ("sv", c_void_p), ("resid", c_void_p), ("ws_offset", c_int64),
+                ("rows", c_int32), ("cols", c_int32)]
+
+
+SV_BLOCK = 8
+
+
 class BgDenseItem(Structure):
     _fields_ = [("x", c_void_p), ("ldx", c_int64), ("w", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("dw", c_void_p),
                 ("db", c_void_p), ("K", c_int32), ("N", c_int32), ("acc_w", c_int32), ("acc_b", c_int32)]
@@ -289,6 +298,8 @@ SIGNATURES = {
     "bg_msssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bg_msssim_level": (c_int, [_P, _P, c_int, c_int64, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "bg_msssim_finish": (c_int, [_P, c_size_t, c_int, c_int, c_int, _P, c_int64, c_int64, _P]),
+    "bg_sv_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "bg_sv_batch": (c_int, [_P, c_int, c_int, _P, c_size_t, _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

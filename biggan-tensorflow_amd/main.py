@@ -75,9 +75,18 @@ FLAGS = [
 #                           the same over random pairs of dataset images (dataset-wide, not per class); 0 (default) is
 #                           off.  --phase test: computed once
 #   --msssim_pairs P        generated pairs per event
+#   --sv_freq N             every N iterations: the top singular values of every weight matrix of G and D (spectrum.py,
+#                           csrc/spectrum.hip) as scalars sv/<variable>/s0 .. in the event file with sv_g_max, sv_d_max,
+#                           sv_resid_max (and sv_sn_ratio_min / _max with --sn) and one "SV: ..." line; 0 (default) is
+#                           off.  --phase test: computed once, written to sv.txt
+#   --sv_k K                values per weight, 1..4
+#   --sv_iters T            iterations per round of the block power iteration (at most 8 rounds per event)
+#   --sv_tol R              rounds stop once every reported residual is <= R: some true sigma^2 then lies within
+#                           R sigma_0^2 of each reported value squared
 EXTRA_FLAGS = [("precision", T, None), ("swd_freq", I, 0), ("swd_images", I, 2048),
                ("nn_freq", I, 0), ("nn_k", I, 3), ("nn_size", I, 64), ("nn_images", I, 0),
-               ("msssim_freq", I, 0), ("msssim_pairs", I, 1024)]
+               ("msssim_freq", I, 0), ("msssim_pairs", I, 1024),
+               ("sv_freq", I, 0), ("sv_k", I, 3), ("sv_iters", I, 8), ("sv_tol", F, 1e-2)]
 
 
 def build_parser():

@@ -187,6 +187,18 @@ class BigGAN(GANBase):
         self.msssim_freq = int(getattr(args, "msssim_freq", 0) or 0)
         self.msssim_pairs = int(getattr(args, "msssim_pairs", 1024) or 1024)
         self._msssim = None                    # metrics.Msssim with the draws of the run, built at the first event
+        # singular-value monitor (extension flags --sv_freq / --sv_k / --sv_iters / --sv_tol; spectrum.py)
+        self.sv_freq = int(getattr(args, "sv_freq", 0) or 0)
+        self.sv_k = int(getattr(args, "sv_k", 3))
+        self.sv_iters = int(getattr(args, "sv_iters", 8))
+        self.sv_tol = float(getattr(args, "sv_tol", 1e-2))
+        if not 1 <= self.sv_k <= 4:
+            raise ValueError("--sv_k %d: 1..4 singular values per weight" % self.sv_k)
+        if not 1 <= self.sv_iters <= 256:
+            raise ValueError("--sv_iters %d: 1..256 iterations per round" % self.sv_iters)
+        if not self.sv_tol > 0.0:
+            raise ValueError("--sv_tol %s: a positive residual" % self.sv_tol)
+        self._sv = None                        # spectrum.SingularValues with the basis of the run, built at the first event
         self.recon_plan = self._recon_plan()
         self.deep = args.deep                                                          # BigGAN.py:20
         self.g_mixed_resblocks = args.g_mixed_resblocks                                # BigGAN.py:40-41
@@ -1583,6 +1595,11 @@ class BigGAN(GANBase):
                         print("MS-SSIM: " + format_scores(scores), flush=True)
                         if self._log_writer is not None:
                             self._log_writer.add_scalars(self.counter - 1, scores)
+                if self.sv_freq > 0 and self.counter % self.sv_freq == 0 and self.rank == 0:
+                    values, line, _ = self.singular_values()       # (rank 0 only: the weights are the same on every rank)
+                    print(line, flush=True)
+                    if self._log_writer is not None:
+                        self._log_writer.add_scalars(self.counter - 1, values)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
             if self._log_writer is not None:
@@ -1978,6 +1995,33 @@ class BigGAN(GANBase):
                 out["msssim_real"] = real
         return out
 
+    # ---- singular-value monitor (spectrum.py) -----------------------------------------------------
+    def singular_values(self):
+        """The top --sv_k singular values of every ``/kernel`` variable of G and D, live weights: (scalars in the order
+        they are logged, the "SV: ..." line, the event as ``spectrum.SingularValues.event`` returns it).  Runs on the
+        current stream outside any captured graph; no collective, so only rank 0 needs to call it.  With --sn the
+        scalars hold sv_sn_ratio_min / _max, the monitor's sigma_0 over the sigma that the last D or G run's spectral norm
+        wrote.  Reads the weights; draws from the monitor's own generator only."""
+        from . import spectrum
+        self._wait_params()                    # (sharded update: the all-gather of the new parameters may be in flight)
+        with torch.no_grad():
+            if self._sv is None:
+                self._sv = spectrum.SingularValues(self.store, self.device, self.sv_k, self.sv_iters, self.sv_tol)
+            result = self._sv.event()
+            sigma_of = None
+            if self.sn:
+                slots = {}
+                for w in result["weights"]:
+                    wn = getattr(self.store.vars[w["name"]], "bg_sn_wn", None)
+                    if wn is not None and getattr(wn, "bg_sigma", None) is not None:
+                        slots[w["name"]] = wn.bg_sigma
+                if slots:
+                    host = torch.cat([t.reshape(1) for t in slots.values()]).cpu().tolist()
+                    table = dict(zip(slots.keys(), host))
+                    sigma_of = table.get
+        values, top = spectrum.scalars(result, self.sv_k, sigma_of)
+        return values, spectrum.format_line(result, top), result
+
     # ---- nearest training images (neighbours.py) -------------------------------------------------
     def nn_plan(self, root="./dataset"):
         from .neighbours import NnPlan
@@ -2094,7 +2138,8 @@ class BigGAN(GANBase):
         floor(sqrt(min(sample_num, batch_size)))^2 EMA samples to ``<result_dir>/<model_dir>/``.  With --swd_freq > 0 the
         checkpoint's quality scores are printed and written to ``swd.txt`` beside them; with --nn_freq > 0 the nearest
         training images of its static samples go to ``nn.png`` / ``nn.txt`` (``nn_noema.*``); with --msssim_freq > 0 its
-        diversity scores are printed and written to ``msssim.txt``."""
+        diversity scores are printed and written to ``msssim.txt``; with --sv_freq > 0 ``sv.txt`` gets one row per monitored
+        weight: name, rows, cols, the --sv_k singular values and their residuals."""
         import numpy as np
         from .utils import save_images, check_folder
         could_load, _ = self.load(self.checkpoint_dir)
@@ -2127,6 +2172,13 @@ class BigGAN(GANBase):
                 with open(os.path.join(result_dir, "msssim.txt"), "w") as f:
                     for k, v in scores.items():
                         f.write("%s\t%.6f\n" % (k, v))
+        if self.sv_freq > 0 and self.rank == 0:
+            _, line, result = self.singular_values()
+            print(line, flush=True)
+            with open(os.path.join(result_dir, "sv.txt"), "w") as f:
+                for w in result["weights"]:
+                    f.write("\t".join([w["name"], str(w["rows"]), str(w["cols"])] + ["%.9g" % x for x in w["sv"]]
+                                      + ["%.3g" % x for x in w["resid"]]) + "\n")
         return paths
 
     # ---- --phase service (BigGAN.py:1298-1369) -----------------------------------------------

@@ -1114,6 +1114,36 @@ int    bg_msssim_finish(const double* ws, size_t ws_bytes, int P, int H, int C, 
                         int64_t row_offset, void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Singular-value monitor: the top singular values of every weight of a network at once (csrc/spectrum.hip, spectrum.py;
+ * an addition to ABI 10: new symbols only).  Block power iteration on W^T W with a basis of BG_SV_BLOCK vectors per weight,
+ * then a Rayleigh-Ritz step.  An item is a weight w[rows][cols] (fp32, row-major; the reshape of BgSnItem) with
+ *   q      [cols][BG_SV_BLOCK] fp32, the basis: orthonormal columns, in and out (it warm-starts the next call)
+ *   sv     [BG_SV_BLOCK] out: the Ritz values sqrt(max(lambda_i, 0)), descending
+ *   resid  [BG_SV_BLOCK] out: || W^T (W q_i) - lambda_i q_i ||_2 / lambda_0 (0 when lambda_0 = 0): some singular value
+ *          squared of W lies within resid[i] * sv[0]^2 of sv[i]^2
+ * b_eff = min(BG_SV_BLOCK, rows, cols): basis columns >= b_eff are set to zero and sv, resid are 0 there.  A direction
+ * that is numerically dependent on the earlier ones (remaining squared norm <= 2^-80 of its squared norm) becomes a zero
+ * column of q; no NaN or Inf is written.  The table lives in device memory; ws_offset is the byte offset (16-byte
+ * aligned) of the item's scratch of bg_sv_workspace_bytes(rows, cols) bytes inside ws, and the call zeroes the part of ws
+ * that it uses.  iters (0..256) iterations of [Y = W Q; Z = W^T Y; Q = orth(Z)], then the Ritz step: 3 * iters + 5
+ * launches for any n_items (1..256); iters = 0 is the Ritz step on the basis as given.  BG_ERR_ARG with a message, before
+ * any launch, for a NULL table, a NULL or misaligned ws, a count out of range or ws_bytes below n_items times the
+ * smallest item's scratch; an item whose own scratch range does not lie inside ws_bytes is left alone by every kernel.
+ * Not bit-reproducible: the second pass adds with fp64 atomics, whose arrival order differs between launches.
+ * ------------------------------------------------------------------------------------------ */
+#define BG_SV_BLOCK 8
+typedef struct BgSvItem {
+    const float* w;        /* [rows, cols] */
+    float* q;              /* [cols, BG_SV_BLOCK], in/out */
+    float* sv;             /* [BG_SV_BLOCK], out */
+    float* resid;          /* [BG_SV_BLOCK], out */
+    int64_t ws_offset;
+    int32_t rows, cols;
+} BgSvItem;
+size_t bg_sv_workspace_bytes(int rows, int cols);
+int    bg_sv_batch(const BgSvItem* items_dev, int n_items, int iters, void* ws, size_t ws_bytes, void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
  * (conv / deconv / gemm families) is bracketed by hipEvents on its stream.
  * bg_prof_collect synchronises the events and returns totals since the last reset.
