@@ -5,6 +5,7 @@ operation is a libbiggan_hip.so launch on the current stream.  Gradients of stor
 written straight into their slice of the flat gradient arena (``scope.Arena``) instead of
 ``Tensor.grad``: the first write of a step overwrites, later ones accumulate.
 """
+import collections
 import math
 import os
 
@@ -731,10 +732,39 @@ def _bias_grad(dy2d, out):
 # ------------------------------------------------------------------------------------------
 # conv / transposed conv
 # ------------------------------------------------------------------------------------------
-def _resident_ok(x, cin, cout, k=1):
-    """The bf16-resident kernels (csrc/igemm16.hip) take channel counts that are multiples of 8 and kernels of at most
-    4 x 4 taps (include/biggan_hip.h); every other layer runs on the fp32-tensor kernels."""
-    return x.dtype == BF16 and cin % 8 == 0 and cout % 8 == 0 and k <= 4
+class ConvRoute(collections.namedtuple("ConvRoute", "kind cast out_dtype")):
+    """What ``conv_route`` answers; ``cast``: a bf16 input is converted to fp32 first."""
+    __slots__ = ()
+
+    def can_accumulate(self, acc):
+        """Whether the launch can add its result into ``acc`` in its epilogue: an accumulator of the result's own type
+        that the call may overwrite (the thin forms fold their 8 channels afterwards; a cast input keeps its own add)."""
+        return (self.kind in ("resident", "f32") and not self.cast and acc.dtype == self.out_dtype
+                and acc.is_contiguous())
+
+
+def conv_route(x_dtype, Cin, Cout, k, out_dtype=None, transposed=False):
+    """The kernels of a k x k convolution (or transposed one) from Cin to Cout channels of an ``x_dtype`` input; reads
+    Precision and its arguments only.
+    resident  the bf16-resident kernels (csrc/igemm16.hip) take channel counts that are multiples of 8 and kernels of at
+              most 4 x 4 taps (include/biggan_hip.h); y is bf16 unless ``out_dtype`` says fp32.
+    thin_in, thin_out   bf16-resident mode, the 3-channel image layers (D's first block: Cin = 3; G_logit: Cout = 3): run
+              on the bf16-resident GEMM kernels with the thin side zero-padded to 8 channels.  The fp32-tensor fallbacks
+              they replace cost 16.8 of 137 ms per config-3 iteration at batch 256 (r02 kernel stats) for 0.3 % of the
+              FLOPs.  y is bf16 (thin input) / fp32 (thin output) unless ``out_dtype`` says otherwise.
+    f32       every other layer: the fp32-tensor kernels (fp32 or bf16 MFMA per Precision.compute; the 3-channel direct
+              kernels where bg_rgbconv_supported says so), fp32 y whatever ``out_dtype``; a bf16 input - channel counts
+              off the 16-byte grid, more than 4 x 4 taps - is cast up first."""
+    if x_dtype == BF16 and Cin % 8 == 0 and Cout % 8 == 0 and k <= 4:
+        return ConvRoute("resident", False, out_dtype or BF16)
+    if Precision.resident and k <= 4 and not transposed:
+        # (the thin side and its rounding residual share the 8 channels: at most 4; a 5 ... 7-channel side - the attention
+        #  projections of a ch = 40 / 48 / 56 model - takes the fp32-tensor kernels like any other odd channel count)
+        if Cin <= 4 and Cout % 8 == 0 and x_dtype in (BF16, torch.float32):
+            return ConvRoute("thin_in", False, out_dtype or BF16)
+        if Cout <= 4 and Cin % 8 == 0 and x_dtype == BF16:
+            return ConvRoute("thin_out", False, out_dtype or torch.float32)
+    return ConvRoute("f32", x_dtype == BF16, torch.float32)
 
 
 def pad_channels(x, C, dtype, axis=-1, mode=hip.PAD_ZERO_FILL):
@@ -752,192 +782,175 @@ def pad_channels(x, C, dtype, axis=-1, mode=hip.PAD_ZERO_FILL):
     return y
 
 
-def _thin_plan(x, cin, cout):
-    """bf16-resident mode, the 3-channel image layers (D's first block: Cin = 3; G_logit: Cout = 3): run on the
-    bf16-resident GEMM kernels with the thin side zero-padded to 8 channels.  The fp32-tensor fallbacks they replace
-    cost 16.8 of 137 ms per config-3 iteration at batch 256 (r02 kernel stats) for 0.3 % of the FLOPs."""
-    if not Precision.resident or x.dtype not in (BF16, torch.float32) or os.environ.get("BG_IMAGE_LAYERS", "") == "fp32":
-        return None                      # (BG_IMAGE_LAYERS=fp32: A/B switch, the fp32-tensor kernels of round 1)
-    # (the thin side and its rounding residual share the 8 channels: at most 4; a 5 ... 7-channel side - the attention
-    #  projections of a ch = 40 / 48 / 56 model - takes the fp32-tensor kernels like any other odd channel count)
-    if cin <= 4 and cout % 8 == 0:
-        return "in"
-    if cout <= 4 and cin % 8 == 0 and x.dtype == BF16:
-        return "out"
-    return None
+def _desc_with(d, **fields):
+    """A copy of the BgConvDesc ``d`` with the named fields changed."""
+    d = hip.BgConvDesc.from_buffer_copy(d)
+    for name, value in fields.items():
+        setattr(d, name, value)
+    return d
+
+
+def _conv_out(ctx, acc, shape, dtype, device):
+    """What a forward launch writes: a fresh tensor, or the accumulator its epilogue adds into (ops.py:313)."""
+    if acc is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert acc.dtype == dtype and acc.is_contiguous(), (acc.dtype, dtype)
+    ctx.mark_dirty(acc)
+    return acc
+
+
+# The forward / backward pairs Conv2dFn dispatches to, called with the library ``L``: one for the thin forms, one for
+# the resident and f32 routes.  A forward gets the contiguous input and the geometry ``g`` (the first eleven BgConvDesc
+# fields) and returns (y, desc, x, w) for its backward; a backward gets the contiguous dy and returns (dx, dw).
+def _thin_fwd(ctx, L, g, x, w, bias, acc=None):
+    N, H, W_, Cin, Ho, Wo, Cout = g[:7]
+    ydt = ctx.route.out_dtype
+    if ctx.route.kind == "thin_in":
+        # x8 = [x_hi | x_lo | 0 0]: the image to ~16 mantissa bits in the otherwise idle padding channels;
+        # forward and wgrad pair it with the kernel duplicated over the two groups of rows
+        x = pad_channels(x, 8, BF16, mode=hip.PAD_SPLIT)
+        d = hip.conv_desc(N, H, W_, 8, *g[4:], hip.COMPUTE_BF16, hip.BF16, hip.BF16 if ydt == BF16 else hip.F32, 1)
+        y = torch.empty((N, Ho, Wo, Cout), dtype=ydt, device=x.device)
+        ws, nb = hip.scratch(L.bg_conv2d_fwd_workspace_bytes, d, x.device)
+        pt = weight_packs(pad_channels(w, 8, torch.float32, axis=2, mode=hip.PAD_DUP))[1]
+        check(L.bg_conv2d_fwd(d, act(x), act(pt), f32(bias), None, act(y), 0, f32(ws), nb, stream()))
+    else:
+        # w8 = [w_hi | w_lo | 0 0] along the output channels: y = y8[:3] + y8[3:6] sees the kernel to ~16 bits
+        b8 = None if bias is None else pad_channels(bias, 8, torch.float32)
+        d = hip.conv_desc(*g[:6], 8, *g[7:], hip.COMPUTE_BF16, hip.BF16, hip.F32, 1)
+        y8 = torch.empty((N, Ho, Wo, 8), dtype=torch.float32, device=x.device)
+        ws, nb = hip.scratch(L.bg_conv2d_fwd_workspace_bytes, d, x.device)
+        pt = weight_packs(pad_channels(w, 8, torch.float32, axis=3, mode=hip.PAD_SPLIT))[1]
+        check(L.bg_conv2d_fwd(d, act(x), act(pt), f32(b8), None, act(y8), 0, f32(ws), nb, stream()))
+        y = pad_channels(y8, Cout, ydt, mode=hip.PAD_FOLD)
+    return y, d, x, w
+
+
+def _thin_bwd(ctx, L, dy):
+    d, x, w = ctx.desc, ctx.x, ctx.w
+    Cin, Cout = w.shape[2], w.shape[3]
+    thin_in = ctx.route.kind == "thin_in"
+    dx = None
+    # thin output: dy8 = [dy_hi | dy_lo | 0 0] - the gradient of the generated image, the 3-channel bottleneck
+    # every generator gradient passes through, enters the GEMMs to ~16 bits
+    dy8 = cast(dy, BF16) if thin_in else pad_channels(dy, 8, BF16, mode=hip.PAD_SPLIT)
+    db16 = _desc_with(d, y_dtype=hip.BF16)
+    if ctx.needs_input_grad[0]:
+        if thin_in:
+            # kernel rows [w_hi | w_lo]: dx = dx8[:3] + dx8[3:6], written by an fp32 epilogue (image gradient)
+            pp = weight_packs(pad_channels(w, 8, torch.float32, axis=2, mode=hip.PAD_SPLIT))[0]
+            dd = _desc_with(db16, x_dtype=hip.F32)
+            dx8 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        else:
+            pp = weight_packs(pad_channels(w, 8, torch.float32, axis=3, mode=hip.PAD_DUP))[0]
+            dd = db16
+            dx8 = torch.empty_like(x)
+        ws, nb = hip.scratch(L.bg_conv2d_dgrad_workspace_bytes, dd, x.device)
+        check(L.bg_conv2d_dgrad(dd, act(dy8), act(pp), None, act(dx8), 0, f32(ws), nb, stream()))
+        dx = pad_channels(dx8, Cin, ctx.in_dtype, mode=hip.PAD_FOLD) if thin_in else dx8
+
+    def wg8(out):
+        # x8 = [x_hi | x_lo] (thin input) or dy8 = [dy_hi | dy_lo] (thin output): dw = the two halves folded
+        nb = L.bg_conv2d_wgrad_workspace_bytes(db16)
+        ws = workspace(nb, x.device)
+        dw8 = torch.empty((d.k, d.k, d.Cin, d.Cout), dtype=torch.float32, device=x.device)
+        check(L.bg_conv2d_wgrad(db16, act(x), act(dy8), f32(dw8), f32(ws), nb, stream()))
+        outer, C, inner = (d.k * d.k, Cin, d.Cout) if thin_in else (d.k * d.k * d.Cin, Cout, 1)
+        check(L.bg_pad_channels(act(dw8), hip.F32, act(out), hip.F32, outer, 8, C, inner, hip.PAD_FOLD, stream()))
+    return dx, param_grad(w, ctx.needs_input_grad[1], wg8)
+
+
+def _plain_fwd(ctx, L, g, x, w, bias, acc):
+    """The resident and the f32 route: one launch on the tensors as they are (the f32 route after its cast)."""
+    N, H, W_, Cin, Ho, Wo, Cout = g[:7]
+    resident = ctx.route.kind == "resident"
+    ptr = act if resident else f32
+    if ctx.route.cast:
+        x = cast(x, torch.float32)         # (odd channel counts: fp32-tensor kernels)
+    if resident:
+        d = hip.conv_desc(*g, hip.COMPUTE_BF16, hip.BF16, hip.BF16 if ctx.route.out_dtype == BF16 else hip.F32, 1)
+    else:
+        w = _c(w)
+        d = hip.conv_desc(*g, Precision.compute)
+    ctx.rgb = not resident and bool(L.bg_rgbconv_supported(d))      # <= 3 output channels: direct HBM-bound kernels
+    r = ctx.d2s
+    if r:                                  # (SubpixelConvFn: the launch stores depth_to_space(y, r) itself)
+        y = torch.empty((N, Ho * r, Wo * r, Cout // (r * r)), dtype=BF16, device=x.device)
+        check(L.bg_conv2d_fwd_d2s(d, act(x), act(weight_packs(w)[1]), f32(bias), None, act(y), r, None, 0, stream()))
+        return y, d, x, w
+    y = _conv_out(ctx, acc, (N, Ho, Wo, Cout), ctx.route.out_dtype, x.device)
+    if ctx.rgb:
+        check(L.bg_rgbconv_fwd(d, f32(x), f32(w), f32(bias), f32(y), int(ctx.acc), stream()))
+    else:
+        ws, nb = hip.scratch(L.bg_conv2d_fwd_workspace_bytes, d, x.device)
+        wk = weight_packs(w)[1] if resident else w
+        check(L.bg_conv2d_fwd(d, ptr(x), ptr(wk), f32(bias), None, ptr(y), int(ctx.acc), f32(ws), nb, stream()))
+    return y, d, x, w
+
+
+def _plain_bwd(ctx, L, dy):
+    d, x, w = ctx.desc, ctx.x, ctx.w
+    resident = ctx.route.kind == "resident"
+    ptr = act if resident else f32
+    fork = ctx.fork if resident else None          # (the fp32-tensor kernels always write a tensor of their own)
+    dx = None
+    if resident:
+        dy = cast(dy, BF16)                # (fp32 when the consumer asked for an fp32 output)
+        d = _desc_with(d, y_dtype=hip.BF16)
+    if ctx.needs_input_grad[0]:
+        dx, add = _fork_target(fork, x)
+        if ctx.rgb:
+            check(L.bg_rgbconv_dgrad(d, f32(dy), f32(w), f32(dx), 0, stream()))
+        else:
+            ws, nb = hip.scratch(L.bg_conv2d_dgrad_workspace_bytes, d, x.device)
+            wk = weight_packs(w)[0] if resident else w
+            check(L.bg_conv2d_dgrad(d, ptr(dy), ptr(wk), None, ptr(dx), int(add), f32(ws), nb, stream()))
+        _fork_done(fork, dx)
+
+    def wg(out):
+        query, launch = L.bg_conv2d_wgrad_workspace_bytes, L.bg_conv2d_wgrad
+        if ctx.rgb:
+            query, launch = L.bg_rgbconv_wgrad_workspace_bytes, L.bg_rgbconv_wgrad
+        nb = query(d)
+        ws = workspace(nb, x.device)
+        check(launch(d, ptr(x), ptr(dy), f32(out), f32(ws), nb, stream()))
+    return dx, param_grad(w, ctx.needs_input_grad[1], wg)
 
 
 class Conv2dFn(Function):
-    """tf.pad(REFLECT)+tf.nn.conv2d(VALID)+bias_add (ops.py:82,94-98) / zero 'SAME'.
-
-    fp32 x: the fp32-tensor kernels (fp32 or bf16 MFMA per Precision.compute), fp32 y.
-    bf16 x: the bf16-resident kernels (packed weights, csrc/igemm16.hip); y is bf16 unless ``out_dtype`` says fp32."""
+    """tf.pad(REFLECT)+tf.nn.conv2d(VALID)+bias_add (ops.py:82,94-98) / zero 'SAME', on the kernels ``conv_route`` names
+    for the input's element type and the layer's shape."""
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, pad_lo, Ho, Wo, pad_mode, out_dtype=None, accumulate_into=None):
         ctx.fork = getattr(x, "bg_fork", None)
+        ctx.d2s = getattr(ctx, "d2s", 0)           # (r where SubpixelConvFn, calling this, found the fused store)
         x = _c(x)
         N, H, W_, Cin = x.shape
         k, _, cin2, Cout = w.shape
         assert cin2 == Cin, (x.shape, w.shape)
-        L = lib()
-        ctx.resident = _resident_ok(x, Cin, Cout, k)
-        ctx.in_dtype = x.dtype
-        ctx.pad8 = None if ctx.resident or k > 4 else _thin_plan(x, Cin, Cout)
-        ctx.acc = accumulate_into is not None
-        if ctx.acc:          # residual sum fused into the epilogue: accumulate_into += conv(x)   (ops.py:313)
-            assert ctx.pad8 is None and tuple(accumulate_into.shape) == (N, Ho, Wo, Cout), "accumulate_into: shape"
-        if ctx.pad8 == "in":
-            # x8 = [x_hi | x_lo | 0 0]: the image to ~16 mantissa bits in the otherwise idle padding channels;
-            # forward and wgrad pair it with the kernel duplicated over the two groups of rows
-            x8 = pad_channels(x, 8, BF16, mode=hip.PAD_SPLIT)
-            ydt = out_dtype or BF16
-            d = hip.conv_desc(N, H, W_, 8, Ho, Wo, Cout, k, stride, pad_lo, pad_mode, hip.COMPUTE_BF16, hip.BF16,
-                              hip.BF16 if ydt == BF16 else hip.F32, 1)
-            y = torch.empty((N, Ho, Wo, Cout), dtype=ydt, device=x.device)
-            ws, nb = hip.scratch(L.bg_conv2d_fwd_workspace_bytes, d, x.device)
-            pt = weight_packs(pad_channels(w, 8, torch.float32, axis=2, mode=hip.PAD_DUP))[1]
-            check(L.bg_conv2d_fwd(d, act(x8), act(pt), f32(bias), None, act(y), 0, f32(ws), nb, stream()))
-            ctx.desc, ctx.rgb = d, False
-            ctx.x, ctx.w, ctx.bias = x8, w, bias
-            return y
-        if ctx.pad8 == "out":
-            # w8 = [w_hi | w_lo | 0 0] along the output channels: y = y8[:3] + y8[3:6] sees the kernel to ~16 bits
-            b8 = None if bias is None else pad_channels(bias, 8, torch.float32)
-            ydt = out_dtype or torch.float32
-            d = hip.conv_desc(N, H, W_, Cin, Ho, Wo, 8, k, stride, pad_lo, pad_mode, hip.COMPUTE_BF16, hip.BF16,
-                              hip.F32, 1)
-            y8 = torch.empty((N, Ho, Wo, 8), dtype=torch.float32, device=x.device)
-            ws, nb = hip.scratch(L.bg_conv2d_fwd_workspace_bytes, d, x.device)
-            pt = weight_packs(pad_channels(w, 8, torch.float32, axis=3, mode=hip.PAD_SPLIT))[1]
-            check(L.bg_conv2d_fwd(d, act(x), act(pt), f32(b8), None, act(y8), 0, f32(ws), nb, stream()))
-            ctx.desc, ctx.rgb = d, False
-            ctx.x, ctx.w, ctx.bias = x, w, bias
-            return pad_channels(y8, Cout, ydt, mode=hip.PAD_FOLD)
-        if x.dtype == BF16 and not ctx.resident:
-            x = cast(x, torch.float32)         # (odd channel counts: fp32-tensor kernels)
-        if ctx.resident:
-            ydt = out_dtype or BF16
-            d = hip.conv_desc(N, H, W_, Cin, Ho, Wo, Cout, k, stride, pad_lo, pad_mode, hip.COMPUTE_BF16, hip.BF16,
-                              hip.BF16 if ydt == BF16 else hip.F32, 1)
-            if ctx.acc:
-                y = accumulate_into
-                assert y.dtype == ydt and y.is_contiguous(), (y.dtype, ydt)
-                ctx.mark_dirty(y)
-            else:
-                y = torch.empty((N, Ho, Wo, Cout), dtype=ydt, device=x.device)
-            ws, nb = hip.scratch(L.bg_conv2d_fwd_workspace_bytes, d, x.device)
-            check(L.bg_conv2d_fwd(d, act(x), act(weight_packs(w)[1]), f32(bias), None, act(y), int(ctx.acc), f32(ws), nb,
-                                  stream()))
-            ctx.desc, ctx.rgb = d, False
-            ctx.x, ctx.w, ctx.bias = x, w, bias
-            return y
-        w = _c(w)
-        d = hip.conv_desc(N, H, W_, Cin, Ho, Wo, Cout, k, stride, pad_lo, pad_mode, Precision.compute)
+        route = ctx.route = conv_route(x.dtype, Cin, Cout, k, out_dtype)
+        ctx.in_dtype, ctx.acc, ctx.bias = x.dtype, accumulate_into is not None, bias
         if ctx.acc:
-            y = accumulate_into
-            assert y.dtype == torch.float32 and y.is_contiguous()
-            ctx.mark_dirty(y)
-        else:
-            y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-        ctx.rgb = bool(L.bg_rgbconv_supported(d))      # <= 3 output channels: direct HBM-bound kernels
-        if ctx.rgb:
-            check(L.bg_rgbconv_fwd(d, f32(x), f32(w), f32(bias), f32(y), int(ctx.acc), stream()))
-        else:
-            ws, nb = hip.scratch(L.bg_conv2d_fwd_workspace_bytes, d, x.device)
-            check(L.bg_conv2d_fwd(d, f32(x), f32(w), f32(bias), None, f32(y), int(ctx.acc), f32(ws), nb, stream()))
-        ctx.desc = d
-        ctx.x, ctx.w, ctx.bias = x, w, bias
+            assert route.kind in ("resident", "f32") and tuple(accumulate_into.shape) == (N, Ho, Wo, Cout), \
+                "accumulate_into: shape"
+        fwd = _plain_fwd if route.kind in ("resident", "f32") else _thin_fwd
+        y, ctx.desc, ctx.x, ctx.w = fwd(ctx, lib(), (N, H, W_, Cin, Ho, Wo, Cout, k, stride, pad_lo, pad_mode), x, w,
+                                        bias, accumulate_into)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         dy = _c(dy)
-        d, x, w, bias = ctx.desc, ctx.x, ctx.w, ctx.bias
-        L = lib()
-        dx = None
+        w, bias = ctx.w, ctx.bias
         db = None
-        if ctx.pad8:
-            Cin, Cout = w.shape[2], w.shape[3]
-            thin_in = ctx.pad8 == "in"
-            if bias is not None:
-                db = param_grad(bias, ctx.needs_input_grad[2], lambda out: _bias_grad(dy.view(-1, Cout), out))
-            # thin output: dy8 = [dy_hi | dy_lo | 0 0] - the gradient of the generated image, the 3-channel bottleneck
-            # every generator gradient passes through, enters the GEMMs to ~16 bits
-            dy8 = cast(dy, BF16) if thin_in else pad_channels(dy, 8, BF16, mode=hip.PAD_SPLIT)
-            db16 = hip.conv_desc(d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.k, d.stride, d.pad_lo, d.pad_mode,
-                                 hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
-            if ctx.needs_input_grad[0]:
-                if thin_in:
-                    # kernel rows [w_hi | w_lo]: dx = dx8[:3] + dx8[3:6], written by an fp32 epilogue (image gradient)
-                    pp = weight_packs(pad_channels(w, 8, torch.float32, axis=2, mode=hip.PAD_SPLIT))[0]
-                    dd = hip.conv_desc(d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.k, d.stride, d.pad_lo, d.pad_mode,
-                                       hip.COMPUTE_BF16, hip.F32, hip.BF16, 1)
-                    dx8 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-                else:
-                    pp = weight_packs(pad_channels(w, 8, torch.float32, axis=3, mode=hip.PAD_DUP))[0]
-                    dd = db16
-                    dx8 = torch.empty_like(x)
-                ws, nb = hip.scratch(L.bg_conv2d_dgrad_workspace_bytes, dd, x.device)
-                check(L.bg_conv2d_dgrad(dd, act(dy8), act(pp), None, act(dx8), 0, f32(ws), nb, stream()))
-                dx = pad_channels(dx8, Cin, ctx.in_dtype, mode=hip.PAD_FOLD) if thin_in else dx8
-
-            def wg8(out):
-                # x8 = [x_hi | x_lo] (thin input) or dy8 = [dy_hi | dy_lo] (thin output): dw = the two halves folded
-                nb = L.bg_conv2d_wgrad_workspace_bytes(db16)
-                ws = workspace(nb, x.device)
-                dw8 = torch.empty((d.k, d.k, d.Cin, d.Cout), dtype=torch.float32, device=x.device)
-                check(L.bg_conv2d_wgrad(db16, act(x), act(dy8), f32(dw8), f32(ws), nb, stream()))
-                if thin_in:
-                    check(L.bg_pad_channels(act(dw8), hip.F32, act(out), hip.F32, d.k * d.k, 8, Cin, d.Cout,
-                                            hip.PAD_FOLD, stream()))
-                else:
-                    check(L.bg_pad_channels(act(dw8), hip.F32, act(out), hip.F32, d.k * d.k * d.Cin, 8, Cout, 1,
-                                            hip.PAD_FOLD, stream()))
-            dw = param_grad(w, ctx.needs_input_grad[1], wg8)
-            ctx.x = ctx.w = ctx.bias = None
-            return dx, dw, db, None, None, None, None, None, None, None
         if bias is not None:
-            db = param_grad(bias, ctx.needs_input_grad[2], lambda out: _bias_grad(dy.view(-1, d.Cout), out))
-        if ctx.resident:
-            dyb = cast(dy, BF16)               # (fp32 when the consumer asked for an fp32 output)
-            db16 = hip.conv_desc(d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.k, d.stride, d.pad_lo, d.pad_mode,
-                                 hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
-            if ctx.needs_input_grad[0]:
-                dx, add = _fork_target(ctx.fork, x)
-                ws, nb = hip.scratch(L.bg_conv2d_dgrad_workspace_bytes, db16, x.device)
-                check(L.bg_conv2d_dgrad(db16, act(dyb), act(weight_packs(w)[0]), None, act(dx), int(add), f32(ws), nb,
-                                        stream()))
-                _fork_done(ctx.fork, dx)
-
-            def wg16(out):
-                nb = L.bg_conv2d_wgrad_workspace_bytes(db16)
-                ws = workspace(nb, x.device)
-                check(L.bg_conv2d_wgrad(db16, act(x), act(dyb), f32(out), f32(ws), nb, stream()))
-            dw = param_grad(w, ctx.needs_input_grad[1], wg16)
-            ctx.x = ctx.w = ctx.bias = None
-            return dx, dw, db, None, None, None, None, None, None, (dy if ctx.acc else None)
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            if ctx.rgb:
-                check(L.bg_rgbconv_dgrad(d, f32(dy), f32(w), f32(dx), 0, stream()))
-            else:
-                ws, nb = hip.scratch(L.bg_conv2d_dgrad_workspace_bytes, d, x.device)
-                check(L.bg_conv2d_dgrad(d, f32(dy), f32(w), None, f32(dx), 0, f32(ws), nb, stream()))
-
-        def wg(out):
-            if ctx.rgb:
-                nb = L.bg_rgbconv_wgrad_workspace_bytes(d)
-                ws = workspace(nb, x.device)
-                check(L.bg_rgbconv_wgrad(d, f32(x), f32(dy), f32(out), f32(ws), nb, stream()))
-                return
-            nb = L.bg_conv2d_wgrad_workspace_bytes(d)
-            ws = workspace(nb, x.device)
-            check(L.bg_conv2d_wgrad(d, f32(x), f32(dy), f32(out), f32(ws), nb, stream()))
-        dw = param_grad(w, ctx.needs_input_grad[1], wg)
+            db = param_grad(bias, ctx.needs_input_grad[2], lambda out: _bias_grad(dy.view(-1, w.shape[3]), out))
+        bwd = _plain_bwd if ctx.route.kind in ("resident", "f32") else _thin_bwd
+        dx, dw = bwd(ctx, lib(), dy)
         ctx.x = ctx.w = ctx.bias = None
         if dx is not None:
-            dx = cast(dx, ctx.in_dtype)
+            dx = cast(dx, ctx.in_dtype)            # (the f32 route of a bf16 input; every other dx has that type)
         return dx, dw, db, None, None, None, None, None, None, (dy if ctx.acc else None)
 
 
@@ -992,23 +1005,16 @@ class SubpixelConvFn(Function):
         assert cin2 == Cin and C4 % (r * r) == 0, (x.shape, w.shape, r)
         C = C4 // (r * r)
         ctx.r = r
-        L = lib()
-        if _fuse_d2s() and r == 2 and out_dtype is None and _resident_ok(x, Cin, C4) and C % 8 == 0:
-            d = hip.conv_desc(N, H, W_, Cin, H, W_, C4, k, 1, pad_lo, pad_mode, hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
-            if L.bg_conv2d_fwd_d2s_supported(d, r):
-                ctx.fork = getattr(x, "bg_fork", None)
-                x = _c(x)
-                ctx.resident, ctx.in_dtype, ctx.pad8, ctx.acc, ctx.rgb = True, x.dtype, None, False, False
-                y = torch.empty((N, H * r, W_ * r, C), dtype=BF16, device=x.device)
-                check(L.bg_conv2d_fwd_d2s(d, act(x), act(weight_packs(w)[1]), f32(bias), None, act(y), r, None, 0,
-                                          stream()))
-                ctx.desc = d
-                ctx.x, ctx.w, ctx.bias = x, w, bias
-                return y
-        if out_dtype is None and x.dtype == BF16 and _resident_ok(x, Cin, C4) and C % 8:
-            out_dtype = torch.float32          # (a bf16 run of C channels off the 16-byte grid: shuffled as fp32)
-        y4 = Conv2dFn.forward(ctx, x, w, bias, 1, pad_lo, H, W_, pad_mode, out_dtype, None)
-        return depth_to_space(y4, r)
+        ctx.d2s = 0
+        # (the route sees the layer's own k: above 4 x 4 taps it is not resident and the fused store is not asked for)
+        if out_dtype is None and conv_route(x.dtype, Cin, C4, k).kind == "resident":
+            if C % 8:
+                out_dtype = torch.float32          # (a bf16 run of C channels off the 16-byte grid: shuffled as fp32)
+            elif r == 2 and _fuse_d2s():
+                d = hip.conv_desc(N, H, W_, Cin, H, W_, C4, k, 1, pad_lo, pad_mode, hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
+                ctx.d2s = r if lib().bg_conv2d_fwd_d2s_supported(d, r) else 0
+        y = Conv2dFn.forward(ctx, x, w, bias, 1, pad_lo, H, W_, pad_mode, out_dtype, None)
+        return y if ctx.d2s else depth_to_space(y, r)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1028,30 +1034,23 @@ class Deconv2dFn(Function):
         N, H, W_, Cin = x.shape
         k, _, Cout, cin2 = w.shape
         assert cin2 == Cin, (x.shape, w.shape)
-        ctx.resident = _resident_ok(x, Cin, Cout, k)
+        ctx.route = conv_route(x.dtype, Cin, Cout, k, transposed=True)
+        resident = ctx.route.kind == "resident"
         ctx.in_dtype = x.dtype
-        if x.dtype == BF16 and not ctx.resident:
+        g = (N, H, W_, Cin, H * stride, W_ * stride, Cout, k, stride, pad_lo, hip.PAD_ZERO)
+        if ctx.route.cast:
             x = cast(x, torch.float32)
-        ydt = BF16 if ctx.resident else torch.float32
-        if ctx.resident:
-            d = hip.conv_desc(N, H, W_, Cin, H * stride, W_ * stride, Cout, k, stride, pad_lo, hip.PAD_ZERO,
-                              hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
+        if resident:
+            d = hip.conv_desc(*g, hip.COMPUTE_BF16, hip.BF16, hip.BF16, 1)
         else:
             w = _c(w)
-            d = hip.conv_desc(N, H, W_, Cin, H * stride, W_ * stride, Cout, k, stride, pad_lo, hip.PAD_ZERO,
-                              Precision.compute)
-        if accumulate_into is not None:
-            y = accumulate_into          # residual sum fused into the epilogue: y += deconv(x)
-            assert y.dtype == ydt, (y.dtype, ydt)
-            ctx.mark_dirty(y)
-            acc = 1
-        else:
-            y = torch.empty((N, H * stride, W_ * stride, Cout), dtype=ydt, device=x.device)
-            acc = 0
+            d = hip.conv_desc(*g, Precision.compute)
+        y = _conv_out(ctx, accumulate_into, (N, H * stride, W_ * stride, Cout), ctx.route.out_dtype, x.device)
+        acc = int(accumulate_into is not None)
         L = lib()
         ws, nb = hip.scratch(L.bg_deconv2d_fwd_workspace_bytes, d, x.device)
-        wk = weight_packs(w)[0] if ctx.resident else w
-        snb = int(L.bg_deconv2d_fwd_stats_workspace_bytes(d)) if (stats_box is not None and ctx.resident) else 0
+        wk = weight_packs(w)[0] if resident else w
+        snb = int(L.bg_deconv2d_fwd_stats_workspace_bytes(d)) if (stats_box is not None and resident) else 0
         if snb > 0:
             sums = zeros(2 * Cout, torch.float64, x.device)
             sws = workspace(snb, x.device)
@@ -1071,15 +1070,16 @@ class Deconv2dFn(Function):
         d, x, w, bias = ctx.desc, ctx.x, ctx.w, ctx.bias
         L = lib()
         dx = None
-        if ctx.resident:
+        resident = ctx.route.kind == "resident"
+        fork = None if ctx.route.cast else ctx.fork        # (the fork's buffer has the input's type, dx here is fp32)
+        if resident:
             dy = cast(dy, BF16)
         if ctx.needs_input_grad[0]:
-            dx, add = _fork_target(ctx.fork if x.dtype == ctx.in_dtype else None, x)
+            dx, add = _fork_target(fork, x)
             ws, nb = hip.scratch(L.bg_deconv2d_dgrad_workspace_bytes, d, x.device)
-            wk = weight_packs(w)[1] if ctx.resident else w
+            wk = weight_packs(w)[1] if resident else w
             check(L.bg_deconv2d_dgrad(d, act(dy), act(wk), None, act(dx), int(add), f32(ws), nb, stream()))
-            if x.dtype == ctx.in_dtype:
-                _fork_done(ctx.fork, dx)
+            _fork_done(fork, dx)
 
         def wg(out):
             nb = L.bg_deconv2d_wgrad_workspace_bytes(d)

@@ -255,16 +255,12 @@ def conv(x, channels, opt, kernel=4, stride=2, pad=0, dilation=1, use_bias=True,
                      Fn.Conv2dFn.apply(x.t, wk, None, stride, pad_lo, Ho, Wo, pad_mode))
             return y if _accumulate_into is None else _add(y, _accumulate_into)
         acc = _accumulate_into
-        if acc is not None and os.environ.get("BG_FUSE_RESIDUAL", "1") == "0":       # A/B switch: separate add kernel
+        # (the route is Conv2dFn's own, so a kernel above 4 x 4 next to a 3-channel side is no thin form and may fuse; no
+        #  caller that passes _accumulate_into uses a kernel above 3; on the fp32-tensor route the result is fp32
+        #  whatever _out_dtype says, so a bf16 accumulator there takes the separate add)
+        if acc is not None and not Fn.conv_route(x.dtype, Cin, channels, kernel, _out_dtype).can_accumulate(acc):
             y = Fn.Conv2dFn.apply(x, wk, bias, stride, pad_lo, Ho, Wo, pad_mode, _out_dtype)
             return _add(y if _out_dtype is not None else _resident_out(y), acc)
-        if acc is not None:
-            # the fused form needs an accumulator of the result's own type and shape that this call may overwrite
-            want = (_out_dtype or (torch.bfloat16 if Fn._resident_ok(x, Cin, channels, kernel) else torch.float32))
-            if (acc.dtype != want or not acc.is_contiguous() or Fn._thin_plan(x, Cin, channels) is not None
-                    or (x.dtype == torch.bfloat16 and not Fn._resident_ok(x, Cin, channels, kernel))):
-                y = Fn.Conv2dFn.apply(x, wk, bias, stride, pad_lo, Ho, Wo, pad_mode, _out_dtype)
-                return _add(y if _out_dtype is not None else _resident_out(y), acc)
         y = Fn.Conv2dFn.apply(x, wk, bias, stride, pad_lo, Ho, Wo, pad_mode, _out_dtype, acc)
         return y if _out_dtype is not None else _resident_out(y)
 
@@ -1051,15 +1047,14 @@ def _act_alpha(act, x):
     return False, None
 
 
-def _bn_out_dtype(x, out_fp32):
-    """bf16-resident mode: batch-norm outputs feed convolutions, so they are written as bf16 (fp32 on request: the
-    3-channel RGB head reads fp32)."""
+def _bn_out_dtype(x):
+    """bf16-resident mode: batch-norm outputs feed convolutions, so they are written as bf16."""
     if _is_meta(x) or not Fn.Precision.resident:
         return None
-    return torch.float32 if out_fp32 else torch.bfloat16
+    return torch.bfloat16
 
 
-def _bn_act(x, z, opt, _out_fp32=False):
+def _bn_act(x, z, opt):
     """(cond_)bn followed by opt['act'], fused into one apply kernel when the activation is PReLU/ReLU."""
     fused_types = ('bn', 'batch_norm', 'batch_norm_broken_renorm', 'batch_renorm')
     if opt.get("bn", {}).get("type", "bn") in fused_types and opt["act"] in (prelu, relu):
@@ -1069,7 +1064,7 @@ def _bn_act(x, z, opt, _out_fp32=False):
                 return batch_renorm(x, opt=opt, scope='batch_renorm', _act=opt["act"])
             return condition_batch_renorm(x, z, opt=opt, scope='batch_renorm', _act=opt["act"])
         if z is None:
-            return batch_norm(x, opt=opt, scope=scope, _act=opt["act"], _out_fp32=_out_fp32)
+            return batch_norm(x, opt=opt, scope=scope, _act=opt["act"])
         return condition_batch_norm(x, z, opt=opt, scope=scope, _act=opt["act"])
     x = bn(x, opt=opt) if z is None else cond_bn(x, z, opt=opt)
     return opt["act"](x)
@@ -1085,7 +1080,7 @@ def bn_glu(x, opt={}, scope='batch_norm'):
     return glu(bn(x, opt=opt, scope=scope))
 
 
-def batch_norm(x, opt={}, scope='batch_norm', _act=None, _out_fp32=False, _glu=False):
+def batch_norm(x, opt={}, scope='batch_norm', _act=None, _glu=False):
     """ops.py:580-585: tf.layers.batch_normalization(momentum, epsilon=1e-5, training).  ``_glu`` (extension): the GLU
     that follows is applied by the same kernel."""
     C = x.shape[-1]
@@ -1105,7 +1100,7 @@ def batch_norm(x, opt={}, scope='batch_norm', _act=None, _out_fp32=False, _glu=F
     if _glu:
         return _resident_out(Fn.BnGluFn.apply(x, gamma, beta, mm, mv, momentum, 1e-05, True, _run.reduce_fn, _run.world))
     return Fn.BnActFn.apply(x, gamma, beta, alpha, mm, mv, momentum, 1e-05, True, bool(opt["is_training"]),
-                            _run.reduce_fn, _run.world, None, _bn_out_dtype(x, _out_fp32))
+                            _run.reduce_fn, _run.world, None, _bn_out_dtype(x))
 
 
 def normalize_renorm_clipping_params(renorm_clipping):
@@ -1142,7 +1137,7 @@ def batch_renorm(x, opt={}, scope='batch_renorm', _act=None):
                   rmin=clip["rmin"], rmax=clip["rmax"], dmax=clip["dmax"],
                   decay=opt.get("bn", {}).get("renorm_momentum", 0.9))
     return Fn.BnActFn.apply(x, gamma, beta, alpha, mm, mv, opt.get("bn", {}).get("momentum", 0.98), 1e-05, False,
-                            bool(opt["is_training"]), _run.reduce_fn, _run.world, renorm, _bn_out_dtype(x, False))
+                            bool(opt["is_training"]), _run.reduce_fn, _run.world, renorm, _bn_out_dtype(x))
 
 
 def condition_batch_norm(x, z, opt={}, scope='batch_norm', _act=None):
@@ -1161,7 +1156,7 @@ def condition_batch_norm(x, z, opt={}, scope='batch_norm', _act=None):
     if _is_meta(x):
         return _meta(x.shape)
     return Fn.BnActFn.apply(x, gamma, beta, alpha, test_mean, test_var, decay, epsilon, False,
-                            bool(opt["is_training"]), _run.reduce_fn, _run.world, None, _bn_out_dtype(x, False))
+                            bool(opt["is_training"]), _run.reduce_fn, _run.world, None, _bn_out_dtype(x))
 
 
 def condition_batch_renorm(x, z, opt={}, scope='batch_renorm', _act=None):
@@ -1199,7 +1194,7 @@ def condition_batch_renorm(x, z, opt={}, scope='batch_renorm', _act=None):
                   update=int(not shared), rmin=clip["rmin"], rmax=clip["rmax"], dmax=clip["dmax"],
                   decay=renorm_decay, fadein_decay=renorm_fadein_decay)
     return Fn.BnActFn.apply(x, gamma, beta, alpha, test_mean, test_var, test_decay, epsilon, False,
-                            bool(opt["is_training"]), _run.reduce_fn, _run.world, renorm, _bn_out_dtype(x, False))
+                            bool(opt["is_training"]), _run.reduce_fn, _run.world, renorm, _bn_out_dtype(x))
 
 
 def spectral_norm(w, iteration=1, _shape_only=False):

@@ -21,7 +21,7 @@ from tests.launch_replay import BF16, F32, PAD_REFLECT, PAD_ZERO, Call
 #   (rule, the sentence of include/biggan_hip.h that documents it, predicate(call) -> bool);
 # a narrowed geometry must be rejected by the FORWARD entry too (error code + message), and at most MAX_REJECTED of one
 # family's calls (convolution, transposed convolution, attention16, attention2: ``family``) may be narrowed.  Nothing
-# model.py can build may match a row: functional._resident_ok sends a layer with more than 4 x 4 taps to the fp32-tensor
+# model.py can build may match a row: functional.conv_route sends a layer with more than 4 x 4 taps to the fp32-tensor
 # kernels before a descriptor of this kind is ever made.
 def _resident_wide_kernel(call):
     """bf16-resident forward / input-gradient launch (the tap kernels of csrc/igemm16.hip walk at most 4 taps per axis)."""

@@ -86,7 +86,7 @@ def test_conv_bf16(precision, N, H, Cin, Cout, k, s):
                                                   (2, 32, 96, 3, 3, 1, torch.bfloat16)])
 def test_image_layers_run_on_the_resident_kernels(N, H, Cin, Cout, k, s, xdt):
     """bf16-resident mode: the 3-channel layers go through the bf16 GEMM kernels with the thin side zero-padded to 8
-    channels (functional._thin_plan); same tolerance as every other bf16 convolution, padded channels receive and
+    channels (functional.conv_route); same tolerance as every other bf16 convolution, padded channels receive and
     produce exact zeros (the gradient of the image / of the 3-channel kernel has no contribution from them)."""
     from biggan_tensorflow_amd import functional as Fn, hip
     Fn.set_precision("bf16")
@@ -813,7 +813,7 @@ def _check_grads(gan, ref_grads, tol=4e-1, p90_tol=2e-1, median_tol=1e-1):
     64^2 / ch 16 worst 0.16, median 0.066; 128^2 / ch 96 at batch 2 median 0.094, the dense / skip kernels of the first
     generator block 0.16-0.18, and one outlier at 0.27-0.34, generator/first/prelu/alpha - 1536 slopes each summing
     32 products at this batch; its value moves by that much between builds whose arithmetic differs only in summation
-    order, and is the same with the image layers on the fp32-tensor kernels (BG_IMAGE_LAYERS=fp32: 0.29)."""
+    order, and was the same with the image layers on the fp32-tensor kernels (0.29)."""
     errs = {}
     for k, g in ref_grads.items():
         if k.endswith("self_attention/f_conv/bias") or k.endswith("self_attention/gamma"):

@@ -899,3 +899,96 @@ def test_depth_to_space_query_agrees_with_the_plan():
     assert seen == {"0", "1"}
     f32 = hip.conv_desc(256, 32, 32, 384, 32, 32, 768, 3, 1, 1, 0)
     assert "d2s" not in hip.plan_describe(f32, "conv2d_fwd_d2s") and L.bg_conv2d_fwd_d2s_supported(f32, 2) == 0
+
+
+# ---- conv_route: the one place that names a convolution's kernel family (host only) ----
+def _route_cases():
+    with open(os.path.join(os.path.dirname(__file__), "golden", "conv_route_traces.json")) as fh:
+        return json.load(fh)["cases"]
+
+
+def _acc_like(dtype, contiguous=True):
+    t = torch.empty(2, 2, dtype=dtype)
+    return t if contiguous else t[:, :1]
+
+
+def test_conv_route_matches_the_recorded_results():
+    """For every case of tests/golden/conv_route_traces.json (recorded from the wrappers before conv_route existed):
+    the route's result type is the recorded one, and can_accumulate says whether the result was the accumulator."""
+    from biggan_tensorflow_amd import functional as Fn
+    DT = {"fp32": torch.float32, "bf16": torch.bfloat16, None: None}
+    cases = _route_cases()
+    assert len(cases) >= 38
+    try:
+        for name, rec in cases.items():
+            c = rec["case"]
+            Fn.set_precision(c["mode"])
+            xdt, out = DT[c["x"]], DT[c["out"]]
+            if c["fn"] == "subpixel":
+                # SubpixelConvFn asks for an fp32 result where the shuffle cannot move bf16 runs of C channels
+                if out is None and Fn.conv_route(xdt, c["cin"], 4 * c["cout"], c["k"]).kind == "resident" and c["cout"] % 8:
+                    out = torch.float32
+                route = Fn.conv_route(xdt, c["cin"], 4 * c["cout"], c["k"], out)
+            else:
+                route = Fn.conv_route(xdt, c["cin"], c["cout"], c["k"], out, transposed=c["fn"] == "deconv")
+            assert str(route.out_dtype) == "torch." + rec["outputs"]["y"][0], name
+            fused = c["acc"] is not None and route.can_accumulate(_acc_like(DT[c["acc"]], c["acc_contig"]))
+            assert fused == rec["y_is_accumulator"], name
+            assert (route.kind in ("thin_in", "thin_out")) == ("thin" in name), name
+            assert route.cast == any(call[0] == "bg_cast" for call in rec["calls"][:1]), name
+    finally:
+        Fn.set_precision("fp32")
+
+
+def test_conv_fuse_decision_is_the_former_predicate_up_to_four_taps():
+    """ops.conv fuses a residual sum where conv_route(...).can_accumulate(acc).  For k <= 4 that is the predicate ops.conv
+    spelled out itself before (copied below); for k > 4 the former copy also refused every layer with a thin input side
+    although Conv2dFn runs those on the fp32-tensor kernels, which can accumulate: exactly the rows listed."""
+    from biggan_tensorflow_amd import functional as Fn
+    BF, F32 = torch.bfloat16, torch.float32
+
+    def resident_ok(xdt, cin, cout, k=1):
+        return xdt == BF and cin % 8 == 0 and cout % 8 == 0 and k <= 4
+
+    def thin_plan(xdt, cin, cout):
+        if not Fn.Precision.resident or xdt not in (BF, F32):
+            return None
+        if cin <= 4 and cout % 8 == 0:
+            return "in"
+        if cout <= 4 and cin % 8 == 0 and xdt == BF:
+            return "out"
+        return None
+
+    def former(xdt, cin, cout, k, acc, out=None):
+        want = out or (BF if resident_ok(xdt, cin, cout, k) else F32)
+        return not (acc.dtype != want or not acc.is_contiguous() or thin_plan(xdt, cin, cout) is not None
+                    or (xdt == BF and not resident_ok(xdt, cin, cout, k)))
+
+    chans = (1, 3, 4, 5, 8, 12, 16)
+    changed = set()
+    try:
+        for mode in ("fp32", "bf16-staged", "bf16"):
+            Fn.set_precision(mode)
+            for xdt in (F32, BF):
+                for cin in chans:
+                    for cout in chans:
+                        for k in (1, 3, 4, 5):
+                            for adt in (F32, BF):
+                                for contig in (True, False):
+                                    acc = _acc_like(adt, contig)
+                                    now = Fn.conv_route(xdt, cin, cout, k).can_accumulate(acc)
+                                    if k <= 4:
+                                        assert now == former(xdt, cin, cout, k, acc), (mode, xdt, cin, cout, k, adt, contig)
+                                    elif now != former(xdt, cin, cout, k, acc):
+                                        assert now
+                                        changed.add((mode, xdt, cin, cout, k, adt, contig))
+                                    # with an ``_out_dtype``: the former copy believed it on the fp32-tensor route too,
+                                    # whose result is fp32 whatever it says (the fused call then hit Conv2dFn's assert)
+                                    for out in (F32, BF):
+                                        route = Fn.conv_route(xdt, cin, cout, k, out)
+                                        if route.can_accumulate(acc) != former(xdt, cin, cout, k, acc, out):
+                                            assert route.kind == "f32" and not route.cast and (k > 4 or out == BF), \
+                                                (mode, xdt, cin, cout, k, adt, contig, out)
+    finally:
+        Fn.set_precision("fp32")
+    assert changed == {("bf16", F32, cin, cout, 5, F32, True) for cin in (1, 3, 4) for cout in (8, 16)}
