@@ -401,6 +401,50 @@ def msssim_finish(ws, P, H, C, scores, row_offset=0):
     return scores
 
 
+# ---- radial power spectrum of image sets (csrc/powerspec.hip; metrics.py drives them).  No autograd anywhere. ----
+def ps_bins(S):
+    """Radial bins of side S: the corner (S/2, S/2) is the last one."""
+    return (math.isqrt(2 * int(S) * int(S)) + 1) // 2 + 1
+
+
+def ps_workspace(n, S, device):
+    """The twiddle table and the row transforms of n images of side S: what ``ps_power`` works in."""
+    nb = int(lib().bg_ps_workspace_bytes(int(n), int(S)))
+    if nb == 0:
+        raise RuntimeError("ps_workspace: n=%d S=%d (n >= 1, S a power of two from 16 to 512)" % (n, S))
+    return torch.empty(nb // 8, dtype=torch.float64, device=device)
+
+
+def ps_power(x, power=None, ws=None):
+    """x [n,S,S,C] fp32 or bf16 in [-1,1] -> ``power`` fp32 [n,S,S/2+1] = |DFT2(luminance)|^2 / S^4 on the half plane
+    kx = 0..S/2, row ky in DFT order.  ``ws``: ``ps_workspace(n, S)`` or larger."""
+    x = _swd_images("ps_power", x)
+    n, S, _, C = x.shape
+    if ws is None:
+        ws = ps_workspace(n, S, x.device)
+    if power is None:
+        power = torch.empty(n, S, S // 2 + 1, dtype=torch.float32, device=x.device)
+    pp = _swd_typed("ps_power", "power", power, torch.float32, (n, S, S // 2 + 1))
+    pw = _swd_typed("ps_power", "ws", ws, torch.float64, (ws.numel(),))
+    check(lib().bg_ps_power(act(x), dt(x), n, S, C, pp, pw, ws.numel() * 8, stream()))
+    return power
+
+
+def ps_profile(power, profiles=None, sum2d=None):
+    """``power`` fp32 [n,S,S/2+1] -> ``profiles`` fp64 [n, ps_bins(S)], the azimuthal average of every image over the full
+    plane; with ``sum2d`` fp64 [S,S/2+1] the images' power is added to it, image 0 first."""
+    if power.dim() != 3 or power.shape[2] != power.shape[1] // 2 + 1:
+        raise RuntimeError("ps_profile: power must be [n,S,S/2+1], got %s" % (tuple(power.shape),))
+    n, S, W = power.shape
+    pp = _swd_typed("ps_profile", "power", power, torch.float32, (n, S, W))
+    if profiles is None:
+        profiles = torch.empty(n, ps_bins(S), dtype=torch.float64, device=power.device)
+    pr = _swd_typed("ps_profile", "profiles", profiles, torch.float64, (n, ps_bins(S)))
+    ps = None if sum2d is None else _swd_typed("ps_profile", "sum2d", sum2d, torch.float64, (S, W))
+    check(lib().bg_ps_profile(pp, n, S, pr, ps, stream()))
+    return profiles
+
+
 def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
     the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns

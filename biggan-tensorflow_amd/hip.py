@@ -300,6 +300,9 @@ SIGNATURES = {
     "bg_msssim_finish": (c_int, [_P, c_size_t, c_int, c_int, c_int, _P, c_int64, c_int64, _P]),
     "bg_sv_workspace_bytes": (c_size_t, [c_int, c_int]),
     "bg_sv_batch": (c_int, [_P, c_int, c_int, _P, c_size_t, _P]),
+    "bg_ps_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "bg_ps_power": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "bg_ps_profile": (c_int, [_P, c_int, c_int, _P, _P, _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

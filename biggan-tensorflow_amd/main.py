@@ -83,10 +83,19 @@ FLAGS = [
 #   --sv_iters T            iterations per round of the block power iteration (at most 8 rounds per event)
 #   --sv_tol R              rounds stop once every reported residual is <= R: some true sigma^2 then lies within
 #                           R sigma_0^2 of each reported value squared
+#   --ps_freq N             every N iterations: the radial power spectrum of --ps_images generated images against the real
+#                           set's (metrics.py, csrc/powerspec.hip): scalars ps_dist (decades between the log profiles),
+#                           ps_hf (above 0: excess fine structure, below 0: blur), ps_peak / ps_peak_at (height and
+#                           frequency in cycles per pixel of the largest spike: what a transposed or sub-pixel
+#                           up-convolution leaves at the Nyquist frequencies) in the event file and one "PS: ..." line,
+#                           the _noema forms as --sample_ema says; 0 (default) is off.  --phase test: computed once,
+#                           ps.txt (one row per radius) and ps.png (the mean 2-D spectra, real beside fake) are written
+#   --ps_images M           generated (and real) images per event
 EXTRA_FLAGS = [("precision", T, None), ("swd_freq", I, 0), ("swd_images", I, 2048),
                ("nn_freq", I, 0), ("nn_k", I, 3), ("nn_size", I, 64), ("nn_images", I, 0),
                ("msssim_freq", I, 0), ("msssim_pairs", I, 1024),
-               ("sv_freq", I, 0), ("sv_k", I, 3), ("sv_iters", I, 8), ("sv_tol", F, 1e-2)]
+               ("sv_freq", I, 0), ("sv_k", I, 3), ("sv_iters", I, 8), ("sv_tol", F, 1e-2),
+               ("ps_freq", I, 0), ("ps_images", I, 1024)]
 
 
 def build_parser():

@@ -11,7 +11,15 @@ consecutive events differ by the weights alone.
 In-training diversity score: the mean multi-scale structural similarity (MS-SSIM; Wang, Simoncelli and Bovik 2003) of
 pairs of generated images that share a class vector (Odena et al. 2017), as ``msssim`` (lower is more diverse, 1.0 is
 collapse).  ``MsssimPlan`` / ``Msssim`` follow the same split and the same rules for draws; csrc/msssim.hip holds the
-kernels; tests/msssim_ref.py restates the metric in float64."""
+kernels; tests/msssim_ref.py restates the metric in float64.
+
+In-training frequency check: the azimuthally averaged power spectrum of real and generated images (Durall et al. 2020,
+"Watch your Up-Convolution"), as ``ps_dist`` / ``ps_hf`` / ``ps_peak`` / ``ps_peak_at``: grid artefacts of an up-sampling
+route are spikes at the axis and corner Nyquist frequencies, blur is a deficit of the high bins.  ``PowerSpectrumPlan`` /
+``PowerSpectrum`` follow the same split and the same rules for draws; csrc/powerspec.hip holds the kernels;
+tests/ps_ref.py restates the metric in float64."""
+import math
+
 import numpy as np
 import torch
 
@@ -332,6 +340,213 @@ class Msssim:
         for v in per_pair:
             total += float(v)
         return total / self._n
+
+
+# ---- in-training frequency check: radial power spectrum of real and generated images (csrc/powerspec.hip) ----
+PS_SIDES = (16, 32, 64, 128, 256, 512)
+PS_FLOOR = 1e-30                      # log10 is taken of max(mean profile, PS_FLOOR)
+PS_DECADES = 8.0                      # range of ps.png below the real set's largest non-DC value
+
+
+def ps_bins(S):
+    """NB(S) = (isqrt(2 S^2) + 1) // 2 + 1: the bins run to the corner (S/2, S/2): 12 / 24 / 46 / 92 / 182 / 363."""
+    return (math.isqrt(2 * int(S) * int(S)) + 1) // 2 + 1
+
+
+def ps_bin_table(S):
+    """int64 [S, S/2 + 1]: the bin r = (isqrt(4 (ky^2 + kx^2)) + 1) // 2 of every coefficient of the half plane, rows in
+    DFT order (ky = 0 .. S/2 - 1, -S/2 .. -1), in integers."""
+    S = int(S)
+    ky = np.arange(S, dtype=np.int64)
+    ky = np.where(ky < S // 2, ky, ky - S)
+    m4 = 4 * (ky[:, None] ** 2 + np.arange(S // 2 + 1, dtype=np.int64)[None, :] ** 2)
+    root = np.array([math.isqrt(int(v)) for v in m4.reshape(-1)], dtype=np.int64).reshape(m4.shape)
+    return (root + 1) // 2
+
+
+def ps_counts(S):
+    """int64 [NB]: coefficients of the FULL plane per bin: columns 0 < kx < S/2 of the half plane count twice."""
+    S = int(S)
+    w = np.full(S // 2 + 1, 2, dtype=np.int64)
+    w[0] = w[-1] = 1
+    return np.bincount(ps_bin_table(S).reshape(-1), weights=np.tile(w, S), minlength=ps_bins(S)).astype(np.int64)
+
+
+class PowerSpectrumPlan:
+    """What one run of the frequency check needs, from the flags alone.
+
+    side, n_bins  S = --img_size, a power of two from 16 to 512; NB(S) radial bins, ``counts`` coefficients each
+    n_images      --ps_images generated images per event; ``n_real`` real ones, once: the first n_images files of the
+                  listing (all of them when the dataset has fewer), or n_images images of uniform noise without a dataset
+    seeds         one per draw, derived from --static_sample_seed; none is shared with the other monitors"""
+
+    def __init__(self, img_size, c_dim, batch_size, ps_images, static_sample_seed, n_files=None):
+        if c_dim not in (1, 3, 4):
+            raise ValueError("ps: c_dim %d (1, 3 or 4)" % c_dim)
+        if int(img_size) not in PS_SIDES:
+            raise ValueError("ps: --img_size %d: the transform takes a power of two from 16 to 512" % int(img_size))
+        self.side = self.img_size = int(img_size)
+        self.c_dim, self.batch_size = int(c_dim), int(batch_size)
+        self.n_images = int(ps_images)
+        if self.n_images < 1:
+            raise ValueError("ps: no images to measure (%d)" % self.n_images)
+        self.from_files = n_files is not None
+        self.n_real = self.n_images if n_files is None else min(self.n_images, int(n_files))
+        if self.n_real < 1:
+            raise ValueError("ps: the dataset has no files")
+        self.n_bins = ps_bins(self.side)
+        self.counts = ps_counts(self.side)
+        self.first_hf = self.side // 4                                 # ps_hf / ps_peak read the bins r >= S/4
+        base = int(static_sample_seed)
+        self.seeds = {name: (base + 32452843 * (i + 1)) % (1 << 32) for i, name in enumerate(("latents", "labels", "real"))}
+
+    # ---- sizes in bytes -------------------------------------------------------------------------
+    @property
+    def plane(self):
+        return self.side * (self.side // 2 + 1)
+
+    @property
+    def workspace_bytes(self):
+        """Twiddle table and row transforms of one generator batch (what bg_ps_workspace_bytes returns)."""
+        return 4096 + self.batch_size * self.plane * 8
+
+    @property
+    def power_bytes(self):
+        return self.batch_size * self.plane * 4
+
+    @property
+    def kept_bytes(self):
+        """What a set leaves behind: fp64 profiles of every image and one fp64 2-D sum."""
+        return self.n_images * self.n_bins * 8 + self.plane * 8
+
+    @property
+    def peak_bytes(self):
+        return self.workspace_bytes + self.power_bytes + self.kept_bytes
+
+    # ---- draws -------------------------------------------------------------------------------------
+    def draw_latents(self, z_dim, trunc):
+        """fp32 [n_images, 1, 1, z_dim] (sampling.draw_z) from a torch generator of the metric's own."""
+        g = torch.Generator(device="cpu")
+        g.manual_seed(self.seeds["latents"])
+        return Sp.draw_z(self.n_images, z_dim, g, trunc)
+
+    def draw_labels(self, label_table):
+        """fp32 [n_images, n_labels]: rows of the label table, drawn with replacement."""
+        return Sp.draw_n_tags(label_table, self.n_images, np.random.RandomState(self.seeds["labels"]))
+
+
+class PowerSpectrum:
+    """A plan on the device.  ``begin`` / ``add`` / ``finish``: images arrive a batch at a time; per batch one power buffer
+    and one workspace exist, what stays is the fp64 profile of every image and the fp64 2-D sum.  ``finish`` returns
+    {"profile": the fp64 mean profile [NB], "sum2d": the summed power [S, S/2 + 1], "n": images}.  ``ops``: the launch
+    wrappers (functional.py)."""
+
+    def __init__(self, plan, device, ops=None):
+        self.plan, self.device = plan, torch.device(device)
+        self.ops = Fn if ops is None else ops
+        self.fake_inputs = None                # (latents, class vectors or None), drawn once by the model
+        self.real = None                       # what ``finish`` returned for the real set, computed at the first event
+
+    def begin(self, n_images=None):
+        p = self.plan
+        self._n = p.n_images if n_images is None else int(n_images)
+        self._profiles = torch.zeros(self._n, p.n_bins, dtype=torch.float64, device=self.device)
+        self._sum2d = torch.zeros(p.side, p.side // 2 + 1, dtype=torch.float64, device=self.device)
+        self._filled = 0
+
+    def add(self, img):
+        """Images [b, S, S, C] (fp32 or bf16); those past n_images (the padding of a last generator batch) are dropped."""
+        p = self.plan
+        b = min(int(img.shape[0]), self._n - self._filled)
+        if b <= 0:
+            return
+        g = img[:b]
+        if tuple(g.shape[1:]) != (p.side, p.side, p.c_dim):
+            raise ValueError("ps: images of %s, the plan is for %s" % (tuple(g.shape[1:]), (p.side, p.side, p.c_dim)))
+        power = self.ops.ps_power(g)
+        self.ops.ps_profile(power, self._profiles[self._filled:self._filled + b], self._sum2d)
+        self._filled += b
+
+    def finish(self):
+        if self._filled != self._n:
+            raise RuntimeError("ps: %d of %d images arrived" % (self._filled, self._n))
+        rows = self._profiles.cpu().numpy()
+        total = np.zeros(self.plan.n_bins, dtype=np.float64)
+        for row in rows:                                   # the fp64 mean over images, added in image order
+            total += row
+        out = {"profile": total / self._n, "sum2d": self._sum2d.cpu().numpy(), "n": self._n}
+        self._profiles = self._sum2d = None
+        return out
+
+    # ---- host tail ---------------------------------------------------------------------------------
+    @staticmethod
+    def log_profile(profile):
+        return np.log10(np.maximum(np.asarray(profile, dtype=np.float64), PS_FLOOR))
+
+    def scores(self, real, fake, prefix="ps"):
+        """D = L_fake - L_real over the bins: ``_dist`` sqrt(mean D^2) over r >= 1 (decades), ``_hf`` mean D over
+        r >= S/4 (above 0: excess fine structure, below 0: blur), ``_peak`` max D over r >= S/4 and ``_peak_at`` its
+        r / S (cycles per pixel).  DC (bin 0) is not read."""
+        S, lo = self.plan.side, self.plan.first_hf
+        D = self.log_profile(fake["profile"]) - self.log_profile(real["profile"])
+        at = lo + int(np.argmax(D[lo:]))
+        return {prefix + "_dist": float(np.sqrt(np.mean(D[1:] ** 2))), prefix + "_hf": float(np.mean(D[lo:])),
+                prefix + "_peak": float(D[at]), prefix + "_peak_at": at / float(S)}
+
+    def table(self, real, fakes):
+        """Rows of ps.txt, one per radius: r, r / S, n_r, L_real, L_<name> of every fake set in ``fakes`` (a dict, in
+        order), then D of each.  Returns (header, rows)."""
+        S = self.plan.side
+        Lr = self.log_profile(real["profile"])
+        Lf = {k: self.log_profile(v["profile"]) for k, v in fakes.items()}
+        header = ["r", "r/S", "n_r", "L_real"] + ["L_" + k for k in Lf] + ["D_" + k for k in Lf]
+        rows = []
+        for r in range(self.plan.n_bins):
+            rows.append([r, r / float(S), int(self.plan.counts[r]), Lr[r]] + [L[r] for L in Lf.values()] +
+                        [L[r] - Lr[r] for L in Lf.values()])
+        return header, rows
+
+    @staticmethod
+    def full_plane(sum2d):
+        """fp64 [S, S/2 + 1] -> [S, S] with DC at (S/2, S/2): column kx < 0 of row ky is column -kx of row -ky."""
+        h = np.asarray(sum2d, dtype=np.float64)
+        S = h.shape[0]
+        full = np.empty((S, S), dtype=np.float64)
+        full[:, :S // 2 + 1] = h
+        neg = (-np.arange(S)) % S
+        for kx in range(S // 2 + 1, S):
+            full[:, kx] = h[neg, S - kx]
+        return np.fft.fftshift(full)
+
+    def image(self, real, fake):
+        """uint8 [S, 2 S]: the mean 2-D spectra of the real and the fake set side by side, log10, the 8 decades below
+        the real set's largest non-DC value scaled to 0..255."""
+        S = self.plan.side
+        planes = [self.full_plane(x["sum2d"]) / float(x["n"]) for x in (real, fake)]
+        ref = planes[0].copy()
+        ref[S // 2, S // 2] = 0.0
+        top = math.log10(max(float(ref.max()), PS_FLOOR))
+        out = []
+        for pl in planes:
+            L = np.log10(np.maximum(pl, PS_FLOOR))
+            out.append(np.clip((L - (top - PS_DECADES)) / PS_DECADES, 0.0, 1.0))
+        return np.round(np.concatenate(out, axis=1) * 255.0).astype(np.uint8)
+
+
+    def save(self, folder, real, sets):
+        """``ps.txt`` and ``ps.png`` in ``folder``; ``sets``: {"ps": the fake set, "ps_noema": the live weights' set}, one
+        or both.  The image shows the moving averages' set when there is one.  Returns the two paths."""
+        import os
+        from .utils import write_png
+        names = {"ps": "fake", "ps_noema": "fake_noema"}
+        header, rows = self.table(real, {names[k]: v for k, v in sets.items()})
+        txt, png = os.path.join(folder, "ps.txt"), os.path.join(folder, "ps.png")
+        with open(txt, "w") as f:
+            f.write("# " + "\t".join(header) + "\n")
+            for row in rows:
+                f.write("\t".join(["%d" % row[0], "%.6f" % row[1], "%d" % row[2]] + ["%.6f" % v for v in row[3:]]) + "\n")
+        write_png(self.image(real, sets["ps"] if "ps" in sets else sets["ps_noema"]), png)
+        return [txt, png]
 
 
 def format_scores(scores):

@@ -187,6 +187,10 @@ class BigGAN(GANBase):
         self.msssim_freq = int(getattr(args, "msssim_freq", 0) or 0)
         self.msssim_pairs = int(getattr(args, "msssim_pairs", 1024) or 1024)
         self._msssim = None                    # metrics.Msssim with the draws of the run, built at the first event
+        # in-training frequency check (extension flags --ps_freq / --ps_images; metrics.py)
+        self.ps_freq = int(getattr(args, "ps_freq", 0) or 0)
+        self.ps_images = int(getattr(args, "ps_images", 1024) or 1024)
+        self._ps = None                        # metrics.PowerSpectrum with the real set's profile and the draws of the run
         # singular-value monitor (extension flags --sv_freq / --sv_k / --sv_iters / --sv_tol; spectrum.py)
         self.sv_freq = int(getattr(args, "sv_freq", 0) or 0)
         self.sv_k = int(getattr(args, "sv_k", 3))
@@ -1600,6 +1604,13 @@ class BigGAN(GANBase):
                     print(line, flush=True)
                     if self._log_writer is not None:
                         self._log_writer.add_scalars(self.counter - 1, values)
+                if self.ps_freq > 0 and self.counter % self.ps_freq == 0:
+                    scores = self.power_spectrum()                                     # (collective: every rank enters)
+                    if self.rank == 0:
+                        from .metrics import format_scores
+                        print("PS: " + format_scores(scores), flush=True)
+                        if self._log_writer is not None:
+                            self._log_writer.add_scalars(self.counter - 1, scores)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
             if self._log_writer is not None:
@@ -2022,6 +2033,79 @@ class BigGAN(GANBase):
         values, top = spectrum.scalars(result, self.sv_k, sigma_of)
         return values, spectrum.format_line(result, top), result
 
+    # ---- in-training frequency check (metrics.py) --------------------------------------------------
+    def ps_plan(self, root="./dataset"):
+        from .metrics import PowerSpectrumPlan
+        files = self._swd_files(root)
+        return PowerSpectrumPlan(self.img_size, self.c_dim, self.batch_size, self.ps_images, self.static_sample_seed,
+                                 n_files=None if files is None else len(files))
+
+    def ps_fake_inputs(self, plan):
+        """(latents [n,1,1,z_dim], class vectors [n,n_labels] or None), with --z_trunc_train's truncation: the same at
+        every event."""
+        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
+        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
+
+    def ps_real_batches(self, plan, root="./dataset"):
+        """The real set, at most ``batch_size`` images at a time on the device: with a dataset folder the first
+        ``plan.n_real`` files of the listing, decoded and resized by the host path without flips (never taken from the
+        training loader); without one, uniform noise from a generator of the metric's own."""
+        B, M = self.batch_size, plan.n_real
+        if plan.from_files:
+            import numpy as np
+            from . import data as D
+            image_data = D.ImageData(self.img_size, self.c_dim, True, False)
+            files = self._swd_files(root)[:M]
+            for lo in range(0, M, B):
+                yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in files[lo:lo + B]])).to(self.device)
+        else:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(plan.seeds["real"])
+            for lo in range(0, M, B):
+                yield torch.rand(min(B, M - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
+                                 generator=gen) * 2.0 - 1.0
+
+    def power_spectrum(self, root="./dataset", details=False):
+        """The frequency check of the current weights: the radial power spectrum of --ps_images generated images against
+        the real set's, as ``ps_dist`` (decades), ``ps_hf`` (above 0: excess fine structure, below 0: blur), ``ps_peak``
+        and ``ps_peak_at`` (cycles per pixel) for the moving averages and / or the ``_noema`` forms for the live weights,
+        as --sample_ema says.  The real set is measured at the first call; only its profile and 2-D sum are kept.  The
+        fakes are regenerated through ``generate`` a batch at a time from latents and class vectors drawn once.  Every
+        rank calls it (``sync_sharded_state`` is collective); rank 0 computes, the others return {}.  Nothing the
+        training run reads is changed.  ``details``: return (scores, the runner, {tag: what ``finish`` returned})."""
+        from . import metrics
+        self.sync_sharded_state()
+        if self.rank != 0:
+            return ({}, None, {}) if details else {}
+        with torch.no_grad():
+            out, sets = {}, {}
+            if self._ps is None:
+                plan = self.ps_plan(root)
+                m = metrics.PowerSpectrum(plan, self.device)
+                m.begin(plan.n_real)
+                for batch in self.ps_real_batches(plan, root):
+                    m.add(batch)
+                m.real = m.finish()
+                m.fake_inputs = self.ps_fake_inputs(plan)
+                self._ps = m
+            m = self._ps
+            for name, ema, wanted in (("ps", True, self.generate_ema_samples), ("ps_noema", False, self.generate_noema_samples)):
+                if wanted:
+                    m.begin()
+                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
+                    sets[name] = m.finish()
+                    for k, v in m.scores(m.real, sets[name]).items():
+                        out[k + name[2:]] = v                              # ps_dist / ps_dist_noema
+        return (out, m, sets) if details else out
+
+    def save_power_spectrum(self, folder, root="./dataset"):
+        """--phase test: ``ps.txt`` (one row per radius: r, r/S, n_r, L_real, L_fake (and L_fake_noema), D) and ``ps.png``
+        (the mean 2-D spectra of the real and the fake set side by side, log10 over 8 decades) in ``folder``."""
+        scores, m, sets = self.power_spectrum(root, details=True)
+        if self.rank != 0:
+            return scores, []
+        return scores, m.save(folder, m.real, sets)
+
     # ---- nearest training images (neighbours.py) -------------------------------------------------
     def nn_plan(self, root="./dataset"):
         from .neighbours import NnPlan
@@ -2139,7 +2223,8 @@ class BigGAN(GANBase):
         checkpoint's quality scores are printed and written to ``swd.txt`` beside them; with --nn_freq > 0 the nearest
         training images of its static samples go to ``nn.png`` / ``nn.txt`` (``nn_noema.*``); with --msssim_freq > 0 its
         diversity scores are printed and written to ``msssim.txt``; with --sv_freq > 0 ``sv.txt`` gets one row per monitored
-        weight: name, rows, cols, the --sv_k singular values and their residuals."""
+        weight: name, rows, cols, the --sv_k singular values and their residuals; with --ps_freq > 0 the radial power
+        spectra go to ``ps.txt`` and the mean 2-D spectra to ``ps.png``."""
         import numpy as np
         from .utils import save_images, check_folder
         could_load, _ = self.load(self.checkpoint_dir)
@@ -2172,6 +2257,12 @@ class BigGAN(GANBase):
                 with open(os.path.join(result_dir, "msssim.txt"), "w") as f:
                     for k, v in scores.items():
                         f.write("%s\t%.6f\n" % (k, v))
+        if self.ps_freq > 0:
+            from .metrics import format_scores
+            scores, written = self.save_power_spectrum(result_dir)
+            if self.rank == 0:
+                print("PS: " + format_scores(scores), flush=True)
+                paths += [p for p in written if p.endswith(".png")]
         if self.sv_freq > 0 and self.rank == 0:
             _, line, result = self.singular_values()
             print(line, flush=True)

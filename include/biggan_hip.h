@@ -1144,6 +1144,29 @@ size_t bg_sv_workspace_bytes(int rows, int cols);
 int    bg_sv_batch(const BgSvItem* items_dev, int n_items, int iters, void* ws, size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Radial power spectrum of image sets (Durall et al. 2020; csrc/powerspec.hip, metrics.py; an addition to ABI 10: new
+ * symbols only).  NHWC images in [-1, 1], contiguous, side S a power of two from 16 to 512, C in {1, 3, 4}: C = 1 is used as
+ * it is, C = 3 and 4 go through Y = 0.299 R + 0.587 G + 0.114 B (alpha is ignored).  F = DFT2(Y), unnormalised, and
+ * P = |F|^2 / S^4, so that the sum of P over the full plane is mean(Y^2); no window, no mean subtraction.  Only the columns
+ * kx = 0 .. S/2 are kept; 0 < kx < S/2 stand for their mirror images as well.  The transforms are fp32 radix-4 / radix-2
+ * passes in LDS with twiddles rounded once from fp64; two real rows share one complex transform.  Every launcher is
+ * stream-ordered and allocates nothing; there are no atomics, so a repeated launch is bit-identical.  BG_ERR_ARG with a
+ * message for a NULL pointer, a bad dtype, side, channel count or image count, a short workspace, a misaligned buffer.
+ *
+ * bg_ps_workspace_bytes: bytes of the workspace of n images of side S (0 for sizes that the launches reject): the
+ *   twiddle table and the row transforms, fp32 complex [n, S, S/2 + 1]; 8-byte aligned.
+ * bg_ps_power: power fp32 [n, S, S/2 + 1] = P; row ky in DFT order (0 .. S/2 - 1, then -S/2 .. -1), unshifted.  x is
+ *   BG_F32 or BG_BF16 [n, S, S, C].
+ * bg_ps_profile: profiles fp64 [n, NB], NB = (isqrt(2 S^2) + 1) / 2 + 1 (12 / 24 / 46 / 92 / 182 / 363 for S = 16 .. 512):
+ *   the mean of P over the coefficients of the full plane whose radius rounds to r, r = (isqrt(4 (ky^2 + kx^2)) + 1) / 2
+ *   with signed frequencies, in integers; bin 0 is DC, bin NB - 1 holds the corner (S/2, S/2).  With sum2d, fp64
+ *   [S, S/2 + 1], P of image 0, then image 1, ... is added to what sum2d holds; sum2d may be NULL.
+ * ------------------------------------------------------------------------------------------ */
+size_t bg_ps_workspace_bytes(int n, int S);
+int    bg_ps_power(const void* x, int dtype, int n, int S, int C, float* power, void* ws, size_t ws_bytes, void* stream);
+int    bg_ps_profile(const float* power, int n, int S, double* profiles, double* sum2d, void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
  * (conv / deconv / gemm families) is bracketed by hipEvents on its stream.
  * bg_prof_collect synchronises the events and returns totals since the last reset.
