@@ -445,6 +445,56 @@ def ps_profile(power, profiles=None, sum2d=None):
     return profiles
 
 
+# ---- precision / recall / density / coverage of descriptor sets (csrc/prdc.hip; metrics.py drives them).  No autograd. ----
+def _prdc_rows(op, name, t):
+    if t.dim() != 2:
+        raise RuntimeError("%s: %s must be bf16 [rows, D], got %s" % (op, name, tuple(t.shape)))
+    return _swd_typed(op, name, t, BF16, tuple(t.shape))
+
+
+def prdc_radii(x, k, out=None):
+    """x bf16 [N,D] -> fp32 [N]: the k-th smallest squared distance (1 <= k <= 8) of every row to the other rows; the row
+    itself is left out by index, an equal row elsewhere counts."""
+    px = _prdc_rows("prdc_radii", "x", x)
+    N, D = x.shape
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=x.device)
+    po = _swd_typed("prdc_radii", "out", out, torch.float32, (N,))
+    check(lib().bg_prdc_radii(px, N, D, int(k), po, stream()))
+    return out
+
+
+def prdc_cover(q, radius_q, set_, count=True, dmin=True):
+    """q bf16 [Q,D] with radius_q fp32 [Q] against set_ bf16 [N,D] -> (count int32 [N], dmin fp32 [N]): how many queries
+    hold row n within their radius (<=), and the squared distance of the nearest query.  ``count`` / ``dmin``: True
+    (allocated here), a tensor to fill, or None / False (not computed; its place in the result is None)."""
+    pq, ps = _prdc_rows("prdc_cover", "q", q), _prdc_rows("prdc_cover", "set", set_)
+    if q.shape[1] != set_.shape[1]:
+        raise RuntimeError("prdc_cover: q [Q,D] and set [N,D], got %s and %s" % (tuple(q.shape), tuple(set_.shape)))
+    (Q, D), N = q.shape, set_.shape[0]
+    count = torch.empty(N, dtype=torch.int32, device=q.device) if count is True else (None if count is False else count)
+    dmin = torch.empty(N, dtype=torch.float32, device=q.device) if dmin is True else (None if dmin is False else dmin)
+    pr = None if radius_q is None else _swd_typed("prdc_cover", "radius_q", radius_q, torch.float32, (Q,))
+    pc = None if count is None else _swd_typed("prdc_cover", "count", count, torch.int32, (N,))
+    pm = None if dmin is None else _swd_typed("prdc_cover", "dmin", dmin, torch.float32, (N,))
+    check(lib().bg_prdc_cover(pq, pr, Q, ps, N, D, pc, pm, stream()))
+    return count, dmin
+
+
+def prdc_reduce(count_f, count_r, dmin_r, radius_r, out=None):
+    """int64 [4] on the device: (#{count_f > 0}, sum count_f, #{count_r > 0}, #{dmin_r <= radius_r})."""
+    M, N = int(count_f.numel()), int(count_r.numel())
+    pf = _swd_typed("prdc_reduce", "count_f", count_f, torch.int32, (M,))
+    pc = _swd_typed("prdc_reduce", "count_r", count_r, torch.int32, (N,))
+    pm = _swd_typed("prdc_reduce", "dmin_r", dmin_r, torch.float32, (N,))
+    pr = _swd_typed("prdc_reduce", "radius_r", radius_r, torch.float32, (N,))
+    if out is None:
+        out = torch.empty(4, dtype=torch.int64, device=count_f.device)
+    po = _swd_typed("prdc_reduce", "out", out, torch.int64, (4,))
+    check(lib().bg_prdc_reduce(pf, M, pc, pm, pr, N, po, stream()))
+    return out
+
+
 def image_batch_u8(raw, table, n, size, channels, raw_bytes=None, out=None):
     """The decoded pixels of n images (data.pack_batch: raw uint8 [bytes], table int32 [n,8], both on the device) ->
     the training batch [n,size,size,channels] fp32 in [-1,1]: TF1 legacy-bilinear resize, flip of the output columns

@@ -303,6 +303,9 @@ SIGNATURES = {
     "bg_ps_workspace_bytes": (c_size_t, [c_int, c_int]),
     "bg_ps_power": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "bg_ps_profile": (c_int, [_P, c_int, c_int, _P, _P, _P]),
+    "bg_prdc_radii": (c_int, [_P, c_int64, c_int, c_int, _P, _P]),
+    "bg_prdc_cover": (c_int, [_P, _P, c_int64, _P, c_int64, c_int, _P, _P, _P]),
+    "bg_prdc_reduce": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, _P]),
     "bg_prof_enable": (None, [c_int]),
     "bg_prof_reset": (None, []),
     "bg_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),

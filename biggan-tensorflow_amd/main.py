@@ -91,11 +91,21 @@ FLAGS = [
 #                           the _noema forms as --sample_ema says; 0 (default) is off.  --phase test: computed once,
 #                           ps.txt (one row per radius) and ps.png (the mean 2-D spectra, real beside fake) are written
 #   --ps_images M           generated (and real) images per event
+#   --pr_freq N             every N iterations: improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage
+#                           (Naeem et al. 2020) of --pr_images generated images against as many real ones, in the
+#                           box-filtered pixel descriptors of the memorisation check (metrics.py, csrc/prdc.hip): scalars
+#                           pr_precision, pr_density (samples off the data manifold lower them) and pr_recall, pr_coverage
+#                           (dropped modes lower them) in the event file and one "PRDC: ..." line, the _noema forms as
+#                           --sample_ema says; 0 (default) is off.  --phase test: computed once, prdc.txt is written
+#   --pr_images M           generated images per event, and real ones (at most the number of dataset files); > --pr_k
+#   --pr_k K                the neighbour whose distance is a row's radius, 1..8
+#   --pr_size S             side of the descriptors, a power of two >= 8; min(img_size, S) is used
 EXTRA_FLAGS = [("precision", T, None), ("swd_freq", I, 0), ("swd_images", I, 2048),
                ("nn_freq", I, 0), ("nn_k", I, 3), ("nn_size", I, 64), ("nn_images", I, 0),
                ("msssim_freq", I, 0), ("msssim_pairs", I, 1024),
                ("sv_freq", I, 0), ("sv_k", I, 3), ("sv_iters", I, 8), ("sv_tol", F, 1e-2),
-               ("ps_freq", I, 0), ("ps_images", I, 1024)]
+               ("ps_freq", I, 0), ("ps_images", I, 1024),
+               ("pr_freq", I, 0), ("pr_images", I, 4096), ("pr_k", I, 3), ("pr_size", I, 64)]
 
 
 def build_parser():

@@ -17,7 +17,13 @@ In-training frequency check: the azimuthally averaged power spectrum of real and
 "Watch your Up-Convolution"), as ``ps_dist`` / ``ps_hf`` / ``ps_peak`` / ``ps_peak_at``: grid artefacts of an up-sampling
 route are spikes at the axis and corner Nyquist frequencies, blur is a deficit of the high bins.  ``PowerSpectrumPlan`` /
 ``PowerSpectrum`` follow the same split and the same rules for draws; csrc/powerspec.hip holds the kernels;
-tests/ps_ref.py restates the metric in float64."""
+tests/ps_ref.py restates the metric in float64.
+
+In-training fidelity / coverage split: improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage
+(Naeem et al. 2020) of the generated set against the real set in the box-filtered pixel descriptors of the memorisation
+check, as ``pr_precision`` / ``pr_recall`` / ``pr_density`` / ``pr_coverage``: samples off the data manifold lower the
+first and third, dropped modes the second and fourth.  ``PrdcPlan`` / ``Prdc`` follow the same split and the same rules
+for draws; csrc/prdc.hip holds the kernels; tests/prdc_ref.py restates the metric in float64."""
 import math
 
 import numpy as np
@@ -547,6 +553,132 @@ class PowerSpectrum:
                 f.write("\t".join(["%d" % row[0], "%.6f" % row[1], "%d" % row[2]] + ["%.6f" % v for v in row[3:]]) + "\n")
         write_png(self.image(real, sets["ps"] if "ps" in sets else sets["ps_noema"]), png)
         return [txt, png]
+
+
+# ---- in-training precision / recall / density / coverage (csrc/prdc.hip) ----
+PR_MAX_K = 8
+
+
+def check_pr_k(k):
+    k = int(k)
+    if k < 1 or k > PR_MAX_K:
+        raise ValueError("prdc: --pr_k %d (1..%d)" % (k, PR_MAX_K))
+    return k
+
+
+class PrdcPlan:
+    """What one run of the precision / recall / density / coverage check needs, from the flags alone.
+
+    side, f, D    descriptors are side x side x c_dim (neighbours.search_side(img_size, --pr_size)), each value the mean of
+                  an f x f box; D = side * side * c_dim values per image, a multiple of 64
+    k             the neighbour whose distance is a row's radius (--pr_k, 1..8)
+    N, M          real and generated images per event: --pr_images both, N capped by the number of dataset files; the real
+                  ones are the first N files of the listing, or N images of uniform noise without a dataset
+    seeds         one per draw, derived from --static_sample_seed; none is shared with the other monitors"""
+
+    def __init__(self, img_size, c_dim, batch_size, pr_images=4096, pr_k=3, pr_size=64, static_sample_seed=0, n_files=None):
+        from .neighbours import search_side
+        if c_dim not in (1, 3, 4):
+            raise ValueError("prdc: c_dim %d (1, 3 or 4)" % c_dim)
+        self.k = check_pr_k(pr_k)
+        self.side = search_side(img_size, pr_size)
+        self.img_size, self.c_dim, self.batch_size = int(img_size), int(c_dim), int(batch_size)
+        self.f = self.img_size // self.side
+        self.D = self.side * self.side * self.c_dim
+        self.M = self.n_images = int(pr_images)
+        if self.M <= self.k:
+            raise ValueError("prdc: --pr_images %d: more than --pr_k %d images are needed" % (self.M, self.k))
+        self.from_files = n_files is not None
+        self.N = self.n_real = self.M if n_files is None else min(self.M, int(n_files))
+        if self.N <= self.k:
+            raise ValueError("prdc: the dataset has %d files, more than --pr_k %d are needed" % (self.N, self.k))
+        base = int(static_sample_seed)
+        self.seeds = {name: (base + 49979687 * (i + 1)) % (1 << 32) for i, name in enumerate(("latents", "labels", "real"))}
+
+    # ---- sizes in bytes -------------------------------------------------------------------------
+    @property
+    def set_bytes(self):
+        """One resident descriptor set of the larger of the two sizes."""
+        return max(self.N, self.M) * self.D * 2
+
+    @property
+    def vector_bytes(self):
+        """Per set its radii; per event a count per row of either set and the real rows' nearest distance; the four
+        integers."""
+        return 4 * (self.N + self.M) + 4 * (self.N + self.M) + 4 * self.N + 32
+
+    @property
+    def peak_bytes(self):
+        return self.N * self.D * 2 + self.M * self.D * 2 + self.vector_bytes
+
+    # ---- draws -------------------------------------------------------------------------------------
+    def draw_latents(self, z_dim, trunc):
+        """fp32 [M, 1, 1, z_dim] (sampling.draw_z) from a torch generator of the metric's own."""
+        g = torch.Generator(device="cpu")
+        g.manual_seed(self.seeds["latents"])
+        return Sp.draw_z(self.M, z_dim, g, trunc)
+
+    def draw_labels(self, label_table):
+        """fp32 [M, n_labels]: rows of the label table, drawn with replacement."""
+        return Sp.draw_n_tags(label_table, self.M, np.random.RandomState(self.seeds["labels"]))
+
+
+class Prdc:
+    """A plan on the device.  ``begin`` / ``add`` / ``finish``: images arrive a batch at a time and are packed
+    (bg_nn_pack) into the resident bf16 buffer [n, D]; ``finish`` measures the set's radii and returns
+    {"desc": bf16 [n, D], "radius": fp32 [n], "n": n}, both on the device.  ``scores`` takes two such sets.  ``ops``: the
+    launch wrappers (functional.py)."""
+
+    def __init__(self, plan, device, ops=None):
+        self.plan, self.device = plan, torch.device(device)
+        self.ops = Fn if ops is None else ops
+        self.fake_inputs = None                # (latents, class vectors or None), drawn once by the model
+        self.real = None                       # what ``finish`` returned for the real set, computed at the first event
+
+    def begin(self, n_images=None):
+        p = self.plan
+        self._n = p.M if n_images is None else int(n_images)
+        self._desc = torch.empty(self._n, p.D, dtype=torch.bfloat16, device=self.device)
+        self._filled = 0
+
+    def add(self, img):
+        """Images [b, S, S, C] (fp32 or bf16); those past n (the padding of a last generator batch) are dropped."""
+        p = self.plan
+        b = min(int(img.shape[0]), self._n - self._filled)
+        if b <= 0:
+            return
+        if tuple(img.shape[1:]) != (p.img_size, p.img_size, p.c_dim):
+            raise ValueError("prdc: images of %s, the plan is for %s" % (tuple(img.shape[1:]), (p.img_size, p.img_size, p.c_dim)))
+        self.ops.nn_pack(img[:b], p.f, False, out=self._desc[self._filled:self._filled + b])
+        self._filled += b
+
+    def finish(self):
+        if self._filled != self._n:
+            raise RuntimeError("prdc: %d of %d images arrived" % (self._filled, self._n))
+        out = {"desc": self._desc, "radius": self.ops.prdc_radii(self._desc, self.plan.k), "n": self._n}
+        self._desc = None
+        return out
+
+    def counts(self, real, fake):
+        """The event's three passes over two finished sets: (count_f int32 [M], count_r int32 [N], dmin_r fp32 [N], out4
+        int64 [4]), all on the device."""
+        count_f, _ = self.ops.prdc_cover(real["desc"], real["radius"], fake["desc"], dmin=None)
+        count_r, dmin_r = self.ops.prdc_cover(fake["desc"], fake["radius"], real["desc"])
+        return count_f, count_r, dmin_r, self.ops.prdc_reduce(count_f, count_r, dmin_r, real["radius"])
+
+    @staticmethod
+    def ratios(out4, k, N, M, prefix="pr"):
+        """The four scores in Python floats from the four integers."""
+        a = [int(v) for v in out4]
+        return {prefix + "_precision": a[0] / float(M), prefix + "_recall": a[2] / float(N),
+                prefix + "_density": a[1] / float(k * M), prefix + "_coverage": a[3] / float(N)}
+
+    def scores(self, real, fake, prefix="pr"):
+        """``_precision``: the share of fakes inside some real row's k-NN ball; ``_density``: the balls a fake lies in,
+        over k; ``_recall``: the share of reals inside some fake's ball; ``_coverage``: the share of reals whose nearest
+        fake is inside the real's own ball.  One 32-byte copy to the host."""
+        out4 = self.counts(real, fake)[3].cpu().tolist()
+        return self.ratios(out4, self.plan.k, real["n"], fake["n"], prefix)
 
 
 def format_scores(scores):

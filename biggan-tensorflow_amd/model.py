@@ -191,6 +191,13 @@ class BigGAN(GANBase):
         self.ps_freq = int(getattr(args, "ps_freq", 0) or 0)
         self.ps_images = int(getattr(args, "ps_images", 1024) or 1024)
         self._ps = None                        # metrics.PowerSpectrum with the real set's profile and the draws of the run
+        # in-training precision / recall / density / coverage (extension flags --pr_freq / --pr_images / --pr_k /
+        # --pr_size; metrics.py)
+        self.pr_freq = int(getattr(args, "pr_freq", 0) or 0)
+        self.pr_images = int(getattr(args, "pr_images", 4096))
+        self.pr_k = int(getattr(args, "pr_k", 3))
+        self.pr_size = int(getattr(args, "pr_size", 64))
+        self._prdc = None                      # metrics.Prdc with the real set, its radii and the draws of the run
         # singular-value monitor (extension flags --sv_freq / --sv_k / --sv_iters / --sv_tol; spectrum.py)
         self.sv_freq = int(getattr(args, "sv_freq", 0) or 0)
         self.sv_k = int(getattr(args, "sv_k", 3))
@@ -1611,6 +1618,13 @@ class BigGAN(GANBase):
                         print("PS: " + format_scores(scores), flush=True)
                         if self._log_writer is not None:
                             self._log_writer.add_scalars(self.counter - 1, scores)
+                if self.pr_freq > 0 and self.counter % self.pr_freq == 0:
+                    scores = self.prdc()                                               # (collective: every rank enters)
+                    if self.rank == 0:
+                        from .metrics import format_scores
+                        print("PRDC: " + format_scores(scores), flush=True)
+                        if self._log_writer is not None:
+                            self._log_writer.add_scalars(self.counter - 1, scores)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
             if self._log_writer is not None:
@@ -2106,6 +2120,85 @@ class BigGAN(GANBase):
             return scores, []
         return scores, m.save(folder, m.real, sets)
 
+    # ---- in-training precision / recall / density / coverage (metrics.py) ---------------------------
+    def prdc_plan(self, root="./dataset"):
+        from .metrics import PrdcPlan
+        files = self._swd_files(root)
+        return PrdcPlan(self.img_size, self.c_dim, self.batch_size, self.pr_images, self.pr_k, self.pr_size,
+                        self.static_sample_seed, n_files=None if files is None else len(files))
+
+    def prdc_fake_inputs(self, plan):
+        """(latents [M,1,1,z_dim], class vectors [M,n_labels] or None), with --z_trunc_train's truncation: the same at
+        every event."""
+        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
+        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
+
+    def prdc_real_batches(self, plan, root="./dataset"):
+        """The real set, at most ``batch_size`` images at a time on the device: with a dataset folder the first
+        ``plan.N`` files of the listing, decoded and resized by the host path without flips (never taken from the
+        training loader); without one, uniform noise from a generator of the metric's own."""
+        B, N = self.batch_size, plan.N
+        if plan.from_files:
+            import numpy as np
+            from . import data as D
+            image_data = D.ImageData(self.img_size, self.c_dim, True, False)
+            files = self._swd_files(root)[:N]
+            for lo in range(0, N, B):
+                yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in files[lo:lo + B]])).to(self.device)
+        else:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(plan.seeds["real"])
+            for lo in range(0, N, B):
+                yield torch.rand(min(B, N - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
+                                 generator=gen) * 2.0 - 1.0
+
+    def prdc(self, root="./dataset", details=False):
+        """Improved precision / recall and density / coverage of --pr_images generated images against the real set in the
+        box-filtered pixel descriptors, as ``pr_precision``, ``pr_recall``, ``pr_density``, ``pr_coverage`` for the moving
+        averages and / or the ``_noema`` forms for the live weights, as --sample_ema says.  The real descriptors and their
+        radii are computed at the first call and kept.  The fakes are regenerated through ``generate`` a batch at a time
+        from latents and class vectors drawn once; an event is the radii of the fake set, two cover passes and one
+        reduction, and reads 32 bytes back.  Every rank calls it (``sync_sharded_state`` is collective); rank 0 computes,
+        the others return {}.  Nothing the training run reads is changed.  ``details``: return (scores, the runner,
+        {tag: what ``finish`` returned})."""
+        from . import metrics
+        self.sync_sharded_state()
+        if self.rank != 0:
+            return ({}, None, {}) if details else {}
+        with torch.no_grad():
+            out, sets = {}, {}
+            if self._prdc is None:
+                plan = self.prdc_plan(root)
+                m = metrics.Prdc(plan, self.device)
+                m.begin(plan.N)
+                for batch in self.prdc_real_batches(plan, root):
+                    m.add(batch)
+                m.real = m.finish()
+                m.fake_inputs = self.prdc_fake_inputs(plan)
+                self._prdc = m
+            m = self._prdc
+            for name, ema, wanted in (("pr", True, self.generate_ema_samples), ("pr_noema", False, self.generate_noema_samples)):
+                if wanted:
+                    m.begin()
+                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
+                    sets[name] = m.finish()
+                    for k, v in m.scores(m.real, sets[name]).items():
+                        out[k + name[2:]] = v                              # pr_recall / pr_recall_noema
+        return (out, m, sets) if details else out
+
+    def save_prdc(self, folder, root="./dataset"):
+        """--phase test: ``prdc.txt`` in ``folder``: one "name<TAB>value" row per score, then k, N, M and D."""
+        scores, m, _ = self.prdc(root, details=True)
+        if self.rank != 0:
+            return scores, []
+        path = os.path.join(folder, "prdc.txt")
+        with open(path, "w") as f:
+            for k, v in scores.items():
+                f.write("%s\t%.6f\n" % (k, v))
+            for k, v in (("k", m.plan.k), ("N", m.plan.N), ("M", m.plan.M), ("D", m.plan.D)):
+                f.write("%s\t%d\n" % (k, v))
+        return scores, [path]
+
     # ---- nearest training images (neighbours.py) -------------------------------------------------
     def nn_plan(self, root="./dataset"):
         from .neighbours import NnPlan
@@ -2224,7 +2317,8 @@ class BigGAN(GANBase):
         training images of its static samples go to ``nn.png`` / ``nn.txt`` (``nn_noema.*``); with --msssim_freq > 0 its
         diversity scores are printed and written to ``msssim.txt``; with --sv_freq > 0 ``sv.txt`` gets one row per monitored
         weight: name, rows, cols, the --sv_k singular values and their residuals; with --ps_freq > 0 the radial power
-        spectra go to ``ps.txt`` and the mean 2-D spectra to ``ps.png``."""
+        spectra go to ``ps.txt`` and the mean 2-D spectra to ``ps.png``; with --pr_freq > 0 precision, recall, density and
+        coverage go to ``prdc.txt``."""
         import numpy as np
         from .utils import save_images, check_folder
         could_load, _ = self.load(self.checkpoint_dir)
@@ -2263,6 +2357,11 @@ class BigGAN(GANBase):
             if self.rank == 0:
                 print("PS: " + format_scores(scores), flush=True)
                 paths += [p for p in written if p.endswith(".png")]
+        if self.pr_freq > 0:
+            from .metrics import format_scores
+            scores, _ = self.save_prdc(result_dir)
+            if self.rank == 0:
+                print("PRDC: " + format_scores(scores), flush=True)
         if self.sv_freq > 0 and self.rank == 0:
             _, line, result = self.singular_values()
             print(line, flush=True)

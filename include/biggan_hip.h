@@ -1167,6 +1167,35 @@ int    bg_ps_power(const void* x, int dtype, int n, int S, int C, float* power, 
 int    bg_ps_profile(const float* power, int n, int S, double* profiles, double* sum2d, void* stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) of a generated set against a
+ * real set, on the bf16 search descriptors of bg_nn_pack (csrc/prdc.hip, metrics.py; an addition to ABI 10: new symbols
+ * only).  All on squared distances d(a, b) = sum_j (a_j - b_j)^2 over bf16 rows [., D], D a multiple of 64, rows 16-byte
+ * aligned: the arithmetic of bg_nn_distances (fp32 differences of exactly widened bf16, one fma per term, no
+ * |a|^2 + |b|^2 - 2 a.b expansion, no MFMA), so equal rows give 0.0f exactly and the relative error is at most
+ * (D + 2) u / (1 - (D + 2) u), u = 2^-24.  The order of summation depends on the element index alone: d(a, b) and d(b, a)
+ * are the same bits, and the radii and the membership tests come from one function.  The [Q, N] matrix is never written: a
+ * block owns 16 set rows, walks all queries and keeps per row what is asked for.  Every launcher is stream-ordered and
+ * allocates nothing; there are no atomics, so a repeated launch is bit-identical.  BG_ERR_ARG with a message, before
+ * anything is launched, for a NULL pointer, a bad size or a misaligned pointer.
+ *
+ * bg_prdc_radii: x bf16 [N, D], 1 <= k <= 8, N >= k + 1 -> radius fp32 [N]: radius[n] is the k-th smallest d(x_n, x_m) over
+ *   m != n.  "Itself" is the row with the same index: a different row of equal content counts (and gives 0); ties count
+ *   with multiplicity.
+ * bg_prdc_cover: q bf16 [Q, D] with radius_q fp32 [Q], set bf16 [N, D] -> count int32 [N], count[n] = #{i < Q :
+ *   d(q_i, set_n) <= radius_q[i]} (inclusive; radius_q may hold 0 and +inf), and dmin fp32 [N], dmin[n] = min_i
+ *   d(q_i, set_n).  Either output may be NULL, not both; radius_q may be NULL when count is.
+ * bg_prdc_reduce: count_f int32 [M], count_r int32 [N], dmin_r and radius_r fp32 [N] -> out4 int64 [4], 8-byte aligned:
+ *   (#{count_f > 0}, sum count_f, #{count_r > 0}, #{dmin_r <= radius_r}).  With k and the sizes: precision = out4[0] / M,
+ *   density = out4[1] / (k M), recall = out4[2] / N, coverage = out4[3] / N, for count_f = cover(q = real with its radii,
+ *   set = fake), count_r = cover(q = fake with its radii, set = real) and dmin_r of the latter.
+ * ------------------------------------------------------------------------------------------ */
+int    bg_prdc_radii(const void* x, int64_t N, int D, int k, float* radius, void* stream);
+int    bg_prdc_cover(const void* q, const float* radius_q, int64_t Q, const void* set, int64_t N, int D, int32_t* count,
+                     float* dmin, void* stream);
+int    bg_prdc_reduce(const int32_t* count_f, int64_t M, const int32_t* count_r, const float* dmin_r, const float* radius_r,
+                      int64_t N, int64_t* out4, void* stream);
+
+/* --------------------------------------------------------------------------------------------
  * Optional per-kernel timing for bench.py's roofline leg: when enabled, every MFMA GEMM launch
  * (conv / deconv / gemm families) is bracketed by hipEvents on its stream.
  * bg_prof_collect synchronises the events and returns totals since the last reset.
