@@ -56,29 +56,128 @@ def floor_pow2(n):
     return 1 << (n.bit_length() - 1)
 
 
-class SwdPlan:
+class MonitorPlan:
+    """What the plans of the monitors share.  A plan class states ``name`` (its tag in messages), ``seed_stride`` and
+    ``draws`` (the names of its seeds, in order), and its constructor sets ``n_fake`` (images generated per event) and
+    ``n_stream`` (real images read at the first event)."""
+    name, seed_stride, draws = None, None, ()
+    images_per_label = 1                   # generated images that share one drawn row of the label table
+
+    def __init__(self, img_size, c_dim, batch_size, static_sample_seed, n_files):
+        if c_dim not in (1, 3, 4):
+            raise ValueError("%s: c_dim %d (1, 3 or 4)" % (self.name, c_dim))
+        self.img_size, self.c_dim, self.batch_size = int(img_size), int(c_dim), int(batch_size)
+        self.from_files = n_files is not None
+        base = int(static_sample_seed)
+        self.seeds = {name: (base + self.seed_stride * (i + 1)) % (1 << 32) for i, name in enumerate(self.draws)}
+
+    def real_order(self):
+        """Indices into the dataset's listing of the real images, in stream order; None: the first ``n_stream`` files."""
+        return None
+
+    def draw_latents(self, z_dim, trunc):
+        """fp32 [n_fake, 1, 1, z_dim] (sampling.draw_z) from a torch generator of the metric's own."""
+        g = torch.Generator(device="cpu")
+        g.manual_seed(self.seeds["latents"])
+        return Sp.draw_z(self.n_fake, z_dim, g, trunc)
+
+    def draw_labels(self, label_table):
+        """fp32 [n_fake, n_labels]: rows of the label table, drawn with replacement, each for ``images_per_label``
+        consecutive images."""
+        rows = Sp.draw_n_tags(label_table, self.n_fake // self.images_per_label, np.random.RandomState(self.seeds["labels"]))
+        return np.repeat(rows, self.images_per_label, axis=0)
+
+
+class Monitor:
+    """What the runners share: a plan on the device with the kept real set and the fake set's inputs, the bookkeeping of
+    ``add`` and ``finish``, and the event driver.  A runner has ``begin`` / ``add`` / ``finish`` of its own, states
+    ``prefix`` (of its scores' names) and may override ``begin_set`` / ``name_scores`` / ``real_scores``.  ``ops``: the
+    launch wrappers (functional.py)."""
+    prefix = None
+
+    def __init__(self, plan, device, ops=None):
+        self.plan, self.device = plan, torch.device(device)
+        self.ops = Fn if ops is None else ops
+        self.real = None                       # what ``finish`` returned for the real set, computed at the first event
+        self.fake_inputs = None                # (latents, class vectors or None) of the fake set, drawn once by the model
+
+    # ---- bookkeeping of one set ----------------------------------------------------------------------
+    def _expect(self, n):
+        self._n, self._filled = int(n), 0
+
+    def _take(self, img):
+        """The rows of ``img`` that the set still misses (None when it is full); the caller adds them to ``_filled``."""
+        p = self.plan
+        b = min(int(img.shape[0]), self._n - self._filled)
+        if b <= 0:
+            return None
+        g = img[:b]
+        if tuple(g.shape[1:]) != (p.img_size, p.img_size, p.c_dim):
+            raise ValueError("%s: images of %s, the plan is for %s" % (p.name, tuple(g.shape[1:]), (p.img_size, p.img_size, p.c_dim)))
+        return g
+
+    def _check_full(self):
+        if self._filled != self._n:
+            raise RuntimeError("%s: %d of %d images arrived" % (self.plan.name, self._filled, self._n))
+
+    # ---- one event --------------------------------------------------------------------------------------
+    def begin_set(self, real):
+        self.begin(self.plan.n_stream if real else None)
+
+    def name_scores(self, fake, ema):
+        """The scores of one finished fake set under the names they are logged by: ps_dist / ps_dist_noema."""
+        return {k + ("" if ema else "_noema"): v for k, v in self.scores(self.real, fake).items()}
+
+    def real_scores(self):
+        """What the real set alone adds to the first event's scores."""
+        return {}
+
+    def event(self, real_batches, generate, ema, noema, details=False):
+        """One event: (scores, {tag: what ``finish`` returned} when ``details``, else {}).  The first one measures the
+        real set, from the batches that ``real_batches()`` yields, and keeps it.  Then the moving averages' fake set and
+        / or the live weights', as ``ema`` / ``noema`` say: ``generate(ema, consume)`` passes every generated batch to
+        ``consume``.  A finished fake set is dropped once its scores are named unless ``details`` asks for it."""
+        first = self.real is None
+        if first:
+            self.begin_set(True)
+            for batch in real_batches():
+                self.add(batch)
+            self.real = self.finish()
+        out, sets = {}, {}
+        for from_ema, wanted in ((True, ema), (False, noema)):
+            if wanted:
+                self.begin_set(False)
+                generate(from_ema, self.add)
+                fake = self.finish()
+                out.update(self.name_scores(fake, from_ema))
+                if details:
+                    sets[self.prefix + ("" if from_ema else "_noema")] = fake
+                del fake                       # (the next set is generated without this one resident)
+        if first:
+            out.update(self.real_scores())
+        return out, sets
+
+
+class SwdPlan(MonitorPlan):
     """What one run of the metric needs, from the flags alone.
 
     n_images    --swd_images rounded down to a power of two (the sort takes power-of-two segments), and to the largest
                 power of two <= the number of dataset files when there is a dataset
     n_rows      N = 128 * n_images descriptors per level and set;  K = 49 * c_dim values each;  S = 4 * 128 directions
     seeds       one per draw, derived from --static_sample_seed"""
+    name, seed_stride = "swd", 7919
+    draws = ("directions", "pos_real", "pos_fake", "latents", "labels", "real")
 
     def __init__(self, img_size, c_dim, batch_size, swd_images, static_sample_seed, n_files=None, repeats=REPEATS,
                  n_dirs=N_DIRS):
-        if c_dim not in (1, 3, 4):
-            raise ValueError("swd: c_dim %d (1, 3 or 4)" % c_dim)
+        super().__init__(img_size, c_dim, batch_size, static_sample_seed, n_files)
         self.sides = level_sides(img_size)
-        self.img_size, self.c_dim, self.batch_size = int(img_size), int(c_dim), int(batch_size)
-        self.n_images = floor_pow2(swd_images if n_files is None else min(int(swd_images), int(n_files)))
-        self.from_files = n_files is not None
+        self.n_fake = self.n_stream = self.n_images = \
+            floor_pow2(swd_images if n_files is None else min(int(swd_images), int(n_files)))
         self.repeats, self.n_dirs = int(repeats), int(n_dirs)
         self.n_rows = PATCHES * self.n_images
         self.K = TAPS * self.c_dim
         self.S = self.repeats * self.n_dirs
-        base = int(static_sample_seed)
-        self.seeds = {name: (base + 7919 * (i + 1)) % (1 << 32)
-                      for i, name in enumerate(("directions", "pos_real", "pos_fake", "latents", "labels", "real"))}
 
     # ---- sizes in bytes -------------------------------------------------------------------------
     @property
@@ -117,44 +216,31 @@ class SwdPlan:
         rng = np.random.RandomState(self.seeds["pos_" + which])
         return [rng.randint(3, side - 3, size=(self.n_images, PATCHES, 2)).astype(np.int32) for side in self.sides]
 
-    def draw_latents(self, z_dim, trunc):
-        """fp32 [n_images, 1, 1, z_dim] (sampling.draw_z) from a torch generator of the metric's own."""
-        g = torch.Generator(device="cpu")
-        g.manual_seed(self.seeds["latents"])
-        return Sp.draw_z(self.n_images, z_dim, g, trunc)
 
-    def draw_labels(self, label_table):
-        """fp32 [n_images, n_labels]: rows of the label table, drawn with replacement."""
-        return Sp.draw_n_tags(label_table, self.n_images, np.random.RandomState(self.seeds["labels"]))
-
-
-class Swd:
+class Swd(Monitor):
     """A plan on the device.  ``begin`` / ``add`` / ``finish`` fill one set's descriptors a batch of images at a time
     (pyramid, gather, discard); ``scores`` projects, sorts and compares the two sets, one level at a time."""
 
+    prefix = "swd"
+
     def __init__(self, plan, device):
-        self.plan, self.device = plan, torch.device(device)
+        super().__init__(plan, device)         # real: (descriptors per level, statistics per level) of the real set
         self.dirs = [torch.from_numpy(d).to(self.device) for d in plan.draw_directions()]
         self.pos = {w: [torch.from_numpy(p).to(self.device) for p in plan.draw_positions(w)] for w in ("real", "fake")}
-        self.real = None                       # (descriptors per level, statistics per level) of the real set, kept
-        self.fake_inputs = None                # (latents, class vectors or None) of the fake set, drawn once by the model
 
     def begin(self, which):
         p = self.plan
-        self._which, self._filled = which, 0
+        self._which = which
+        self._expect(p.n_images)
         self._desc = [torch.empty(p.n_rows, p.K, dtype=torch.float32, device=self.device) for _ in p.sides]
         self._part = [Fn.swd_partials(p.n_images, p.c_dim, self.device) for _ in p.sides]
 
     def add(self, img):
         """Images [b, S, S, C] (fp32 or bf16); those past n_images (the padding of a last generator batch) are dropped."""
-        p = self.plan
-        b = min(int(img.shape[0]), p.n_images - self._filled)
-        if b <= 0:
+        p, g = self.plan, self._take(img)
+        if g is None:
             return
-        g = img[:b]
-        if tuple(g.shape[1:]) != (p.img_size, p.img_size, p.c_dim):
-            raise ValueError("swd: images of %s, the plan is for %s" % (tuple(g.shape[1:]), (p.img_size, p.img_size, p.c_dim)))
-        lo = self._filled
+        lo, b = self._filled, int(g.shape[0])
         for i in range(len(p.sides)):
             if i + 1 < len(p.sides):
                 g1 = Fn.swd_pyr_down(g)
@@ -166,8 +252,7 @@ class Swd:
         self._filled += b
 
     def finish(self):
-        if self._filled != self.plan.n_images:
-            raise RuntimeError("swd: %d of %d images arrived" % (self._filled, self.plan.n_images))
+        self._check_full()
         out = (self._desc, [Fn.swd_stats(w) for w in self._part])
         self._desc = self._part = None
         return out
@@ -187,6 +272,12 @@ class Swd:
         out = {"%s_%d" % (prefix, side): float(v) for side, v in zip(p.sides, per_level)}
         out[prefix + "_avg"] = float(np.mean(per_level))
         return out
+
+    def begin_set(self, real):
+        self.begin("real" if real else "fake")
+
+    def name_scores(self, fake, ema):
+        return self.scores(fake, "swd" if ema else "swd_noema")            # swd_64 / swd_noema_64
 
 
 # ---- in-training diversity score: mean MS-SSIM of generated pairs (csrc/msssim.hip; DESIGN.md gives the definition) ----
@@ -211,7 +302,7 @@ def msssim_weights(levels):
     return w / w.sum()
 
 
-class MsssimPlan:
+class MsssimPlan(MonitorPlan):
     """What one run of the diversity score needs, from the flags alone.
 
     n_pairs       P = --msssim_pairs generated pairs; the two images of a pair have independent latents and, with
@@ -219,23 +310,20 @@ class MsssimPlan:
     n_real_pairs  pairs of the real baseline: P random pairs of the first 2 P dataset files (fewer when the dataset has
                   fewer than 2 P files), or P pairs of uniform noise without a dataset
     seeds         one per draw, derived from --static_sample_seed; none is shared with SwdPlan or NnPlan"""
+    name, seed_stride, draws = "msssim", 15485863, ("latents", "labels", "real", "real_pairs")
+    images_per_label = 2                   # rows 2 p and 2 p + 1 are pair p: independent latents, one class vector
 
     def __init__(self, img_size, c_dim, batch_size, msssim_pairs, static_sample_seed, n_files=None):
-        if c_dim not in (1, 3, 4):
-            raise ValueError("msssim: c_dim %d (1, 3 or 4)" % c_dim)
+        super().__init__(img_size, c_dim, batch_size, static_sample_seed, n_files)
         self.sides = msssim_sides(img_size)
         self.weights = msssim_weights(len(self.sides))
-        self.img_size, self.c_dim, self.batch_size = int(img_size), int(c_dim), int(batch_size)
         self.n_pairs = int(msssim_pairs)
         if self.n_pairs < 1:
             raise ValueError("msssim: no pairs to measure (%d)" % self.n_pairs)
-        self.from_files = n_files is not None
         self.n_real_pairs = self.n_pairs if n_files is None else min(self.n_pairs, int(n_files) // 2)
         if self.n_real_pairs < 1:
             raise ValueError("msssim: the real baseline needs two dataset files, there are %d" % int(n_files))
-        base = int(static_sample_seed)
-        self.seeds = {name: (base + 15485863 * (i + 1)) % (1 << 32)
-                      for i, name in enumerate(("latents", "labels", "real", "real_pairs"))}
+        self.n_fake, self.n_stream = 2 * self.n_pairs, 2 * self.n_real_pairs
 
     # ---- sizes in bytes -------------------------------------------------------------------------
     @property
@@ -267,39 +355,27 @@ class MsssimPlan:
         return self.workspace_bytes + self.pyramid_bytes + self.score_bytes
 
     # ---- draws -------------------------------------------------------------------------------------
-    def draw_latents(self, z_dim, trunc):
-        """fp32 [2 P, 1, 1, z_dim] (sampling.draw_z): rows 2 p and 2 p + 1 are pair p, drawn independently."""
-        g = torch.Generator(device="cpu")
-        g.manual_seed(self.seeds["latents"])
-        return Sp.draw_z(2 * self.n_pairs, z_dim, g, trunc)
-
-    def draw_labels(self, label_table):
-        """fp32 [2 P, n_labels]: one row of the label table per pair, drawn with replacement, for both of its images."""
-        rows = Sp.draw_n_tags(label_table, self.n_pairs, np.random.RandomState(self.seeds["labels"]))
-        return np.repeat(rows, 2, axis=0)
-
     def draw_real_pairs(self):
         """int64 [n_real_pairs, 2]: a random perfect matching of the first 2 n_real_pairs dataset files."""
         perm = np.random.RandomState(self.seeds["real_pairs"]).permutation(2 * self.n_real_pairs)
         return perm.reshape(self.n_real_pairs, 2).astype(np.int64)
 
+    def real_order(self):
+        return self.draw_real_pairs().reshape(-1)
 
-class Msssim:
+
+class Msssim(Monitor):
     """A plan on the device.  ``begin`` / ``add`` / ``finish``: images arrive a generator batch at a time, rows 2 p and
     2 p + 1 of the stream being pair p.  A batch may hold an odd number of images, so the last image of one batch can be
     the first of a pair that the next batch completes: it is carried.  Per batch one workspace and one pooled pyramid
     exist; what stays is the fp64 score of every pair.  ``ops``: the launch wrappers (functional.py)."""
-
-    def __init__(self, plan, device, ops=None):
-        self.plan, self.device = plan, torch.device(device)
-        self.ops = Fn if ops is None else ops
-        self.fake_inputs = None                # (latents, class vectors or None), drawn once by the model
-        self.real = None                       # the real baseline, computed at the first event
+    prefix = "msssim"
 
     def begin(self, n_pairs=None):
-        self._n = self.plan.n_pairs if n_pairs is None else int(n_pairs)
-        self._scores = torch.zeros(self._n, dtype=torch.float64, device=self.device)
-        self._images, self._pairs, self._carry = 0, 0, None
+        n_pairs = self.plan.n_pairs if n_pairs is None else int(n_pairs)
+        self._expect(2 * n_pairs)
+        self._scores = torch.zeros(n_pairs, dtype=torch.float64, device=self.device)
+        self._pairs, self._carry = 0, None
 
     def _launch(self, x):
         """x [2 p, S, S, C]: p pairs as consecutive rows -> their scores at rows ``self._pairs`` on."""
@@ -319,14 +395,10 @@ class Msssim:
 
     def add(self, img):
         """Images [b, S, S, C] (fp32 or bf16); those past 2 n_pairs (the padding of a last generator batch) are dropped."""
-        p = self.plan
-        b = min(int(img.shape[0]), 2 * self._n - self._images)
-        if b <= 0:
+        g = self._take(img)
+        if g is None:
             return
-        g = img[:b]
-        if tuple(g.shape[1:]) != (p.img_size, p.img_size, p.c_dim):
-            raise ValueError("msssim: images of %s, the plan is for %s" % (tuple(g.shape[1:]), (p.img_size, p.img_size, p.c_dim)))
-        self._images += b
+        self._filled += int(g.shape[0])
         if self._carry is not None:                        # the pair that straddles two batches
             self._launch(torch.cat([self._carry.to(g.dtype), g[:1]]))
             self._carry, g = None, g[1:]
@@ -338,14 +410,22 @@ class Msssim:
 
     def finish(self):
         """The mean of the pairs' scores, the doubles added on the host in index order."""
-        if self._images != 2 * self._n or self._pairs != self._n:
-            raise RuntimeError("msssim: %d of %d images arrived" % (self._images, 2 * self._n))
+        self._check_full()                                 # (every image in: no pair is left half carried)
         per_pair = self._scores.cpu().numpy()
         self.per_pair, self._scores = per_pair, None
         total = 0.0
         for v in per_pair:
             total += float(v)
-        return total / self._n
+        return total / (self._n // 2)
+
+    def begin_set(self, real):
+        self.begin(self.plan.n_real_pairs if real else None)
+
+    def name_scores(self, fake, ema):
+        return {"msssim" if ema else "msssim_noema": fake}
+
+    def real_scores(self):
+        return {"msssim_real": self.real}
 
 
 # ---- in-training frequency check: radial power spectrum of real and generated images (csrc/powerspec.hip; DESIGN.md) ----
@@ -378,33 +458,29 @@ def ps_counts(S):
     return np.bincount(ps_bin_table(S).reshape(-1), weights=np.tile(w, S), minlength=ps_bins(S)).astype(np.int64)
 
 
-class PowerSpectrumPlan:
+class PowerSpectrumPlan(MonitorPlan):
     """What one run of the frequency check needs, from the flags alone.
 
     side, n_bins  S = --img_size, a power of two from 16 to 512; NB(S) radial bins, ``counts`` coefficients each
     n_images      --ps_images generated images per event; ``n_real`` real ones, once: the first n_images files of the
                   listing (all of them when the dataset has fewer), or n_images images of uniform noise without a dataset
     seeds         one per draw, derived from --static_sample_seed; none is shared with the other monitors"""
+    name, seed_stride, draws = "ps", 32452843, ("latents", "labels", "real")
 
     def __init__(self, img_size, c_dim, batch_size, ps_images, static_sample_seed, n_files=None):
-        if c_dim not in (1, 3, 4):
-            raise ValueError("ps: c_dim %d (1, 3 or 4)" % c_dim)
-        if int(img_size) not in PS_SIDES:
-            raise ValueError("ps: --img_size %d: the transform takes a power of two from 16 to 512" % int(img_size))
-        self.side = self.img_size = int(img_size)
-        self.c_dim, self.batch_size = int(c_dim), int(batch_size)
-        self.n_images = int(ps_images)
+        super().__init__(img_size, c_dim, batch_size, static_sample_seed, n_files)
+        if self.img_size not in PS_SIDES:
+            raise ValueError("ps: --img_size %d: the transform takes a power of two from 16 to 512" % self.img_size)
+        self.side = self.img_size
+        self.n_fake = self.n_images = int(ps_images)
         if self.n_images < 1:
             raise ValueError("ps: no images to measure (%d)" % self.n_images)
-        self.from_files = n_files is not None
-        self.n_real = self.n_images if n_files is None else min(self.n_images, int(n_files))
+        self.n_stream = self.n_real = self.n_images if n_files is None else min(self.n_images, int(n_files))
         if self.n_real < 1:
             raise ValueError("ps: the dataset has no files")
         self.n_bins = ps_bins(self.side)
         self.counts = ps_counts(self.side)
         self.first_hf = self.side // 4                                 # ps_hf / ps_peak read the bins r >= S/4
-        base = int(static_sample_seed)
-        self.seeds = {name: (base + 32452843 * (i + 1)) % (1 << 32) for i, name in enumerate(("latents", "labels", "real"))}
 
     # ---- sizes in bytes -------------------------------------------------------------------------
     @property
@@ -429,53 +505,32 @@ class PowerSpectrumPlan:
     def peak_bytes(self):
         return self.workspace_bytes + self.power_bytes + self.kept_bytes
 
-    # ---- draws -------------------------------------------------------------------------------------
-    def draw_latents(self, z_dim, trunc):
-        """fp32 [n_images, 1, 1, z_dim] (sampling.draw_z) from a torch generator of the metric's own."""
-        g = torch.Generator(device="cpu")
-        g.manual_seed(self.seeds["latents"])
-        return Sp.draw_z(self.n_images, z_dim, g, trunc)
 
-    def draw_labels(self, label_table):
-        """fp32 [n_images, n_labels]: rows of the label table, drawn with replacement."""
-        return Sp.draw_n_tags(label_table, self.n_images, np.random.RandomState(self.seeds["labels"]))
-
-
-class PowerSpectrum:
+class PowerSpectrum(Monitor):
     """A plan on the device.  ``begin`` / ``add`` / ``finish``: images arrive a batch at a time; per batch one power buffer
     and one workspace exist, what stays is the fp64 profile of every image and the fp64 2-D sum.  ``finish`` returns
     {"profile": the fp64 mean profile [NB], "sum2d": the summed power [S, S/2 + 1], "n": images}.  ``ops``: the launch
     wrappers (functional.py)."""
-
-    def __init__(self, plan, device, ops=None):
-        self.plan, self.device = plan, torch.device(device)
-        self.ops = Fn if ops is None else ops
-        self.fake_inputs = None                # (latents, class vectors or None), drawn once by the model
-        self.real = None                       # what ``finish`` returned for the real set, computed at the first event
+    prefix = "ps"
 
     def begin(self, n_images=None):
         p = self.plan
-        self._n = p.n_images if n_images is None else int(n_images)
+        self._expect(p.n_images if n_images is None else n_images)
         self._profiles = torch.zeros(self._n, p.n_bins, dtype=torch.float64, device=self.device)
         self._sum2d = torch.zeros(p.side, p.side // 2 + 1, dtype=torch.float64, device=self.device)
-        self._filled = 0
 
     def add(self, img):
         """Images [b, S, S, C] (fp32 or bf16); those past n_images (the padding of a last generator batch) are dropped."""
-        p = self.plan
-        b = min(int(img.shape[0]), self._n - self._filled)
-        if b <= 0:
+        g = self._take(img)
+        if g is None:
             return
-        g = img[:b]
-        if tuple(g.shape[1:]) != (p.side, p.side, p.c_dim):
-            raise ValueError("ps: images of %s, the plan is for %s" % (tuple(g.shape[1:]), (p.side, p.side, p.c_dim)))
+        b = int(g.shape[0])
         power = self.ops.ps_power(g)
         self.ops.ps_profile(power, self._profiles[self._filled:self._filled + b], self._sum2d)
         self._filled += b
 
     def finish(self):
-        if self._filled != self._n:
-            raise RuntimeError("ps: %d of %d images arrived" % (self._filled, self._n))
+        self._check_full()
         rows = self._profiles.cpu().numpy()
         total = np.zeros(self.plan.n_bins, dtype=np.float64)
         for row in rows:                                   # the fp64 mean over images, added in image order
@@ -566,7 +621,7 @@ def check_pr_k(k):
     return k
 
 
-class PrdcPlan:
+class PrdcPlan(MonitorPlan):
     """What one run of the precision / recall / density / coverage check needs, from the flags alone.
 
     side, f, D    descriptors are side x side x c_dim (neighbours.search_side(img_size, --pr_size)), each value the mean of
@@ -575,25 +630,21 @@ class PrdcPlan:
     N, M          real and generated images per event: --pr_images both, N capped by the number of dataset files; the real
                   ones are the first N files of the listing, or N images of uniform noise without a dataset
     seeds         one per draw, derived from --static_sample_seed; none is shared with the other monitors"""
+    name, seed_stride, draws = "prdc", 49979687, ("latents", "labels", "real")
 
     def __init__(self, img_size, c_dim, batch_size, pr_images=4096, pr_k=3, pr_size=64, static_sample_seed=0, n_files=None):
         from .neighbours import search_side
-        if c_dim not in (1, 3, 4):
-            raise ValueError("prdc: c_dim %d (1, 3 or 4)" % c_dim)
+        super().__init__(img_size, c_dim, batch_size, static_sample_seed, n_files)
         self.k = check_pr_k(pr_k)
         self.side = search_side(img_size, pr_size)
-        self.img_size, self.c_dim, self.batch_size = int(img_size), int(c_dim), int(batch_size)
         self.f = self.img_size // self.side
         self.D = self.side * self.side * self.c_dim
-        self.M = self.n_images = int(pr_images)
+        self.n_fake = self.M = self.n_images = int(pr_images)
         if self.M <= self.k:
             raise ValueError("prdc: --pr_images %d: more than --pr_k %d images are needed" % (self.M, self.k))
-        self.from_files = n_files is not None
-        self.N = self.n_real = self.M if n_files is None else min(self.M, int(n_files))
+        self.n_stream = self.N = self.n_real = self.M if n_files is None else min(self.M, int(n_files))
         if self.N <= self.k:
             raise ValueError("prdc: the dataset has %d files, more than --pr_k %d are needed" % (self.N, self.k))
-        base = int(static_sample_seed)
-        self.seeds = {name: (base + 49979687 * (i + 1)) % (1 << 32) for i, name in enumerate(("latents", "labels", "real"))}
 
     # ---- sizes in bytes -------------------------------------------------------------------------
     @property
@@ -611,50 +662,30 @@ class PrdcPlan:
     def peak_bytes(self):
         return self.N * self.D * 2 + self.M * self.D * 2 + self.vector_bytes
 
-    # ---- draws -------------------------------------------------------------------------------------
-    def draw_latents(self, z_dim, trunc):
-        """fp32 [M, 1, 1, z_dim] (sampling.draw_z) from a torch generator of the metric's own."""
-        g = torch.Generator(device="cpu")
-        g.manual_seed(self.seeds["latents"])
-        return Sp.draw_z(self.M, z_dim, g, trunc)
 
-    def draw_labels(self, label_table):
-        """fp32 [M, n_labels]: rows of the label table, drawn with replacement."""
-        return Sp.draw_n_tags(label_table, self.M, np.random.RandomState(self.seeds["labels"]))
-
-
-class Prdc:
+class Prdc(Monitor):
     """A plan on the device.  ``begin`` / ``add`` / ``finish``: images arrive a batch at a time and are packed
     (bg_nn_pack) into the resident bf16 buffer [n, D]; ``finish`` measures the set's radii and returns
     {"desc": bf16 [n, D], "radius": fp32 [n], "n": n}, both on the device.  ``scores`` takes two such sets.  ``ops``: the
     launch wrappers (functional.py)."""
-
-    def __init__(self, plan, device, ops=None):
-        self.plan, self.device = plan, torch.device(device)
-        self.ops = Fn if ops is None else ops
-        self.fake_inputs = None                # (latents, class vectors or None), drawn once by the model
-        self.real = None                       # what ``finish`` returned for the real set, computed at the first event
+    prefix = "pr"
 
     def begin(self, n_images=None):
         p = self.plan
-        self._n = p.M if n_images is None else int(n_images)
+        self._expect(p.M if n_images is None else n_images)
         self._desc = torch.empty(self._n, p.D, dtype=torch.bfloat16, device=self.device)
-        self._filled = 0
 
     def add(self, img):
         """Images [b, S, S, C] (fp32 or bf16); those past n (the padding of a last generator batch) are dropped."""
-        p = self.plan
-        b = min(int(img.shape[0]), self._n - self._filled)
-        if b <= 0:
+        g = self._take(img)
+        if g is None:
             return
-        if tuple(img.shape[1:]) != (p.img_size, p.img_size, p.c_dim):
-            raise ValueError("prdc: images of %s, the plan is for %s" % (tuple(img.shape[1:]), (p.img_size, p.img_size, p.c_dim)))
-        self.ops.nn_pack(img[:b], p.f, False, out=self._desc[self._filled:self._filled + b])
+        b = int(g.shape[0])
+        self.ops.nn_pack(g, self.plan.f, False, out=self._desc[self._filled:self._filled + b])
         self._filled += b
 
     def finish(self):
-        if self._filled != self._n:
-            raise RuntimeError("prdc: %d of %d images arrived" % (self._filled, self._n))
+        self._check_full()
         out = {"desc": self._desc, "radius": self.ops.prdc_radii(self._desc, self.plan.k), "n": self._n}
         self._desc = None
         return out
@@ -679,6 +710,13 @@ class Prdc:
         fake is inside the real's own ball.  One 32-byte copy to the host."""
         out4 = self.counts(real, fake)[3].cpu().tolist()
         return self.ratios(out4, self.plan.k, real["n"], fake["n"], prefix)
+
+
+# kind -> (plan class, runner class, the model's flags that the plan's constructor takes after batch_size)
+MONITORS = {"swd": (SwdPlan, Swd, ("swd_images",)),
+            "msssim": (MsssimPlan, Msssim, ("msssim_pairs",)),
+            "ps": (PowerSpectrumPlan, PowerSpectrum, ("ps_images",)),
+            "prdc": (PrdcPlan, Prdc, ("pr_images", "pr_k", "pr_size"))}
 
 
 def format_scores(scores):

@@ -176,7 +176,8 @@ class BigGAN(GANBase):
         # in-training quality score (extension flags --swd_freq / --swd_images; metrics.py)
         self.swd_freq = int(getattr(args, "swd_freq", 0) or 0)
         self.swd_images = int(getattr(args, "swd_images", 2048) or 2048)
-        self._swd = None                       # metrics.Swd with the kept real set, built at the first event
+        self._monitors = {}                    # kind -> its metrics.Monitor with the kept real set and the draws of the run,
+                                               # built at the kind's first event ("swd", "msssim", "ps", "prdc")
         # nearest training images (extension flags --nn_freq / --nn_k / --nn_size / --nn_images; neighbours.py)
         self.nn_freq = int(getattr(args, "nn_freq", 0) or 0)
         self.nn_k = int(getattr(args, "nn_k", 3) or 3)
@@ -186,18 +187,15 @@ class BigGAN(GANBase):
         # in-training diversity score (extension flags --msssim_freq / --msssim_pairs; metrics.py)
         self.msssim_freq = int(getattr(args, "msssim_freq", 0) or 0)
         self.msssim_pairs = int(getattr(args, "msssim_pairs", 1024) or 1024)
-        self._msssim = None                    # metrics.Msssim with the draws of the run, built at the first event
         # in-training frequency check (extension flags --ps_freq / --ps_images; metrics.py)
         self.ps_freq = int(getattr(args, "ps_freq", 0) or 0)
         self.ps_images = int(getattr(args, "ps_images", 1024) or 1024)
-        self._ps = None                        # metrics.PowerSpectrum with the real set's profile and the draws of the run
         # in-training precision / recall / density / coverage (extension flags --pr_freq / --pr_images / --pr_k /
         # --pr_size; metrics.py)
         self.pr_freq = int(getattr(args, "pr_freq", 0) or 0)
         self.pr_images = int(getattr(args, "pr_images", 4096))
         self.pr_k = int(getattr(args, "pr_k", 3))
         self.pr_size = int(getattr(args, "pr_size", 64))
-        self._prdc = None                      # metrics.Prdc with the real set, its radii and the draws of the run
         # singular-value monitor (extension flags --sv_freq / --sv_k / --sv_iters / --sv_tol; spectrum.py)
         self.sv_freq = int(getattr(args, "sv_freq", 0) or 0)
         self.sv_k = int(getattr(args, "sv_k", 3))
@@ -1591,40 +1589,20 @@ class BigGAN(GANBase):
                 if samples and (idx + 1) % self.print_freq == 0:                      # BigGAN.py:1125
                     self.save_samples(epoch, idx + 1)
                 if self.swd_freq > 0 and self.counter % self.swd_freq == 0:
-                    scores = self.swd()                                                # (collective: every rank enters)
-                    if self.rank == 0:
-                        from .metrics import format_scores
-                        print("SWD: " + format_scores(scores), flush=True)
-                        if self._log_writer is not None:
-                            self._log_writer.add_scalars(self.counter - 1, scores)
+                    self._log_scores("SWD", self.swd())                                # (collective: every rank enters)
                 if self.nn_freq > 0 and self.counter % self.nn_freq == 0:
                     self.save_neighbours(epoch, idx + 1)                               # (collective: every rank enters)
                 if self.msssim_freq > 0 and self.counter % self.msssim_freq == 0:
-                    scores = self.msssim()                                             # (collective: every rank enters)
-                    if self.rank == 0:
-                        from .metrics import format_scores
-                        print("MS-SSIM: " + format_scores(scores), flush=True)
-                        if self._log_writer is not None:
-                            self._log_writer.add_scalars(self.counter - 1, scores)
+                    self._log_scores("MS-SSIM", self.msssim())                         # (collective: every rank enters)
                 if self.sv_freq > 0 and self.counter % self.sv_freq == 0 and self.rank == 0:
                     values, line, _ = self.singular_values()       # (rank 0 only: the weights are the same on every rank)
                     print(line, flush=True)
                     if self._log_writer is not None:
                         self._log_writer.add_scalars(self.counter - 1, values)
                 if self.ps_freq > 0 and self.counter % self.ps_freq == 0:
-                    scores = self.power_spectrum()                                     # (collective: every rank enters)
-                    if self.rank == 0:
-                        from .metrics import format_scores
-                        print("PS: " + format_scores(scores), flush=True)
-                        if self._log_writer is not None:
-                            self._log_writer.add_scalars(self.counter - 1, scores)
+                    self._log_scores("PS", self.power_spectrum())                      # (collective: every rank enters)
                 if self.pr_freq > 0 and self.counter % self.pr_freq == 0:
-                    scores = self.prdc()                                               # (collective: every rank enters)
-                    if self.rank == 0:
-                        from .metrics import format_scores
-                        print("PRDC: " + format_scores(scores), flush=True)
-                        if self._log_writer is not None:
-                            self._log_writer.add_scalars(self.counter - 1, scores)
+                    self._log_scores("PRDC", self.prdc())                              # (collective: every rank enters)
             start_batch_id = 0                                                         # BigGAN.py:1164-1166
             self.save(self.checkpoint_dir, self.counter)
             if self._log_writer is not None:
@@ -1879,17 +1857,43 @@ class BigGAN(GANBase):
             write(Sp.sample_names(self.model_name, epoch, idx, tag)["cls"], zs[:dim * dim], cls_z, True, dim)
         return paths
 
-    # ---- in-training quality score (metrics.py) -------------------------------------------------
-    def swd_real_batches(self, plan, root="./dataset"):
-        """The real set of the quality score, ``batch_size`` images at a time on the device: with a dataset folder the
-        first ``plan.n_images`` files of the listing, decoded and resized by the host path without flips (never taken from
-        the training loader); without one, uniform noise from a generator of the metric's own."""
-        B, M = self.batch_size, plan.n_images
+    # ---- in-training monitors: quality, diversity, frequency check, precision / recall (metrics.py) ----
+    def _dataset_files(self, root="./dataset"):
+        """The dataset's file listing (None without a dataset folder), as the training loader would list it."""
+        from . import data as D
+        if not os.path.isdir(os.path.join(root, self.dataset_name)):
+            return None
+        files, _ = D.load_data(self.dataset_name, self.args.label_file, self.args.weight_file,
+                               ignore_missing=self.args.ignore_missing_labels, n_labels=self.n_labels, root=root)
+        return list(files)
+
+    def monitor_plan(self, kind, root="./dataset"):
+        """The plan of the monitor ``kind`` ("swd", "msssim", "ps" or "prdc") from its flags and the dataset's listing."""
+        from .metrics import MONITORS
+        plan_class, _, flags = MONITORS[kind]
+        files = self._dataset_files(root)
+        return plan_class(self.img_size, self.c_dim, self.batch_size, *[getattr(self, f) for f in flags],
+                          self.static_sample_seed, n_files=None if files is None else len(files))
+
+    def monitor_fake_inputs(self, plan):
+        """(latents [n,1,1,z_dim], class vectors [n,n_labels] or None) of a monitor's fake set, n = ``plan.n_fake``: drawn
+        from the plan's seeds, with --z_trunc_train's truncation and rows of the label table, the same at every event.
+        (MS-SSIM: rows 2p and 2p + 1 are pair p - independent latents, one row of the label table for both.)"""
+        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
+        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
+
+    def monitor_real_batches(self, plan, root="./dataset"):
+        """The real set of a monitor, at most ``batch_size`` images at a time on the device: with a dataset folder the
+        first ``plan.n_stream`` files of the listing, or those that ``plan.real_order()`` names (MS-SSIM: a random matching
+        of the first files, the pairs as consecutive rows), decoded and resized by the host path without flips (never
+        taken from the training loader); without one, uniform noise from a generator of the metric's own."""
+        B, M = self.batch_size, plan.n_stream
         if plan.from_files:
             import numpy as np
             from . import data as D
             image_data = D.ImageData(self.img_size, self.c_dim, True, False)
-            files = self._swd_files(root)[:M]
+            files, order = self._dataset_files(root), plan.real_order()
+            files = files[:M] if order is None else [files[i] for i in order]
             for lo in range(0, M, B):
                 yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in files[lo:lo + B]])).to(self.device)
         else:
@@ -1899,26 +1903,45 @@ class BigGAN(GANBase):
                 yield torch.rand(min(B, M - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
                                  generator=gen) * 2.0 - 1.0
 
-    def _swd_files(self, root="./dataset"):
-        """The dataset's file listing (None without a dataset folder), as the training loader would list it."""
-        from . import data as D
-        if not os.path.isdir(os.path.join(root, self.dataset_name)):
-            return None
-        files, _ = D.load_data(self.dataset_name, self.args.label_file, self.args.weight_file,
-                               ignore_missing=self.args.ignore_missing_labels, n_labels=self.n_labels, root=root)
-        return list(files)
+    def _monitor_event(self, kind, root="./dataset", details=False):
+        """One event of the monitor ``kind`` (metrics.Monitor.event): its scores, or with ``details`` (scores, the runner,
+        {tag: what ``finish`` returned}).  The runner is built at the kind's first event and kept with its real set; the
+        fake set's inputs are drawn once, after the real set is measured.  Every rank calls it (``sync_sharded_state`` is
+        collective); rank 0 computes, the others return {}."""
+        from .metrics import MONITORS
+        self.sync_sharded_state()
+        if self.rank != 0:
+            return ({}, None, {}) if details else {}
+        with torch.no_grad():
+            m = self._monitors.get(kind)
+            if m is None:
+                m = self._monitors[kind] = MONITORS[kind][1](self.monitor_plan(kind, root), self.device)
 
-    def swd_plan(self, root="./dataset"):
-        from .metrics import SwdPlan
-        files = self._swd_files(root)
-        return SwdPlan(self.img_size, self.c_dim, self.batch_size, self.swd_images, self.static_sample_seed,
-                       n_files=None if files is None else len(files))
+            def generate(ema, consume):
+                if m.fake_inputs is None:
+                    m.fake_inputs = self.monitor_fake_inputs(m.plan)
+                self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=consume)
 
-    def swd_fake_inputs(self, plan):
-        """(latents [n,1,1,z_dim], class vectors [n,n_labels] or None) of the fake set: drawn from the plan's seeds, with
-        --z_trunc_train's truncation and rows of the label table, the same at every event."""
-        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
-        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
+            out, sets = m.event(lambda: self.monitor_real_batches(m.plan, root), generate, self.generate_ema_samples,
+                                self.generate_noema_samples, details)
+        return (out, m, sets) if details else out
+
+    def _log_scores(self, tag, scores):
+        """Rank 0: the "TAG: name: value, ..." line of an event and, while a training log is open, its scalars.  Returns
+        ``scores``."""
+        if self.rank == 0:
+            from .metrics import format_scores
+            print(tag + ": " + format_scores(scores), flush=True)
+            if getattr(self, "_log_writer", None) is not None:                       # (--phase test opens no log)
+                self._log_writer.add_scalars(self.counter - 1, scores)
+        return scores
+
+    def _write_scores(self, path, scores):
+        """Rank 0: one "name<TAB>value" row per score."""
+        if self.rank == 0:
+            with open(path, "w") as f:
+                for k, v in scores.items():
+                    f.write("%s\t%.6f\n" % (k, v))
 
     def swd(self, root="./dataset"):
         """The sliced Wasserstein scores of the current weights: {``swd_<side>``: 1e3 x distance per pyramid level,
@@ -1926,63 +1949,7 @@ class BigGAN(GANBase):
         says.  The real set's descriptors are computed at the first call and kept; the fake set is regenerated through
         ``generate`` a batch at a time from latents drawn once.  Every rank calls it (``sync_sharded_state`` is
         collective); rank 0 computes, the others return {}.  Nothing the training run reads is changed."""
-        from . import metrics
-        self.sync_sharded_state()
-        if self.rank != 0:
-            return {}
-        with torch.no_grad():
-            if self._swd is None:
-                plan = self.swd_plan(root)
-                m = metrics.Swd(plan, self.device)
-                m.begin("real")
-                for batch in self.swd_real_batches(plan, root):
-                    m.add(batch)
-                m.real = m.finish()
-                m.fake_inputs = self.swd_fake_inputs(plan)
-                self._swd = m
-            m = self._swd
-            out = {}
-            for prefix, ema, wanted in (("swd", True, self.generate_ema_samples),
-                                        ("swd_noema", False, self.generate_noema_samples)):
-                if wanted:
-                    m.begin("fake")
-                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
-                    out.update(m.scores(m.finish(), prefix))
-        return out
-
-    # ---- in-training diversity score (metrics.py) ------------------------------------------------
-    def msssim_plan(self, root="./dataset"):
-        from .metrics import MsssimPlan
-        files = self._swd_files(root)
-        return MsssimPlan(self.img_size, self.c_dim, self.batch_size, self.msssim_pairs, self.static_sample_seed,
-                          n_files=None if files is None else len(files))
-
-    def msssim_fake_inputs(self, plan):
-        """(latents [2P,1,1,z_dim], class vectors [2P,n_labels] or None): rows 2p and 2p + 1 are pair p - independent
-        latents with --z_trunc_train's truncation, one row of the label table for both - the same at every event."""
-        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
-        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
-
-    def msssim_real_batches(self, plan, root="./dataset"):
-        """The pairs of the real baseline as consecutive rows, at most ``batch_size`` images at a time on the device: with
-        a dataset folder a random matching of the first 2 ``plan.n_real_pairs`` files of the listing (the plan's draw),
-        decoded and resized by the host path without flips (never taken from the training loader); without one, uniform
-        noise from a generator of the metric's own."""
-        B, M = self.batch_size, 2 * plan.n_real_pairs
-        if plan.from_files:
-            import numpy as np
-            from . import data as D
-            image_data = D.ImageData(self.img_size, self.c_dim, True, False)
-            files = self._swd_files(root)
-            order = [files[i] for i in plan.draw_real_pairs().reshape(-1)]
-            for lo in range(0, M, B):
-                yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in order[lo:lo + B]])).to(self.device)
-        else:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(plan.seeds["real"])
-            for lo in range(0, M, B):
-                yield torch.rand(min(B, M - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
-                                 generator=gen) * 2.0 - 1.0
+        return self._monitor_event("swd", root)
 
     def msssim(self, root="./dataset"):
         """The diversity score of the current weights: {``msssim``: the mean MS-SSIM of --msssim_pairs generated pairs} for
@@ -1991,34 +1958,7 @@ class BigGAN(GANBase):
         of dataset images (dataset-wide, not per class).  The pairs are regenerated through ``generate`` a batch at a
         time from latents and class vectors drawn once.  Every rank calls it (``sync_sharded_state`` is collective);
         rank 0 computes, the others return {}.  Nothing the training run reads is changed."""
-        from . import metrics
-        self.sync_sharded_state()
-        if self.rank != 0:
-            return {}
-        with torch.no_grad():
-            out = {}
-            if self._msssim is None:
-                plan = self.msssim_plan(root)
-                m = metrics.Msssim(plan, self.device)
-                m.begin(plan.n_real_pairs)
-                for batch in self.msssim_real_batches(plan, root):
-                    m.add(batch)
-                m.real = m.finish()
-                m.fake_inputs = self.msssim_fake_inputs(plan)
-                self._msssim = m
-                real = m.real
-            else:
-                real = None
-            m = self._msssim
-            for name, ema, wanted in (("msssim", True, self.generate_ema_samples),
-                                      ("msssim_noema", False, self.generate_noema_samples)):
-                if wanted:
-                    m.begin()
-                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
-                    out[name] = m.finish()
-            if real is not None:
-                out["msssim_real"] = real
-        return out
+        return self._monitor_event("msssim", root)
 
     # ---- singular-value monitor (spectrum.py) -----------------------------------------------------
     def singular_values(self):
@@ -2047,38 +1987,6 @@ class BigGAN(GANBase):
         values, top = spectrum.scalars(result, self.sv_k, sigma_of)
         return values, spectrum.format_line(result, top), result
 
-    # ---- in-training frequency check (metrics.py) --------------------------------------------------
-    def ps_plan(self, root="./dataset"):
-        from .metrics import PowerSpectrumPlan
-        files = self._swd_files(root)
-        return PowerSpectrumPlan(self.img_size, self.c_dim, self.batch_size, self.ps_images, self.static_sample_seed,
-                                 n_files=None if files is None else len(files))
-
-    def ps_fake_inputs(self, plan):
-        """(latents [n,1,1,z_dim], class vectors [n,n_labels] or None), with --z_trunc_train's truncation: the same at
-        every event."""
-        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
-        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
-
-    def ps_real_batches(self, plan, root="./dataset"):
-        """The real set, at most ``batch_size`` images at a time on the device: with a dataset folder the first
-        ``plan.n_real`` files of the listing, decoded and resized by the host path without flips (never taken from the
-        training loader); without one, uniform noise from a generator of the metric's own."""
-        B, M = self.batch_size, plan.n_real
-        if plan.from_files:
-            import numpy as np
-            from . import data as D
-            image_data = D.ImageData(self.img_size, self.c_dim, True, False)
-            files = self._swd_files(root)[:M]
-            for lo in range(0, M, B):
-                yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in files[lo:lo + B]])).to(self.device)
-        else:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(plan.seeds["real"])
-            for lo in range(0, M, B):
-                yield torch.rand(min(B, M - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
-                                 generator=gen) * 2.0 - 1.0
-
     def power_spectrum(self, root="./dataset", details=False):
         """The frequency check of the current weights: the radial power spectrum of --ps_images generated images against
         the real set's, as ``ps_dist`` (decades), ``ps_hf`` (above 0: excess fine structure, below 0: blur), ``ps_peak``
@@ -2087,70 +1995,13 @@ class BigGAN(GANBase):
         fakes are regenerated through ``generate`` a batch at a time from latents and class vectors drawn once.  Every
         rank calls it (``sync_sharded_state`` is collective); rank 0 computes, the others return {}.  Nothing the
         training run reads is changed.  ``details``: return (scores, the runner, {tag: what ``finish`` returned})."""
-        from . import metrics
-        self.sync_sharded_state()
-        if self.rank != 0:
-            return ({}, None, {}) if details else {}
-        with torch.no_grad():
-            out, sets = {}, {}
-            if self._ps is None:
-                plan = self.ps_plan(root)
-                m = metrics.PowerSpectrum(plan, self.device)
-                m.begin(plan.n_real)
-                for batch in self.ps_real_batches(plan, root):
-                    m.add(batch)
-                m.real = m.finish()
-                m.fake_inputs = self.ps_fake_inputs(plan)
-                self._ps = m
-            m = self._ps
-            for name, ema, wanted in (("ps", True, self.generate_ema_samples), ("ps_noema", False, self.generate_noema_samples)):
-                if wanted:
-                    m.begin()
-                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
-                    sets[name] = m.finish()
-                    for k, v in m.scores(m.real, sets[name]).items():
-                        out[k + name[2:]] = v                              # ps_dist / ps_dist_noema
-        return (out, m, sets) if details else out
+        return self._monitor_event("ps", root, details)
 
     def save_power_spectrum(self, folder, root="./dataset"):
         """--phase test: ``ps.txt`` (one row per radius: r, r/S, n_r, L_real, L_fake (and L_fake_noema), D) and ``ps.png``
         (the mean 2-D spectra of the real and the fake set side by side, log10 over 8 decades) in ``folder``."""
         scores, m, sets = self.power_spectrum(root, details=True)
-        if self.rank != 0:
-            return scores, []
-        return scores, m.save(folder, m.real, sets)
-
-    # ---- in-training precision / recall / density / coverage (metrics.py) ---------------------------
-    def prdc_plan(self, root="./dataset"):
-        from .metrics import PrdcPlan
-        files = self._swd_files(root)
-        return PrdcPlan(self.img_size, self.c_dim, self.batch_size, self.pr_images, self.pr_k, self.pr_size,
-                        self.static_sample_seed, n_files=None if files is None else len(files))
-
-    def prdc_fake_inputs(self, plan):
-        """(latents [M,1,1,z_dim], class vectors [M,n_labels] or None), with --z_trunc_train's truncation: the same at
-        every event."""
-        z = plan.draw_latents(self.z_dim, self.z_trunc_train)
-        return z, (plan.draw_labels(self._label_table()) if self.acgan else None)
-
-    def prdc_real_batches(self, plan, root="./dataset"):
-        """The real set, at most ``batch_size`` images at a time on the device: with a dataset folder the first
-        ``plan.N`` files of the listing, decoded and resized by the host path without flips (never taken from the
-        training loader); without one, uniform noise from a generator of the metric's own."""
-        B, N = self.batch_size, plan.N
-        if plan.from_files:
-            import numpy as np
-            from . import data as D
-            image_data = D.ImageData(self.img_size, self.c_dim, True, False)
-            files = self._swd_files(root)[:N]
-            for lo in range(0, N, B):
-                yield torch.from_numpy(np.stack([image_data.image_processing(f) for f in files[lo:lo + B]])).to(self.device)
-        else:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(plan.seeds["real"])
-            for lo in range(0, N, B):
-                yield torch.rand(min(B, N - lo), self.img_size, self.img_size, self.c_dim, device=self.device,
-                                 generator=gen) * 2.0 - 1.0
+        return scores, ([] if self.rank != 0 else m.save(folder, m.real, sets))
 
     def prdc(self, root="./dataset", details=False):
         """Improved precision / recall and density / coverage of --pr_images generated images against the real set in the
@@ -2161,30 +2012,7 @@ class BigGAN(GANBase):
         reduction, and reads 32 bytes back.  Every rank calls it (``sync_sharded_state`` is collective); rank 0 computes,
         the others return {}.  Nothing the training run reads is changed.  ``details``: return (scores, the runner,
         {tag: what ``finish`` returned})."""
-        from . import metrics
-        self.sync_sharded_state()
-        if self.rank != 0:
-            return ({}, None, {}) if details else {}
-        with torch.no_grad():
-            out, sets = {}, {}
-            if self._prdc is None:
-                plan = self.prdc_plan(root)
-                m = metrics.Prdc(plan, self.device)
-                m.begin(plan.N)
-                for batch in self.prdc_real_batches(plan, root):
-                    m.add(batch)
-                m.real = m.finish()
-                m.fake_inputs = self.prdc_fake_inputs(plan)
-                self._prdc = m
-            m = self._prdc
-            for name, ema, wanted in (("pr", True, self.generate_ema_samples), ("pr_noema", False, self.generate_noema_samples)):
-                if wanted:
-                    m.begin()
-                    self.generate(m.fake_inputs[0], m.fake_inputs[1], ema=ema, _synced=True, _consume=m.add)
-                    sets[name] = m.finish()
-                    for k, v in m.scores(m.real, sets[name]).items():
-                        out[k + name[2:]] = v                              # pr_recall / pr_recall_noema
-        return (out, m, sets) if details else out
+        return self._monitor_event("prdc", root, details)
 
     def save_prdc(self, folder, root="./dataset"):
         """--phase test: ``prdc.txt`` in ``folder``: one "name<TAB>value" row per score, then k, N, M and D."""
@@ -2192,9 +2020,8 @@ class BigGAN(GANBase):
         if self.rank != 0:
             return scores, []
         path = os.path.join(folder, "prdc.txt")
-        with open(path, "w") as f:
-            for k, v in scores.items():
-                f.write("%s\t%.6f\n" % (k, v))
+        self._write_scores(path, scores)
+        with open(path, "a") as f:
             for k, v in (("k", m.plan.k), ("N", m.plan.N), ("M", m.plan.M), ("D", m.plan.D)):
                 f.write("%s\t%d\n" % (k, v))
         return scores, [path]
@@ -2202,7 +2029,7 @@ class BigGAN(GANBase):
     # ---- nearest training images (neighbours.py) -------------------------------------------------
     def nn_plan(self, root="./dataset"):
         from .neighbours import NnPlan
-        files = self._swd_files(root)
+        files = self._dataset_files(root)
         return NnPlan(self.img_size, self.c_dim, self.batch_size, self.nn_size, self.nn_images, self.static_sample_seed,
                       n_files=None if files is None else len(files))
 
@@ -2242,7 +2069,7 @@ class BigGAN(GANBase):
         if self._nn is None:
             from . import neighbours
             plan = self.nn_plan(root)
-            files = self._swd_files(root)
+            files = self._dataset_files(root)
             s = neighbours.NearestSet(plan, self.device, files)
             for batch in self.nn_set_batches(plan, files):
                 s.add(batch)
@@ -2333,35 +2160,18 @@ class BigGAN(GANBase):
             paths.append(save_images(samples[:dim * dim, :, :, :], [dim, dim],
                                      result_dir + '/' + self.model_name + '_test_{}.png'.format(i)))
         if self.swd_freq > 0:
-            from .metrics import format_scores
-            scores = self.swd()
-            if self.rank == 0:
-                print("SWD: " + format_scores(scores), flush=True)
-                with open(os.path.join(result_dir, "swd.txt"), "w") as f:
-                    for k, v in scores.items():
-                        f.write("%s\t%.6f\n" % (k, v))
+            self._write_scores(os.path.join(result_dir, "swd.txt"), self._log_scores("SWD", self.swd()))
         if self.nn_freq > 0:
             paths += self.save_neighbours(0, 0, folder=result_dir,
                                           names={p: {"png": p + ".png", "txt": p + ".txt"} for p in ("nn", "nn_noema")})
         if self.msssim_freq > 0:
-            from .metrics import format_scores
-            scores = self.msssim()
-            if self.rank == 0:
-                print("MS-SSIM: " + format_scores(scores), flush=True)
-                with open(os.path.join(result_dir, "msssim.txt"), "w") as f:
-                    for k, v in scores.items():
-                        f.write("%s\t%.6f\n" % (k, v))
+            self._write_scores(os.path.join(result_dir, "msssim.txt"), self._log_scores("MS-SSIM", self.msssim()))
         if self.ps_freq > 0:
-            from .metrics import format_scores
             scores, written = self.save_power_spectrum(result_dir)
-            if self.rank == 0:
-                print("PS: " + format_scores(scores), flush=True)
-                paths += [p for p in written if p.endswith(".png")]
+            self._log_scores("PS", scores)
+            paths += [p for p in written if p.endswith(".png")]
         if self.pr_freq > 0:
-            from .metrics import format_scores
-            scores, _ = self.save_prdc(result_dir)
-            if self.rank == 0:
-                print("PRDC: " + format_scores(scores), flush=True)
+            self._log_scores("PRDC", self.save_prdc(result_dir)[0])
         if self.sv_freq > 0 and self.rank == 0:
             _, line, result = self.singular_values()
             print(line, flush=True)

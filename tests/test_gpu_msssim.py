@@ -208,15 +208,15 @@ def test_model_scores_agree_with_the_reference_and_leave_the_run_alone(tmp_path)
     assert list(first) == ["msssim", "msssim_real"] and list(second) == ["msssim"]       # the baseline: the first call only
     assert second["msssim"] == first["msssim"] and all(0.0 <= v <= 1.0 + 1e-6 for v in first.values())
     # the same images through the float64 restatement: 5 pairs = 10 images in batches of 4, so a pair is carried
-    plan = gan.msssim_plan()
+    plan = gan.monitor_plan("msssim")
     assert plan.n_pairs == 5 and not plan.from_files and plan.n_real_pairs == 5
-    z, cls_z = gan.msssim_fake_inputs(plan)
+    z, cls_z = gan.monitor_fake_inputs(plan)
     assert z.shape[0] == 10 and cls_z is None
     fake = gan.generate(z, cls_z, ema=True).float().cpu().numpy()
     want, gate = _reference_with_its_own_gate(fake)
     print("msssim: device %.9g reference %.9g gate %.3g" % (first["msssim"], want, gate))
     assert abs(first["msssim"] - want) <= gate
-    real = torch.cat(list(gan.msssim_real_batches(plan))).cpu().numpy()
+    real = torch.cat(list(gan.monitor_real_batches(plan))).cpu().numpy()
     want, gate = _reference_with_its_own_gate(real)
     print("msssim_real: device %.9g reference %.9g gate %.3g" % (first["msssim_real"], want, gate))
     assert abs(first["msssim_real"] - want) <= gate
@@ -233,8 +233,8 @@ def test_model_scores_agree_with_the_reference_and_leave_the_run_alone(tmp_path)
 
 def test_pairs_share_a_class_vector_with_labels(tmp_path):
     gan = _model(tmp_path, "labels", n_labels=4)
-    plan = gan.msssim_plan()
-    z, cls_z = gan.msssim_fake_inputs(plan)
+    plan = gan.monitor_plan("msssim")
+    z, cls_z = gan.monitor_fake_inputs(plan)
     assert cls_z.shape == (10, 4) and np.array_equal(cls_z[0::2], cls_z[1::2])
     scores = gan.msssim()
     fake = gan.generate(z, cls_z, ema=True).float().cpu().numpy()
@@ -250,12 +250,12 @@ def test_the_real_baseline_pairs_the_first_files_without_flips(tmp_path):
     for i in range(7):
         utils.write_png(rng.randint(0, 256, size=(70, 80, 3)).astype(np.uint8), str(root / "toy" / ("%02d.png" % i)))
     gan = _model(tmp_path, "files", dataset="toy")
-    plan = gan.msssim_plan(str(root))
+    plan = gan.monitor_plan("msssim", str(root))
     assert plan.from_files and plan.n_real_pairs == 3                   # min(5 asked, 7 // 2 files)
-    files = gan._swd_files(str(root))
+    files = gan._dataset_files(str(root))
     order = plan.draw_real_pairs().reshape(-1)
     assert sorted(order) == list(range(6))
-    real = torch.cat(list(gan.msssim_real_batches(plan, str(root))))
+    real = torch.cat(list(gan.monitor_real_batches(plan, str(root))))
     want = np.stack([D.ImageData(64, 3, True, False).image_processing(files[i]) for i in order])
     assert np.array_equal(real.cpu().numpy(), want)
     scores = gan.msssim(str(root))
@@ -303,7 +303,7 @@ def test_training_state_and_losses_with_the_score_are_bit_identical(run_pair):
         assert torch.equal(a[k], b[k]), k
     assert any(k.endswith("/u") for k in a) and any(k.endswith("/Adam_1") for k in a)
     assert torch.equal(scored.gen.get_state(), plain.gen.get_state()) and scored.counter == plain.counter == 3
-    assert plain._msssim is None and scored._msssim is not None
+    assert plain._monitors.get("msssim") is None and scored._monitors.get("msssim") is not None
     assert len(run_pair["seen"]) == 3 and run_pair["seen"] == run_pair["seen2"]
 
 

@@ -323,10 +323,10 @@ def test_model_scores_agree_with_the_reference_and_leave_the_run_alone(tmp_path)
     real = runner.real
     assert real["n"] == 16 and tuple(real["desc"].shape) == (16, plan.D) and tuple(real["radius"].shape) == (16,)
     # the descriptors are those of the plan's draws through the generator and the pack
-    z, cls_z = gan.prdc_fake_inputs(plan)
+    z, cls_z = gan.monitor_fake_inputs(plan)
     assert z.shape[0] == 16 and cls_z is None
     assert torch.equal(sets["pr"]["desc"], Fn.nn_pack(gan.generate(z, cls_z, ema=True), plan.f))
-    assert torch.equal(real["desc"], Fn.nn_pack(torch.cat(list(gan.prdc_real_batches(plan))), plan.f))
+    assert torch.equal(real["desc"], Fn.nn_pack(torch.cat(list(gan.monitor_real_batches(plan))), plan.f))
     assert _within_bands(first, "", real, sets["pr"], 3)
     # --sample_ema both: the live weights under their own tags
     gan.generate_noema_samples = True
@@ -335,7 +335,7 @@ def test_model_scores_agree_with_the_reference_and_leave_the_run_alone(tmp_path)
     assert all(both[k] == first[k] for k in first)
     assert torch.equal(sets["pr_noema"]["desc"], Fn.nn_pack(gan.generate(z, cls_z, ema=False), plan.f))
     assert _within_bands(both, "_noema", real, sets["pr_noema"], 3)
-    assert gan._prdc.real is real                           # the real set is measured once
+    assert gan._monitors["prdc"].real is real                 # the real set is measured once
     _same_state(gan, snap)
 
 
@@ -347,9 +347,9 @@ def test_the_real_set_is_the_first_files_without_flips(tmp_path):
     for i in range(9):
         utils.write_png(rng.randint(0, 256, size=(70, 80, 3)).astype(np.uint8), str(root / "toy" / ("%02d.png" % i)))
     gan = _model(tmp_path, "files", dataset="toy", pr_size=32)
-    plan = gan.prdc_plan(str(root))
+    plan = gan.monitor_plan("prdc", str(root))
     assert plan.from_files and (plan.N, plan.M, plan.f, plan.D) == (9, 16, 2, 32 * 32 * 3)
-    files = gan._swd_files(str(root))
+    files = gan._dataset_files(str(root))
     want = np.stack([D.ImageData(64, 3, True, False).image_processing(f) for f in files[:9]])
     scores, runner, sets = gan.prdc(str(root), details=True)
     assert torch.equal(runner.real["desc"], Fn.nn_pack(torch.from_numpy(want).cuda(), 2))
@@ -395,7 +395,7 @@ def test_training_state_and_losses_with_the_check_are_bit_identical(run_pair):
         assert torch.equal(a[k], b[k]), k
     assert any(k.endswith("/u") for k in a) and any(k.endswith("/Adam_1") for k in a)
     assert torch.equal(scored.gen.get_state(), plain.gen.get_state()) and scored.counter == plain.counter == 3
-    assert plain._prdc is None and scored._prdc is not None
+    assert plain._monitors.get("prdc") is None and scored._monitors.get("prdc") is not None
     assert len(run_pair["seen"]) == 3 and run_pair["seen"] == run_pair["seen2"]
 
 

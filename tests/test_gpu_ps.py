@@ -236,12 +236,12 @@ def test_model_scores_agree_with_the_reference_and_leave_the_run_alone(tmp_path)
     assert np.array_equal(np.random.get_state()[1], np_state)
     assert list(first) == ["ps_dist", "ps_hf", "ps_peak", "ps_peak_at"] and second == first
     # the same images through the float64 restatement: 8 images in batches of 4
-    plan = gan.ps_plan()
+    plan = gan.monitor_plan("ps")
     assert plan.n_images == 8 and not plan.from_files and plan.n_real == 8
-    z, cls_z = gan.ps_fake_inputs(plan)
+    z, cls_z = gan.monitor_fake_inputs(plan)
     assert z.shape[0] == 8 and cls_z is None
     fake = gan.generate(z, cls_z, ema=True).float().cpu().numpy()
-    real = torch.cat(list(gan.ps_real_batches(plan))).cpu().numpy()
+    real = torch.cat(list(gan.monitor_real_batches(plan))).cpu().numpy()
     want, gate = _reference_with_its_own_gate(real, fake)
     print("device %s\nreference %s\ngates %s" % (first, want, gate))
     assert first["ps_peak_at"] == want["ps_peak_at"]
@@ -267,16 +267,16 @@ def test_the_real_set_is_the_first_files_without_flips(tmp_path):
     for i in range(5):
         utils.write_png(rng.randint(0, 256, size=(70, 80, 3)).astype(np.uint8), str(root / "toy" / ("%02d.png" % i)))
     gan = _model(tmp_path, "files", dataset="toy")
-    plan = gan.ps_plan(str(root))
+    plan = gan.monitor_plan("ps", str(root))
     assert plan.from_files and plan.n_real == 5 and plan.n_images == 8
-    files = gan._swd_files(str(root))
-    real = torch.cat(list(gan.ps_real_batches(plan, str(root))))
+    files = gan._dataset_files(str(root))
+    real = torch.cat(list(gan.monitor_real_batches(plan, str(root))))
     want = np.stack([D.ImageData(64, 3, True, False).image_processing(f) for f in files[:5]])
     assert np.array_equal(real.cpu().numpy(), want)
     scores = gan.power_spectrum(str(root))
-    assert gan._ps.real["n"] == 5
+    assert gan._monitors["ps"].real["n"] == 5
     ref = R.reference(want)
-    assert np.abs(gan._ps.real["profile"] / R.set_profile(ref["profiles"]) - 1.0)[R.significant(ref).all(axis=0)].max() \
+    assert np.abs(gan._monitors["ps"].real["profile"] / R.set_profile(ref["profiles"]) - 1.0)[R.significant(ref).all(axis=0)].max() \
         <= R.PROFILE_GATE
     assert set(scores) == {"ps_dist", "ps_hf", "ps_peak", "ps_peak_at"}
 
@@ -320,7 +320,7 @@ def test_training_state_and_losses_with_the_check_are_bit_identical(run_pair):
         assert torch.equal(a[k], b[k]), k
     assert any(k.endswith("/u") for k in a) and any(k.endswith("/Adam_1") for k in a)
     assert torch.equal(scored.gen.get_state(), plain.gen.get_state()) and scored.counter == plain.counter == 3
-    assert plain._ps is None and scored._ps is not None
+    assert plain._monitors.get("ps") is None and scored._monitors.get("ps") is not None
     assert len(run_pair["seen"]) == 3 and run_pair["seen"] == run_pair["seen2"]
 
 

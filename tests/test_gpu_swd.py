@@ -272,11 +272,11 @@ def test_model_scores_agree_with_the_reference_and_leave_the_run_alone(tmp_path)
     assert list(first) == ["swd_64", "swd_32", "swd_16", "swd_avg"] and all(np.isfinite(v) for v in first.values())
     assert first == second
     # the same images, positions and directions through the float64 restatement
-    plan = gan.swd_plan()
+    plan = gan.monitor_plan("swd")
     assert plan.n_images == 8 and not plan.from_files
-    z, cls_z = gan.swd_fake_inputs(plan)
+    z, cls_z = gan.monitor_fake_inputs(plan)
     fake = _n64(gan.generate(z, cls_z, ema=True))
-    real = _n64(torch.cat(list(gan.swd_real_batches(plan))))
+    real = _n64(torch.cat(list(gan.monitor_real_batches(plan))))
     _same_state(gan, snap)
     pos_r, pos_f, dirs = plan.draw_positions("real"), plan.draw_positions("fake"), plan.draw_directions()
     lr, lf = R.laplacian_pyramid(real), R.laplacian_pyramid(fake)
@@ -303,16 +303,16 @@ def test_the_real_set_is_the_first_files_of_the_dataset_without_flips(tmp_path):
     for i in range(5):
         utils.write_png(rng.randint(0, 256, size=(70, 80, 3)).astype(np.uint8), str(root / "toy" / ("%02d.png" % i)))
     gan = _model(tmp_path, "files", dataset="toy")
-    plan = gan.swd_plan(str(root))
+    plan = gan.monitor_plan("swd", str(root))
     assert plan.from_files and plan.n_images == 4                   # min(8 asked, 5 files) rounded down to a power of two
-    files = gan._swd_files(str(root))
+    files = gan._dataset_files(str(root))
     assert [os.path.basename(f) for f in files] == ["%02d.png" % i for i in range(5)]
-    real = torch.cat(list(gan.swd_real_batches(plan, str(root))))
+    real = torch.cat(list(gan.monitor_real_batches(plan, str(root))))
     want = np.stack([D.ImageData(64, 3, True, False).image_processing(f) for f in files[:4]])
     assert np.array_equal(real.cpu().numpy(), want)
     scores = gan.swd(str(root))
     assert list(scores) == ["swd_64", "swd_32", "swd_16", "swd_avg"] and all(np.isfinite(v) for v in scores.values())
-    assert gan._swd.plan.n_images == 4 and gan.swd(str(root)) == scores
+    assert gan._monitors["swd"].plan.n_images == 4 and gan.swd(str(root)) == scores
 
 
 def _train(tmp_path, tag, swd_freq, **kw):
@@ -357,7 +357,7 @@ def test_training_state_with_the_score_is_bit_identical(run_pair):
     assert any(k.endswith("/u") for k in a) and any(k.endswith("/Adam_1") for k in a)
     assert any(k.endswith("/ExponentialMovingAverage") for k in a)
     assert torch.equal(scored.gen.get_state(), plain.gen.get_state()) and scored.counter == plain.counter == 3
-    assert plain._swd is None and scored._swd is not None
+    assert plain._monitors.get("swd") is None and scored._monitors.get("swd") is not None
 
 
 def test_training_losses_with_the_score_are_bit_identical(run_pair):

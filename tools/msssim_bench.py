@@ -59,9 +59,9 @@ def _measure(a):
         torch.cuda.synchronize()
         return start.elapsed_time(stop) / reps
 
-    plan = gan.msssim_plan()
+    plan = gan.monitor_plan("msssim")
     H, C, levels = plan.img_size, plan.c_dim, len(plan.sides)
-    z, cls_z = gan.msssim_fake_inputs(plan)
+    z, cls_z = gan.monitor_fake_inputs(plan)
 
     def sweep():
         batches = []

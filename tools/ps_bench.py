@@ -63,9 +63,9 @@ def _measure(a):
         torch.cuda.synchronize()
         return start.elapsed_time(stop) / reps
 
-    plan = gan.ps_plan()
+    plan = gan.monitor_plan("ps")
     side, W, nb = plan.side, plan.side // 2 + 1, plan.n_bins
-    z, cls_z = gan.ps_fake_inputs(plan)
+    z, cls_z = gan.monitor_fake_inputs(plan)
 
     def sweep():
         batches = []
@@ -91,7 +91,7 @@ def _measure(a):
             lo += p.shape[0]
     profile_ms = device_timed(profile)
     first = gan.power_spectrum()                                       # draws, the real set
-    runner = gan._ps
+    runner = gan._monitors["ps"]
 
     def tail():
         rows = profiles.cpu().numpy()

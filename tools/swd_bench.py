@@ -48,13 +48,13 @@ def _measure(a):
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / reps, r
 
-    plan = gan.swd_plan()
+    plan = gan.monitor_plan("swd")
     levels = len(plan.sides)
     m = metrics.Swd(plan, "cuda")
 
     def real_set():
         m.begin("real")
-        for batch in gan.swd_real_batches(plan):
+        for batch in gan.monitor_real_batches(plan):
             m.add(batch)
         return m.finish()
 
@@ -63,7 +63,7 @@ def _measure(a):
     m.real = real_set()
     torch.cuda.synchronize()
     real_ms = (time.perf_counter() - t0) * 1e3                       # one-time: timed cold, as a run pays it
-    z, cls_z = gan.swd_fake_inputs(plan)
+    z, cls_z = gan.monitor_fake_inputs(plan)
 
     def sweep():
         batches = []
