@@ -5,18 +5,9 @@
 //   distances   out[i,n] = sum_j (q[i,j] - set[n,j])^2 over bf16 rows, computed as differences in fp32
 //   topk        the k <= 16 smallest (value, index) pairs of every fp32 row, ascending, ties to the lower index
 //
-// The distance kernel.  The squared distance is not expanded into |q|^2 + |s|^2 - 2 q.s: for a near-copy d << |q|^2 and
-// the expansion cancels exactly where the answer matters, so there is no MFMA here, only fp32 differences, and a set row
-// that equals a query gives 0.0f.  A block of 256 threads owns NN_ROWS = 16 set rows, four per wave.  Per query tile of
-// NN_QT = 8 queries and per chunk of NN_DC = 2048 elements it stages the queries' chunk in LDS (32 KiB, rows of 4 KiB), then
-// every wave walks the chunk 512 elements at a time: lane l holds elements [8 l, 8 l + 8) of its four set rows from one
-// 16-byte global load each, reads the same 16 bytes of each query from LDS (lane-contiguous, so every 16-lane group of a
-// ds_read_b128 covers the 64 banks once), and adds (q - s)^2 into 8 x 4 accumulators of two floats (even and odd
-// elements, the shape of v_pk_add_f32 / v_pk_fma_f32).  LDS bytes are NN_QT / 4 = 2 x the HBM bytes.  Lanes past the end
-// of a row (D is a multiple of 64, not of 512) take zeros for both operands.  After the last chunk the 32 sums of a lane go
-// through a transposing butterfly: at distance 32, 16, 8, 4, 2 a lane keeps one half of its values and adds the other
-// half's counterpart from its partner, so that 31 shuffles leave one value per lane, and one more at distance 1 finishes
-// it.  Every (i, n) sum is thus made by one wave in one fixed order: no atomics, no partials across blocks, and two
+// The distance kernel.  A block owns 16 set rows and walks the queries in tiles of 8 with the row walker of rowdist.h,
+// which describes the arithmetic, the tiling and the order of summation; the even lane of each lane pair stores its tile's
+// d(i, n).  Every (i, n) sum is made by one wave in one fixed order: no atomics, no partials across blocks, and two
 // launches give the same bits.
 //
 // The selection.  A thread scans its part of a row with a stride of 256 and keeps its K best in registers (an unrolled
@@ -24,20 +15,15 @@
 // than NN_TK_SEG are split over blocks, whose lists go through a workspace into a second pass of the same kernel.  The
 // order on (value, index) is total, so the result does not depend on how the row was split.
 #include "common.h"
+#include "rowdist.h"
 
 #include <math.h>
 
 namespace bg {
 
-#define NN_BLOCK 256
-#define NN_QT 8
-#define NN_RW 4                      // set rows per wave
-#define NN_ROWS (4 * NN_RW)          // set rows per block
-#define NN_DC 2048                   // elements of a query row staged per pass
+#define NN_BLOCK 256                 // the pack and selection kernels
 #define NN_TK_SEG 16384              // elements of a row per block of the first selection pass
 #define NN_TK_MAX_SPLITS 256
-
-typedef float nn_f2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float nn_widen(float v) { return v; }
 __device__ __forceinline__ float nn_widen(uint16_t bits) { return __uint_as_float((uint32_t)bits << 16); }   // bf16, exact
@@ -71,96 +57,19 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_pack_kernel(const T* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------- distances
-__device__ __forceinline__ void nn_unpack(const uint4& w, nn_f2 (&v)[4]) {
-    v[0] = nn_f2{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u)};
-    v[1] = nn_f2{__uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
-    v[2] = nn_f2{__uint_as_float(w.z << 16), __uint_as_float(w.z & 0xffff0000u)};
-    v[3] = nn_f2{__uint_as_float(w.w << 16), __uint_as_float(w.w & 0xffff0000u)};
-}
-
-// one step of the transposing butterfly: HALF values stay, each plus the partner lane's counterpart of the other half
-template <int HALF>
-__device__ __forceinline__ void nn_fold(float (&v)[NN_QT * NN_RW], int lane) {
-    const bool hi = (lane & (HALF == 16 ? 32 : HALF == 8 ? 16 : HALF == 4 ? 8 : HALF == 2 ? 4 : 2)) != 0;
-    constexpr int dist = HALF == 16 ? 32 : HALF == 8 ? 16 : HALF == 4 ? 8 : HALF == 2 ? 4 : 2;
-#pragma unroll
-    for (int i = 0; i < HALF; ++i) {
-        const float keep = hi ? v[i + HALF] : v[i];
-        const float send = hi ? v[i] : v[i + HALF];
-        v[i] = keep + __shfl_xor(send, dist, 64);
-    }
-}
-
-__global__ __launch_bounds__(NN_BLOCK) void nn_distances_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ set,
+__global__ __launch_bounds__(RD_BLOCK) void nn_distances_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ set,
                                                                 int Q, int64_t N, int D, float* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) uint16_t qs[NN_QT * NN_DC];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int64_t row0 = (int64_t)blockIdx.x * NN_ROWS + wave * NN_RW;
-    const uint16_t* rows[NN_RW];
-#pragma unroll
-    for (int r = 0; r < NN_RW; ++r) {
-        const int64_t n = row0 + r < N ? row0 + r : N - 1;          // rows past the end repeat the last one; not stored
-        rows[r] = set + n * D;
-    }
-    for (int q0 = 0; q0 < Q; q0 += NN_QT) {
-        nn_f2 acc[NN_QT][NN_RW];
-#pragma unroll
-        for (int i = 0; i < NN_QT; ++i)
-#pragma unroll
-            for (int r = 0; r < NN_RW; ++r) acc[i][r] = nn_f2{0.0f, 0.0f};
-        for (int c0 = 0; c0 < D; c0 += NN_DC) {
-            const int len = D - c0 < NN_DC ? D - c0 : NN_DC;        // a multiple of 8
-            __syncthreads();                                        // the previous chunk has been read
-#pragma unroll
-            for (int i = 0; i < NN_QT; ++i) {
-                const bool have = q0 + i < Q;                       // queries past the end are zeros; not stored
-                const uint16_t* src = q + (int64_t)(have ? q0 + i : 0) * D + c0;
-                for (int o = t * 8; o < len; o += NN_BLOCK * 8) {
-                    uint4 w = *reinterpret_cast<const uint4*>(src + o);
-                    if (!have) w = uint4{0u, 0u, 0u, 0u};
-                    *reinterpret_cast<uint4*>(&qs[i * NN_DC + o]) = w;
-                }
-            }
-            __syncthreads();
-            for (int o = lane * 8; o < len + lane * 8; o += 512) {  // every lane of the wave makes the same number of turns
-                const bool in = o < len;
-                nn_f2 sv[NN_RW][4];
-#pragma unroll
-                for (int r = 0; r < NN_RW; ++r) {
-                    uint4 w = uint4{0u, 0u, 0u, 0u};
-                    if (in) w = *reinterpret_cast<const uint4*>(rows[r] + c0 + o);
-                    nn_unpack(w, sv[r]);
-                }
-#pragma unroll
-                for (int i = 0; i < NN_QT; ++i) {
-                    uint4 w = uint4{0u, 0u, 0u, 0u};
-                    if (in) w = *reinterpret_cast<const uint4*>(&qs[i * NN_DC + o]);
-                    nn_f2 qv[4];
-                    nn_unpack(w, qv);
-#pragma unroll
-                    for (int r = 0; r < NN_RW; ++r)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const nn_f2 d = qv[j] - sv[r][j];
-                            acc[i][r] = __builtin_elementwise_fma(d, d, acc[i][r]);
-                        }
-                }
-            }
-        }
-        float v[NN_QT * NN_RW];
-#pragma unroll
-        for (int i = 0; i < NN_QT; ++i)
-#pragma unroll
-            for (int r = 0; r < NN_RW; ++r) v[i * NN_RW + r] = acc[i][r].x + acc[i][r].y;
-        nn_fold<16>(v, lane);
-        nn_fold<8>(v, lane);
-        nn_fold<4>(v, lane);
-        nn_fold<2>(v, lane);
-        nn_fold<1>(v, lane);
-        const float sum = v[0] + __shfl_xor(v[0], 1, 64);
-        const int slot = lane >> 1;                                  // lane bits 5..1 = the index i * NN_RW + r it ended with
-        const int i = slot / NN_RW, r = slot % NN_RW;
-        if ((lane & 1) == 0 && q0 + i < Q && row0 + r < N) out[(int64_t)(q0 + i) * N + row0 + r] = sum;
+    const int64_t row0 = (int64_t)blockIdx.x * RD_ROWS + wave * RD_RW;
+    const uint16_t* rows[RD_RW];
+    rd_rows(set, N, D, row0, rows);
+    const int i = lane >> 3;                                         // the lane pair's query slot and row (rd_tile)
+    const int64_t n = row0 + ((lane >> 1) & 3);
+    RowsAhead ahead;
+    rd_prologue(ahead, rows, D, lane);
+    for (int q0 = 0; q0 < Q; q0 += RD_QT) {
+        const float d = rd_tile(ahead, q, q0, Q, rows, D, t, lane);
+        if ((lane & 1) == 0 && q0 + i < Q && n < N) out[(int64_t)(q0 + i) * N + n] = d;
     }
 }
 
@@ -294,11 +203,11 @@ int bg_nn_pack(const void* x, int x_dtype, int B, int S, int C, int f, int mirro
 
 int bg_nn_distances(const void* q, const void* set, int Q, int64_t N, int D, float* out, void* stream) {
     BG_REQUIRE(q && set && out, "bg_nn_distances: NULL pointer");
-    BG_REQUIRE(Q > 0 && N > 0 && (N + NN_ROWS - 1) / NN_ROWS <= 0x7fffffffLL, "bg_nn_distances: Q=%d N=%lld", Q, (long long)N);
+    BG_REQUIRE(Q > 0 && N > 0 && (N + RD_ROWS - 1) / RD_ROWS <= 0x7fffffffLL, "bg_nn_distances: Q=%d N=%lld", Q, (long long)N);
     BG_REQUIRE(D >= 64 && D % 64 == 0, "bg_nn_distances: D=%d (a multiple of 64)", D);
     BG_REQUIRE((((uintptr_t)q | (uintptr_t)set) & 15) == 0 && ((uintptr_t)out & 3) == 0,
                "bg_nn_distances: q and set must be 16-byte aligned");
-    hipLaunchKernelGGL(nn_distances_kernel, dim3((unsigned)((N + NN_ROWS - 1) / NN_ROWS)), dim3(NN_BLOCK), 0, as_stream(stream),
+    hipLaunchKernelGGL(nn_distances_kernel, dim3((unsigned)((N + RD_ROWS - 1) / RD_ROWS)), dim3(RD_BLOCK), 0, as_stream(stream),
                        static_cast<const uint16_t*>(q), static_cast<const uint16_t*>(set), Q, N, D, out);
     BG_LAUNCH_CHECK();
     return BG_OK;

@@ -23,7 +23,7 @@ Prints one JSON line, ms per event (mean of --reps after one untimed pass):
                     k-th column; pairs_ms is bg_nn_distances of the real slab against the generated set and torch
                     comparisons on the matrix, which serve both directions at once (count per column, count and minimum
                     per row); total_ms their sum with the torch reduction.  ``equal``: the four integers are the fused ones
-                    (the two distance kernels share their arithmetic, so they must be)
+                    (the two kernels call one function)
 
 The measurement runs in a child process under its own time limit (--timeout seconds); host work uses at most 16 threads.
 """
